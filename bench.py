@@ -19,7 +19,8 @@ Workload at N=1: BASELINE config 2 — the Mip-NeRF360 garden .ply is not availa
 synthetic scene of SURVEY.md §8d stands in (same splat count, labelled so), at the reference's default pose. Extra keys
 at N=1 (measured after, and outside, the timed region of the headline): the same scene from a pose outside the cloud,
 and from far away, a blend-bound variant (opacities x 0.1) and the forward-only mode without the sorted lists.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0. --dump-outputs DIR also writes what the last timed step returned as DIR/<name>.npy; the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -44,6 +45,7 @@ import torch
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 measured-achievable
 N_SIMD = 1024              # 256 CUs x 4 SIMDs
 DEFAULT_SPLATS = 5_834_784
+DUMP_BYTES = 64 << 20      # --dump-outputs: the most written in all
 
 
 def parse_args():
@@ -93,7 +95,14 @@ def parse_args():
     p.add_argument("--dry-run", action="store_true",
                    help="launcher / rendezvous / band-exchange plumbing check on CPU over gloo: renders nothing, measures "
                         "nothing, prints a line with value null")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default="",
+                   help="after the timed steps, write what the last of them returned to its caller (the image, num_rendered and, "
+                        "with --backward, the gradients) as DIR/<name>.npy, float32 or float64, at most 64 MB in all "
+                        "(sample_outputs); rank 0 only")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 # ---- launching N ranks ------------------------------------------------------------------------------------------------
@@ -231,6 +240,35 @@ def cpu_baseline(scene, cam, every: int):
     }
 
 
+def sample_outputs(arrays: dict) -> dict:
+    """name -> tensor, in float32 (float64 where the array is float64 or int64), at most DUMP_BYTES in all. An array larger
+    than its share of that is reduced to the elements (flattened) at positions drawn with seed 0 from its size alone, so
+    that two builds run with the same arguments keep the same positions. Returns name -> (copy, what it holds)."""
+    out, left = {}, DUMP_BYTES
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())       # (the small ones first: what they leave is shared out)
+    for i, (name, t) in enumerate(items):
+        dtype = torch.float64 if t.dtype in (torch.float64, torch.int64) else torch.float32
+        share = left // (len(items) - i) // (8 if dtype == torch.float64 else 4)
+        n = t.numel()
+        if n > share:
+            idx = np.unique(np.random.default_rng(0).integers(0, n, share))
+            c = t.reshape(-1)[torch.from_numpy(idx).to(t.device)].to(dtype)
+            what = f"{idx.size} of {n} elements (flattened, seed 0)"
+        else:
+            c = t.to(dtype, copy=True)
+            what = f"all {n} elements"
+        out[name] = (c, what)
+        left -= c.numel() * c.element_size()
+    return out
+
+
+def write_outputs(path: str, outputs: dict) -> None:
+    os.makedirs(path, exist_ok=True)
+    for name, (c, what) in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), c.cpu().numpy())
+        print(f"bench.py: {os.path.join(path, name + '.npy')}: {what}", file=sys.stderr)
+
+
 class Runner:
     """One rasterizer + (when sharded) its band exchange; `measure` times K steps of it."""
 
@@ -246,6 +284,7 @@ class Runner:
         self.dl_dout = None
         self.bw_ms = [0.0, 0.0]
         self.bw_outputs = None              # gsr_backward's optional outputs: None = every array
+        self.grads = None                   # what the last step's backward returned (owned by the rasterizer)
         self.split_ms = [0.0, 0.0]          # sharded runs: device time of the render and of the band exchange (HIP events, profiled frames)
 
     def step(self, cam, profile=False, **kw):
@@ -258,9 +297,10 @@ class Runner:
         frame = rast.draw(cam, profile=profile, tile_rows=rows, sync=not self.distributed, **kw)
         if timed:
             ev[1].record()
+        self.grads = None
         if self.dl_dout is not None:
-            rast.backward(self.dl_dout, profile=profile, semantics=kw.get("semantics", "gscuda"), sh_degree=kw.get("sh_degree", 3),
-                          wide_sums=os.environ.get("GSR_BW_WIDE_SUMS", "1") != "0", outputs=self.bw_outputs)
+            self.grads = rast.backward(self.dl_dout, profile=profile, semantics=kw.get("semantics", "gscuda"), sh_degree=kw.get("sh_degree", 3),
+                                       wide_sums=os.environ.get("GSR_BW_WIDE_SUMS", "1") != "0", outputs=self.bw_outputs)
             if profile:
                 self.bw_ms[0] += rast.last_backward_ms[0]
                 self.bw_ms[1] += rast.last_backward_ms[1]
@@ -282,7 +322,9 @@ class Runner:
             dist.barrier()
             torch.cuda.synchronize(self.device)
 
-    def measure(self, cam, steps, warmup, **kw):
+    def measure(self, cam, steps, warmup, keep_outputs=False, **kw):
+        """keep_outputs: out["outputs"] holds device copies of what the last timed step returned (sample_outputs), taken
+        after the timed region."""
         rast, exch = self.rast, self.exch
 
         def counted_frame():
@@ -320,10 +362,15 @@ class Runner:
         t0 = time.perf_counter()
         stamps = [t0]
         for _ in range(steps):
-            self.step(cam, **kw)                    # (ends with the stream's synchronise: a step's work is complete when it returns)
+            frame = self.step(cam, **kw)            # (ends with the stream's synchronise: a step's work is complete when it returns)
             stamps.append(time.perf_counter())
         self.sync_all()
         out["elapsed"] = time.perf_counter() - t0
+        if keep_outputs:
+            # (before the profiled frames below, which write the same buffers)
+            arrays = {"out_color": frame, "num_rendered": torch.tensor([rast.last_num_rendered], dtype=torch.float64)}
+            arrays.update(self.grads or {})
+            out["outputs"] = sample_outputs(arrays)
         per_step = np.diff(np.asarray(stamps)) * 1e3
         out["ms_median"], out["ms_p99"] = float(np.median(per_step)), float(np.percentile(per_step, 99))
         out["tiles_reordered"] = bool(rast.last_tiles_reordered)
@@ -655,7 +702,7 @@ def main() -> int:
                    semantics=args.semantics, sh_degree=args.sh_degree,
                    sorted_lists=not args.no_sorted_lists, colors_precomp=args.colors_precomp, tile_history=not args.no_tile_history,
                    deep_tiles=False if args.no_deep_tiles else None)
-    m = run.measure(cam, args.steps, args.warmup, **draw_kw)
+    m = run.measure(cam, args.steps, args.warmup, keep_outputs=bool(args.dump_outputs) and rank == 0, **draw_kw)
 
     # (extras and the committed PMC figures belong to the default workload; with --ply the frame is the file's)
     default_frame = (not from_file and args.scene == "garden_like" and args.splats == DEFAULT_SPLATS and (W, H) == (1920, 1080) and not args.pose
@@ -901,6 +948,8 @@ def main() -> int:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, m["outputs"])
         sys.stdout.flush()
         print(json.dumps(out), flush=True)          # the ONE JSON line, last thing on stdout
     return 0

@@ -44,3 +44,28 @@ def test_world_size_must_match_gpus():
 def test_single_gpu_run_without_a_device_fails_loudly():
     p = _run("--gpus", "1", "--steps", "1")
     assert p.returncode != 0 and p.stdout.strip() == "" and "no CPU path" in p.stderr
+
+
+def test_steps_below_one_are_refused():
+    p = _run("--steps", "0")
+    assert p.returncode != 0 and p.stdout.strip() == "" and "--steps" in p.stderr
+
+
+def test_dumped_outputs_fit_the_limit_and_keep_their_positions():
+    """bench.py --dump-outputs: arrays beyond their share of 64 MB are sampled at positions fixed by their size, so two
+    builds run with the same arguments write comparable files; small arrays are written whole, in their shape."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(1)
+    arrays = {"out_color": torch.rand((3, 1080, 1920), generator=g), "num_rendered": torch.tensor([7.0], dtype=torch.float64),
+              "dL_dshs": torch.rand((1_000_000, 48), generator=g), "counts": torch.arange(10, dtype=torch.int64)}
+    a, b = bench.sample_outputs(arrays), bench.sample_outputs({k: v.clone() for k, v in arrays.items()})
+    assert sum(c.numel() * c.element_size() for c, _ in a.values()) <= bench.DUMP_BYTES
+    assert a["num_rendered"][0].dtype == torch.float64 and a["counts"][0].dtype == torch.float64
+    assert torch.equal(a["counts"][0], arrays["counts"].double()) and a["out_color"][0].dtype == torch.float32
+    for k in arrays:
+        assert torch.equal(a[k][0], b[k][0]), k
+    c = a["dL_dshs"][0]
+    assert 0 < c.numel() < arrays["dL_dshs"].numel() and bool(np.isin(c.numpy(), arrays["dL_dshs"].numpy()).all())

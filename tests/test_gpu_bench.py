@@ -87,3 +87,27 @@ def test_sharded_path_forced_onto_one_rank():
     # the split a poor N-GPU number would be attributed with: device time of the render and of the exchange behind it
     assert pr["render_ms"] > 0.0 and pr["exchange_ms"] >= 0.0 and pr["render_ms"] <= 1.5 * pr["ms_per_step"] + 0.2
     assert pr["num_rendered"] == cfg["num_rendered"] > 0
+
+
+def test_dump_outputs_writes_the_last_timed_frame(tmp_path):
+    """--dump-outputs DIR: the image and num_rendered of the last timed step, as the C++ oracle computes them for the same
+    seeded scene and camera; with --backward the gradients beside them, 64 MB in all at most."""
+    import numpy as np
+    from gsrast_amd import camera, scenes
+    from oracle import cpu_oracle
+    d = tmp_path / "fwd"
+    j = _run_bench({}, "--scene", "isotropic", "--width", "128", "--height", "128", "--no-extras", "--dump-outputs", str(d),
+                   splats="1000")
+    assert j["steps"] == 3
+    exp = cpu_oracle.forward(scenes.isotropic_scene(1000, 42), camera.default_camera(128, 128))
+    img, nr = np.load(d / "out_color.npy"), np.load(d / "num_rendered.npy")
+    assert img.dtype == np.float32 and img.shape == (3, 128, 128) and nr.dtype == np.float64
+    assert int(nr[0]) == exp["num_rendered"] == j["config"]["num_rendered"]
+    assert float(np.abs(img - exp["out_color"]).max()) <= 1e-4
+    b = tmp_path / "bwd"
+    _run_bench({}, "--backward", "--no-extras", "--dump-outputs", str(b))
+    files = {p.name: np.load(p) for p in b.iterdir()}
+    assert {"out_color.npy", "num_rendered.npy", "dL_dmean2D.npy", "dL_dshs.npy", "dL_dmeans3D.npy"} <= set(files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert any(np.abs(a).max() > 0 for k, a in files.items() if k.startswith("dL_"))
