@@ -112,7 +112,8 @@ def blend_backward(means2D, conic_opacity, colors, ranges, point_list, n_contrib
     return {"dL_dmean2D": d_mean, "dL_dconic": d_conic, "dL_dopacity": d_op, "dL_dcolor": d_col}
 
 
-def blend_tile_backward(xy, co, col, tx, ty, width, height, background, dL_dout_tile, t_cutoff=0.001, f32_forward=False):
+def blend_tile_backward(xy, co, col, tx, ty, width, height, background, dL_dout_tile, t_cutoff=0.001, f32_forward=False,
+                        magnitudes=False):
     """One 16 x 16 tile, vectorised [L records x 256 pixels], float64: the forward loop of `blend_forward` and the
     gradients of `blend_backward` restricted to this tile's pixels. Used at frame sizes where the per-pixel
     Python loops above would take hours; tests/test_backward_oracle.py checks it against them.
@@ -126,7 +127,15 @@ def blend_tile_backward(xy, co, col, tx, ty, width, height, background, dL_dout_
     f32_forward: power, exp (libm's expf), alpha and the transmittance product are evaluated in float32 in the forward's
     operation order (GSCuda.cu:634-657) — the function the HIP backward differentiates, decisions included: with terms of
     1e3 in the power of a screen-filling splat a float64 forward is another function at the 1e-4 level — and the gradient
-    sums over them in float64: what remains against the HIP backward is the backward's own arithmetic."""
+    sums over them in float64: what remains against the HIP backward is the backward's own arithmetic.
+    magnitudes: also returns, per record, the condition scale of each sum — M_mean [L,2], M_conic [L,3], M_cov [L,3], M_op [L],
+    M_col [L,3]: the same sums with every factor replaced by its absolute value (dL/dalpha becomes
+    |T_before cg| + |behind / (1 - alpha)|, cg and `behind` themselves sums of absolute values), so M >= |sum| componentwise and
+    a floating-point evaluation of the sum errs by a few units of rounding times M whatever cancels inside it —; `k` [L]: the
+    walk depth, over the record's contributing pixels the largest number of contributing records from it to the pixel's last
+    contributor (itself included) — how many reciprocals a back-to-front walk applies to rebuild the T the record saw;
+    `pixels` / `free_pixels` [L]: its contributing pixels, and those of them where alpha is not clamped (raw <= 0.99); and per
+    pixel `stop_idx` [16,16]: the list position of the record that ended the pixel (the transmittance test), -1 if none."""
     xy = np.asarray(xy, np.float64).reshape(-1, 2)
     co = np.asarray(co, np.float64).reshape(-1, 4)
     col = np.asarray(col, np.float64).reshape(-1, 3)
@@ -139,9 +148,14 @@ def blend_tile_backward(xy, co, col, tx, ty, width, height, background, dL_dout_
     gp = np.asarray(dL_dout_tile, np.float64).reshape(3, -1) * inside[None, :]
     if L == 0:
         out = np.where(inside[None, :], bg[:, None], 0.0)
-        return {"d_mean": np.zeros((0, 2)), "d_conic": np.zeros((0, 3)), "d_cov": np.zeros((0, 3)), "d_op": np.zeros(0), "d_col": np.zeros((0, 3)),
-                "out": out.reshape(3, TILE, TILE), "final_t": inside.astype(np.float64).reshape(TILE, TILE),
-                "n_contrib": np.zeros((TILE, TILE), np.int64)}
+        res = {"d_mean": np.zeros((0, 2)), "d_conic": np.zeros((0, 3)), "d_cov": np.zeros((0, 3)), "d_op": np.zeros(0), "d_col": np.zeros((0, 3)),
+               "out": out.reshape(3, TILE, TILE), "final_t": inside.astype(np.float64).reshape(TILE, TILE),
+               "n_contrib": np.zeros((TILE, TILE), np.int64)}
+        if magnitudes:
+            res.update(M_mean=np.zeros((0, 2)), M_conic=np.zeros((0, 3)), M_cov=np.zeros((0, 3)), M_op=np.zeros(0), M_col=np.zeros((0, 3)),
+                       k=np.zeros(0, np.int64), pixels=np.zeros(0, np.int64), free_pixels=np.zeros(0, np.int64),
+                       stop_idx=np.full((TILE, TILE), -1, np.int64))
+        return res
     dx = xy[:, 0:1] - px[None, :]
     dy = xy[:, 1:2] - py[None, :]
     A, B, Cc, op = co[:, 0:1], co[:, 1:2], co[:, 2:3], co[:, 3:4]
@@ -191,9 +205,25 @@ def blend_tile_backward(xy, co, col, tx, ty, width, height, background, dL_dout_
     d_mean = np.stack([((-A * dx - B * dy) * dLp).sum(1), ((-Cc * dy - B * dx) * dLp).sum(1)], 1)
     ux, uy = A * dx + B * dy, B * dx + Cc * dy
     d_cov = np.stack([(0.5 * ux * ux * dLp).sum(1), (0.5 * ux * uy * dLp).sum(1), (0.5 * uy * uy * dLp).sum(1)], 1)
-    return {"d_mean": d_mean, "d_conic": d_conic, "d_cov": d_cov, "d_op": d_op, "d_col": d_col,
-            "out": np.where(inside[None, :], out, 0.0).reshape(3, TILE, TILE),
-            "final_t": np.where(inside, final_t, 0.0).reshape(TILE, TILE), "n_contrib": n_contrib.reshape(TILE, TILE)}
+    res = {"d_mean": d_mean, "d_conic": d_conic, "d_cov": d_cov, "d_op": d_op, "d_col": d_col,
+           "out": np.where(inside[None, :], out, 0.0).reshape(3, TILE, TILE),
+           "final_t": np.where(inside, final_t, 0.0).reshape(TILE, TILE), "n_contrib": n_contrib.reshape(TILE, TILE)}
+    if magnitudes:
+        ag = np.abs(gp)
+        cga = np.abs(col) @ ag
+        behind_a = (final_t * (np.abs(bg) @ ag))[None, :] + ((w * cga).sum(axis=0)[None, :] - np.cumsum(w * cga, axis=0))
+        dLa_a = np.where(free, t_before * cga + behind_a / (1.0 - np.where(free, alpha, 0.0)), 0.0)
+        dLp_a = op * G * dLa_a
+        adx, ady = np.abs(dx), np.abs(dy)
+        uxa, uya = np.abs(A) * adx + np.abs(B) * ady, np.abs(B) * adx + np.abs(Cc) * ady
+        walk = np.cumsum(contrib[::-1], axis=0)[::-1]               # contributing records from k to the pixel's last one
+        res.update(M_mean=np.stack([(uxa * dLp_a).sum(1), (uya * dLp_a).sum(1)], 1),
+                   M_conic=np.stack([(0.5 * adx * adx * dLp_a).sum(1), (adx * ady * dLp_a).sum(1), (0.5 * ady * ady * dLp_a).sum(1)], 1),
+                   M_cov=np.stack([(0.5 * uxa * uxa * dLp_a).sum(1), (0.5 * uxa * uya * dLp_a).sum(1), (0.5 * uya * uya * dLp_a).sum(1)], 1),
+                   M_op=(G * dLa_a).sum(axis=1), M_col=np.einsum("lp,cp->lc", w, ag),
+                   k=np.where(contrib, walk, 0).max(axis=1), pixels=contrib.sum(axis=1), free_pixels=free.sum(axis=1),
+                   stop_idx=np.where(has_stop & inside, stop_idx, -1).reshape(TILE, TILE))
+    return res
 
 
 # ---- cov3D -> conic (computeCov2D + inverse), and its gradient ------------------------------------

@@ -142,3 +142,166 @@ def check_backward_chain_inria(got, g, scene, cam, w, h, ids, deg, clamped):
         mag = np.maximum(np.abs(e).max(1), 1e-3 * np.abs(e).max())
         assert (err <= tol * np.maximum(mag, 1e-30)).all(), (name, float((err / np.maximum(mag, 1e-30)).max()))
     return [float(np.abs(e).max()) if m else 0.0 for e in (exp_cov, exp_mean, exp_scale, exp_rot, exp_sh)]
+
+
+_GRAD_KEYS = (("dL_dmean2D", "d_mean", "M_mean"), ("dL_dconic", "d_conic", "M_conic"), ("dL_dcov2D", "d_cov", "M_cov"),
+              ("dL_dopacity", "d_op", "M_op"), ("dL_dcolors", "d_col", "M_col"))
+
+
+def oracle_gradients(r, dL, bg, tiles, targets, max_depth, bad_pixels=None, f32_forward=False, magnitudes=False, t_cutoff=0.001,
+                     full_lists=False):
+    """Float64 gradients (oracle/backward_np.blend_tile_backward) of the Gaussians `targets`, summed over `tiles` (which must
+    contain every tile those Gaussians touch), from the forward state of the rasterizer `r` (its means2D, conics, colours and
+    sorted lists). Returns a dict:
+      exp      {dL_dmean2D [n,2], dL_dconic [n,3], dL_dcov2D [n,3], dL_dopacity [n,1], dL_dcolors [n,3]}
+      differs  (y, x) of every pixel whose last contributor differs from the GPU's nContrib
+    and with magnitudes=True also
+      M        the condition scale of every sum, keyed like exp (blend_tile_backward's M_*)
+      k        [n] walk depth (largest over the Gaussian's records); pixels, free_pixels [n]: contributing pixels, and those of
+               them where alpha is not clamped; tiles [n]: tiles where the Gaussian contributes
+      n_contrib, final_t  the oracle's per-pixel outputs [H,W] on the evaluated tiles (elsewhere -1 and NaN), stop_idx [H,W]
+    bad_pixels (a list, optional): receives (y, x) of every pixel on which the oracle's forward and the GPU's disagree —
+    another last contributor, or another transmittance (a record at alpha = 1/255 taken by one of them only).
+    full_lists: evaluate every tile's whole list (else the prefix that reaches the GPU's deepest last contributor of the tile:
+    enough when the GPU's nContrib is right, which the caller must then check on its own)."""
+    import torch
+    from oracle import backward_np as B
+    W, H = r.width, r.height
+    gx = (W + 15) // 16
+    geo = r.map_geometry_state()
+    ranges = r.map_image_state()["ranges"].cpu().numpy().view(np.uint32).astype(np.int64)
+    ncontrib = r.map_image_state()["nContrib"]
+    plist = r.map_binning_state()["values"]
+    final_t = r.map_image_state()["finalT"]
+    row_of = np.full(r.num_gaussians, -1, np.int64)
+    row_of[targets] = np.arange(len(targets))
+    n = len(targets)
+    dims = {"dL_dmean2D": 2, "dL_dconic": 3, "dL_dcov2D": 3, "dL_dopacity": 1, "dL_dcolors": 3}
+    sums = {k: np.zeros((n, d)) for k, d in dims.items()}
+    mags = {k: np.zeros((n, d)) for k, d in dims.items()}
+    k_walk, pixels, free_pixels, n_tiles = (np.zeros(n, np.int64) for _ in range(4))
+    nc_frame, ft_frame, stop_frame = np.full((H, W), -1, np.int64), np.full((H, W), np.nan), np.full((H, W), -1, np.int64)
+    differs_px = []
+    dL_host = dL.cpu().numpy() if hasattr(dL, "cpu") else np.asarray(dL)
+    for tx, ty in tiles:
+        t = ty * gx + tx
+        ya, yb, xa, xb = ty * 16, min(H, ty * 16 + 16), tx * 16, min(W, tx * 16 + 16)
+        nc_tile = ncontrib[ya:yb, xa:xb]
+        a = int(ranges[t, 0])
+        length = max(0, int(ranges[t, 1]) - a)
+        depth = length if full_lists else int(nc_tile.max())     # the list prefix that reaches every pixel's last contributor
+        assert depth <= length and depth <= max_depth, (depth, length, max_depth)
+        ids = plist[a:a + depth].to(torch.int64)
+        tile_g = np.zeros((3, 16, 16))
+        tile_g[:, : yb - ya, : xb - xa] = dL_host[:, ya:yb, xa:xb]
+        res = B.blend_tile_backward(geo["means2D"][ids].cpu().numpy(), geo["conicOpacity"][ids].cpu().numpy(),
+                                    geo["rgb"][ids].cpu().numpy(), tx, ty, W, H, bg, tile_g, t_cutoff=t_cutoff,
+                                    f32_forward=f32_forward, magnitudes=magnitudes)
+        differs = res["n_contrib"][: yb - ya, : xb - xa] != nc_tile.cpu().numpy()
+        bad = int(differs.sum())
+        differs_px.extend((ya + int(y), xa + int(x)) for y, x in zip(*np.nonzero(differs)))
+        if bad_pixels is not None:
+            ft = final_t[ya:yb, xa:xb].cpu().numpy().astype(np.float64)
+            differs = differs | (np.abs(res["final_t"][: yb - ya, : xb - xa] - ft) > 1e-5 + 1e-3 * ft)
+            bad_pixels.extend((ya + int(y), xa + int(x)) for y, x in zip(*np.nonzero(differs)))
+        if bad == 0:       # float32 chain of up to 10 000 records against float64: sanity only (parity is the C++ oracle's job)
+            assert np.abs(res["out"][:, : yb - ya, : xb - xa] - r.out_color[:, ya:yb, xa:xb].cpu().numpy()).max() <= 3e-3
+        rows = row_of[ids.cpu().numpy()]
+        hit = rows >= 0
+        for key, d, m in _GRAD_KEYS:
+            np.add.at(sums[key], rows[hit], res[d][hit].reshape(-1, sums[key].shape[1]))
+            if magnitudes:
+                np.add.at(mags[key], rows[hit], res[m][hit].reshape(-1, mags[key].shape[1]))
+        if magnitudes:
+            np.maximum.at(k_walk, rows[hit], res["k"][hit])
+            np.add.at(pixels, rows[hit], res["pixels"][hit])
+            np.add.at(free_pixels, rows[hit], res["free_pixels"][hit])
+            np.add.at(n_tiles, rows[hit], (res["pixels"][hit] > 0).astype(np.int64))
+            nc_frame[ya:yb, xa:xb] = res["n_contrib"][: yb - ya, : xb - xa]
+            ft_frame[ya:yb, xa:xb] = res["final_t"][: yb - ya, : xb - xa]
+            stop_frame[ya:yb, xa:xb] = res["stop_idx"][: yb - ya, : xb - xa]
+    out = {"exp": sums, "differs": differs_px}
+    if magnitudes:
+        out.update(M=mags, k=k_walk, pixels=pixels, free_pixels=free_pixels, tiles=n_tiles, n_contrib=nc_frame, final_t=ft_frame,
+                   stop_idx=stop_frame)
+    return out
+
+
+def gradients_of(got_dev, targets):
+    """The render backward's per-Gaussian sums of the Gaussians `targets` (numpy, keyed like oracle_gradients' exp)."""
+    import torch
+    idx = torch.from_numpy(np.asarray(targets)).to(got_dev["dL_dcolors"].device)
+    return {"dL_dmean2D": got_dev["dL_dmean2D"][idx].cpu().numpy(),
+            "dL_dconic": got_dev["dL_dconic_opacity"][idx][:, :3].cpu().numpy(),
+            "dL_dcov2D": got_dev["dL_dcov2D"][idx][:, :3].cpu().numpy(),
+            "dL_dopacity": got_dev["dL_dconic_opacity"][idx][:, 3:4].cpu().numpy(),
+            "dL_dcolors": got_dev["dL_dcolors"][idx].cpu().numpy()}
+
+
+# Per-Gaussian error bound of the render backward (assert_backward_per_gaussian):
+#     |got - exp| <= BW_TAU * (k + BW_C [+ tiles with float sums]) * M + BW_ATOL
+# M: the sum's condition scale (all factors in absolute value), k: the walk depth (reciprocals behind the rebuilt T), tiles: the
+# float sums of the tiles, one per tile in any order (wide_sums=False, or the block feed's per-entry sums). BW_C covers what every record pays whatever its depth: the fused
+# sums over a lane's four pixels, the six-level wave reduction, the final rounding. Calibrated on one MI355X over every scene and
+# path of tests/test_gpu_backward_edges.py (10 scenes x 6 paths): worst |err| / ((k + 8) M) measured 2.80e-8 (garden pose 1,
+# sorted list), 2.54e-8 (garden pose 0), 1.96e-8 (long lists), 1.94e-8 (termination at 1e-4, band), 1.07e-8 (clamp), 9.2e-9
+# (screen-filling splat), 6.8e-9 (1/255 twins), 4.5e-9 (per-entry sums scene); with float tile sums worst
+# |err| / ((k + 8 + tiles) M) 2.62e-8 (float atomics), 1.47e-9 (per-entry sums). BW_TAU is 4x the worst, just under float32
+# epsilon (1.19e-7).
+BW_C = 8.0
+BW_TAU = 1.1e-7
+BW_ATOL = 1e-30
+
+
+def assert_backward_inputs(n_contrib, final_t, ref, what=""):
+    """What the backward reads of the forward — nContrib and finalT — against the float32 oracle's (f32_forward), bit for bit, on
+    the pixels the oracle evaluated. A failure here is the FORWARD's (or the oracle's), not the backward's."""
+    nc = np.asarray(n_contrib).view(np.uint32).astype(np.int64)
+    ft = np.asarray(final_t, np.float32)
+    on = ref["n_contrib"] >= 0
+    assert on.any(), what
+    bad_nc = int((nc[on] != ref["n_contrib"][on]).sum())
+    bad_ft = int((ft[on].view(np.uint32) != ref["final_t"][on].astype(np.float32).view(np.uint32)).sum())
+    assert bad_nc == 0 and bad_ft == 0, (f"{what}: the forward state differs from the float32 oracle's ({bad_nc} nContrib, {bad_ft} "
+                                         "finalT words): the forward (or the oracle's restatement of it) is at fault, not the backward")
+
+
+def assert_backward_per_gaussian(got, ref, float_tile_sums=False, what=""):
+    """The render backward's sums of every Gaussian of `ref` (oracle_gradients(..., f32_forward=True, magnitudes=True)) against
+    the oracle's, Gaussian by Gaussian and component by component — not against a scale shared by the whole frame, under which
+    the Gaussians behind an opaque front (T ~ 1e-3) could be 100 % wrong:
+      support  a Gaussian no pixel composites gets 0.0 in every component, bit for bit; one that some pixel composites gets
+               non-zero colour gradients (dL_dout is random: they cannot vanish)
+      clamp    a Gaussian clamped (raw > 0.99) on every pixel it composites gets exactly zero mean, conic, opacity and
+               covariance gradients
+      value    |got - exp| <= BW_TAU (k + BW_C [+ tiles]) M + BW_ATOL
+    float_tile_sums: the tiles' sums of a Gaussian were added in float in some order (wide_sums=False, or the block feed's
+    per-entry sums): the tiles term is added. got: gradients_of(...). Returns the worst ratio |got - exp| / ((k + BW_C [+ tiles]) M)
+    over the components with M > 0 (printed; where M = 0 the bound is BW_ATOL)."""
+    exp, M = ref["exp"], ref["M"]
+    none = ref["pixels"] == 0
+    clamped = (ref["pixels"] > 0) & (ref["free_pixels"] == 0)
+    depth = ref["k"].astype(np.float64) + BW_C + (ref["tiles"].astype(np.float64) if float_tile_sums else 0.0)
+    worst, worst_at = 0.0, None
+    for key, _, _ in _GRAD_KEYS:
+        e, m = exp[key], M[key]
+        g = np.asarray(got[key], np.float64).reshape(e.shape)
+        assert np.isfinite(g).all(), (what, key)
+        assert (g[none] == 0.0).all(), (what, key, "a Gaussian no pixel composites must get exactly zero",
+                                         np.nonzero(none)[0][(g[none] != 0).any(1)][:8])
+        if key != "dL_dcolors":
+            assert (g[clamped] == 0.0).all(), (what, key, "a Gaussian clamped on every pixel it composites moves no alpha",
+                                               np.nonzero(clamped)[0][(g[clamped] != 0).any(1)][:8])
+        err = np.abs(g - e)
+        bound = BW_TAU * depth[:, None] * m + BW_ATOL
+        ratio = np.where(m > 0, err / np.maximum(depth[:, None] * m, 1e-300), 0.0)
+        i = np.unravel_index(int(np.argmax(ratio)), e.shape)
+        if ratio[i] > worst:
+            worst, worst_at = float(ratio[i]), (key, int(i[0]), int(ref["k"][i[0]]), float(e[i]), float(g[i]), float(m[i]))
+        over = err > bound
+        assert not over.any(), (what, key, f"{int(over.any(1).sum())} Gaussians over the bound; worst ratio {float(ratio.max()):.3e}",
+                                worst_at)
+    assert (np.asarray(got["dL_dcolors"])[~none] != 0.0).all(), (what, "a composited Gaussian without colour gradient")
+    print(f"[backward per Gaussian] {what}: {int((~none).sum())} composited ({int(clamped.sum())} clamped everywhere), worst "
+          f"|err| / ((k + c{' + tiles' if float_tile_sums else ''}) M) = {worst:.3e} at {worst_at}")
+    return worst

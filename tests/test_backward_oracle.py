@@ -187,3 +187,124 @@ def test_upstream_profile_chain_matches_finite_differences():
     # and the two profiles agree where they coincide: a unit quaternion gives the same covariance
     q = rng.normal(size=4); q /= np.linalg.norm(q)
     assert np.abs(B.inria_cov3d(scale, q, 1.0) - B.cov3d(scale, q, 1.0)).max() <= 1e-12
+
+
+def _tiles_of(means, co, col, ranges, plist, w, h, bg, g_out, **kw):
+    """blend_tile_backward on every tile of a _toy scene: yields (tx, ty, ids, result)."""
+    gx, gy = (w + 15) // 16, (h + 15) // 16
+    for ty in range(gy):
+        for tx in range(gx):
+            a, b = ranges[ty * gx + tx]
+            ids = plist[a:b]
+            tile_g = np.zeros((3, 16, 16))
+            y1, x1 = min(h, ty * 16 + 16), min(w, tx * 16 + 16)
+            tile_g[:, : y1 - ty * 16, : x1 - tx * 16] = g_out[:, ty * 16:y1, tx * 16:x1]
+            yield tx, ty, ids, B.blend_tile_backward(means[ids], co[ids], col[ids], tx, ty, w, h, bg, tile_g, **kw)
+
+
+_SUMS = (("d_mean", "M_mean"), ("d_conic", "M_conic"), ("d_cov", "M_cov"), ("d_op", "M_op"), ("d_col", "M_col"))
+
+
+def test_magnitudes_bound_every_sum():
+    """magnitudes=True: M >= |sum| componentwise, for the float64 and the float32 forward; a record no pixel composites has
+    M = 0, k = 0; a record that is clamped on every pixel it composites has no opacity / conic / mean / covariance scale."""
+    for seed in (0, 3, 5):
+        means, co, col, ranges, plist, w, h, bg, g_out = _toy(seed=seed, n=40, w=40, h=30)
+        co = co.copy()
+        co[:6, :3] *= 0.3
+        for f32 in (False, True):
+            n_contrib = n_none = 0
+            for tx, ty, ids, r in _tiles_of(means, co, col, ranges, plist, w, h, bg, g_out, f32_forward=f32, magnitudes=True):
+                for d, m in _SUMS:
+                    assert (r[m] >= 0).all() and (np.abs(r[d]) <= r[m] * (1 + 1e-12) + 1e-300).all(), (seed, f32, d)
+                none = r["pixels"] == 0
+                n_contrib += int((~none).sum())
+                n_none += int(none.sum())
+                assert (r["k"][none] == 0).all() and (r["k"][~none] >= 1).all()
+                for d, m in _SUMS:
+                    assert (r[m][none] == 0).all() and (r[d][none] == 0).all(), (d, m)
+                clamped = (r["pixels"] > 0) & (r["free_pixels"] == 0)
+                for m in ("M_mean", "M_conic", "M_cov", "M_op"):
+                    assert (r[m][clamped] == 0).all(), m
+                assert (r["M_col"][~none] > 0).all()
+            assert n_contrib > 0 and n_none > 0
+
+
+def test_magnitudes_equal_the_sums_where_every_term_has_one_sign():
+    """One record over a tile, dL/dout > 0, colours > 0, black background: every pixel's dL/dalpha is cg > 0, so the opacity,
+    colour, dA and dC sums have terms of one sign and M equals |sum| — and the diagonal covariance sums too where B = 0 (else
+    u = K d is itself a sum of two terms whose signs differ across the footprint)."""
+    rng = np.random.default_rng(2)
+    g = rng.uniform(0.1, 1.0, (3, 16, 16))
+    for xy, conic, op in (((7.3, 8.6), (0.05, 0.0, 0.08), 0.7), ((3.0, 12.0), (0.3, -0.1, 0.2), 0.95)):
+        r = B.blend_tile_backward(np.array([xy]), np.array([conic + (op,)]), np.array([[0.9, 0.2, 0.6]]), 0, 0, 16, 16,
+                                  np.zeros(3), g, magnitudes=True)
+        assert r["pixels"][0] > 4 and r["k"][0] == 1
+        for d, m, c in (("d_op", "M_op", None), ("d_col", "M_col", slice(None)), ("d_conic", "M_conic", [0, 2]),
+                        ("d_cov", "M_cov", [0, 2])):
+            if d == "d_cov" and conic[1] != 0.0:
+                continue
+            got, mag = np.abs(r[d][0] if c is None else r[d][0][c]), r[m][0] if c is None else r[m][0][c]
+            assert np.all(mag > 0) and np.allclose(got, mag, rtol=1e-12, atol=0), (d, got, mag)
+        # the mean's terms change sign across the footprint: M strictly above |sum|
+        assert (r["M_mean"][0] > np.abs(r["d_mean"][0]) * (1 + 1e-6)).all()
+
+
+def _walk_depths(means, co, ranges, plist, w, h, t_cutoff=0.001):
+    """Per pixel, the loop of blend_forward; per Gaussian, the largest count of contributing records from it to a pixel's
+    last contributor (itself included), over the pixels it contributes to."""
+    k = np.zeros(len(means), np.int64)
+    for px, py, ids in B._pixel_lists(ranges, plist, w, h):
+        T, seen = 1.0, []
+        for g in ids:
+            dx, dy = means[g, 0] - px, means[g, 1] - py
+            power = -0.5 * (co[g, 0] * dx * dx + co[g, 2] * dy * dy) - co[g, 1] * dx * dy
+            if power > 0.0:
+                continue
+            alpha = min(0.99, co[g, 3] * np.exp(power))
+            if alpha < 1.0 / 255.0:
+                continue
+            if T * (1.0 - alpha) < t_cutoff:
+                break
+            T *= 1.0 - alpha
+            seen.append(g)
+        for j, g in enumerate(seen):
+            k[g] = max(k[g], len(seen) - j)
+    return k
+
+
+def test_walk_depth_matches_a_per_pixel_loop():
+    for seed in (0, 3, 5):
+        means, co, col, ranges, plist, w, h, bg, g_out = _toy(seed=seed, n=40, w=40, h=30)
+        co = co.copy()
+        co[:6, :3] *= 0.3
+        exp = _walk_depths(means, co, ranges, plist, w, h)
+        k = np.zeros(len(means), np.int64)
+        for tx, ty, ids, r in _tiles_of(means, co, col, ranges, plist, w, h, bg, g_out, magnitudes=True):
+            np.maximum.at(k, ids, r["k"])
+        assert np.array_equal(k, exp), (seed, k, exp)
+        assert exp.max() >= 10 and exp.min() <= 2
+
+
+def test_vectorised_tile_backward_with_the_float32_forward():
+    """f32_forward=True against the float64 per-pixel loops: the same contributing set on the _toy scenes, the transmittance
+    and the gradients to float32 rounding of the forward (no fused multiply-add in the float32 power)."""
+    for seed in (0, 3, 5):
+        means, co, col, ranges, plist, w, h, bg, g_out = _toy(seed=seed, n=40, w=40, h=30)
+        co = co.copy()
+        co[:6, :3] *= 0.3
+        means, co, col = (np.asarray(v, np.float32).astype(np.float64) for v in (means, co, col))
+        out, ft, nc = B.blend_forward(means, co, col, ranges, plist, w, h, bg)
+        g = B.blend_backward(means, co, col, ranges, plist, nc, ft, w, h, bg, g_out)
+        acc = {k: np.zeros_like(v) for k, v in g.items()}
+        for tx, ty, ids, r in _tiles_of(means, co, col, ranges, plist, w, h, bg, g_out, f32_forward=True):
+            y1, x1 = min(h, ty * 16 + 16) - ty * 16, min(w, tx * 16 + 16) - tx * 16
+            assert np.array_equal(r["n_contrib"][:y1, :x1], nc[ty * 16:ty * 16 + y1, tx * 16:tx * 16 + x1])
+            assert np.abs(r["final_t"][:y1, :x1] - ft[ty * 16:ty * 16 + y1, tx * 16:tx * 16 + x1]).max() <= 1e-5
+            assert np.abs(r["out"][:, :y1, :x1] - out[:, ty * 16:ty * 16 + y1, tx * 16:tx * 16 + x1]).max() <= 1e-5
+            np.add.at(acc["dL_dmean2D"], ids, r["d_mean"])
+            np.add.at(acc["dL_dconic"], ids, r["d_conic"])
+            np.add.at(acc["dL_dopacity"], ids, r["d_op"])
+            np.add.at(acc["dL_dcolor"], ids, r["d_col"])
+        for k in g:
+            assert np.abs(acc[k] - g[k]).max() <= 1e-5 * max(1.0, np.abs(g[k]).max()), (k, np.abs(acc[k] - g[k]).max())

@@ -15,7 +15,7 @@ import gc
 import numpy as np
 import pytest
 
-from helpers import assert_blend_parity, check_backward_chain, image_report
+from helpers import assert_blend_parity, check_backward_chain, gradients_of, image_report, oracle_gradients
 
 pytestmark = pytest.mark.gpu
 
@@ -219,65 +219,8 @@ def _tile_rects(means2D, ext, gx, gy):
     return x0, y0, x1, y1
 
 
-def _oracle_gradients(r, dL, bg, tiles, targets, max_depth, bad_pixels=None, f32_forward=False):
-    """Float64 gradients (oracle/backward_np.blend_tile_backward) of the Gaussians `targets`, summed over `tiles`
-    (which must contain every tile those Gaussians touch). Returns (dict of [len(targets), d] arrays, pixels whose
-    last contributor differs from the GPU's). bad_pixels (a list, optional): receives (y, x) of every pixel on which the
-    float64 forward and the GPU's float32 forward disagree — another last contributor, or another transmittance (a record
-    at alpha = 1/255 taken by one of them only)."""
-    import torch
-    from oracle import backward_np as B
-    W, H = r.width, r.height
-    gx = (W + 15) // 16
-    geo = r.map_geometry_state()
-    ranges = r.map_image_state()["ranges"].cpu().numpy().view(np.uint32).astype(np.int64)
-    ncontrib = r.map_image_state()["nContrib"]
-    plist = r.map_binning_state()["values"]
-    final_t = r.map_image_state()["finalT"]
-    row_of = np.full(r.num_gaussians, -1, np.int64)
-    row_of[targets] = np.arange(len(targets))
-    sums = {"dL_dmean2D": np.zeros((len(targets), 2)), "dL_dconic": np.zeros((len(targets), 3)), "dL_dcov2D": np.zeros((len(targets), 3)),
-            "dL_dopacity": np.zeros((len(targets), 1)), "dL_dcolors": np.zeros((len(targets), 3))}
-    mismatch = 0
-    for tx, ty in tiles:
-        t = ty * gx + tx
-        ya, yb, xa, xb = ty * 16, min(H, ty * 16 + 16), tx * 16, min(W, tx * 16 + 16)
-        nc_tile = ncontrib[ya:yb, xa:xb]
-        depth = int(nc_tile.max())                       # the list prefix that reaches every pixel's last contributor
-        a = int(ranges[t, 0])
-        assert depth <= int(ranges[t, 1]) - a and depth <= max_depth
-        ids = plist[a:a + depth].to(torch.int64)
-        tile_g = np.zeros((3, 16, 16))
-        tile_g[:, : yb - ya, : xb - xa] = dL[:, ya:yb, xa:xb].cpu().numpy()
-        res = B.blend_tile_backward(geo["means2D"][ids].cpu().numpy(), geo["conicOpacity"][ids].cpu().numpy(),
-                                    geo["rgb"][ids].cpu().numpy(), tx, ty, W, H, bg, tile_g, f32_forward=f32_forward)
-        differs = res["n_contrib"][: yb - ya, : xb - xa] != nc_tile.cpu().numpy()
-        bad = int(differs.sum())
-        mismatch += bad
-        if bad_pixels is not None:
-            ft = final_t[ya:yb, xa:xb].cpu().numpy().astype(np.float64)
-            differs = differs | (np.abs(res["final_t"][: yb - ya, : xb - xa] - ft) > 1e-5 + 1e-3 * ft)
-            bad_pixels.extend((ya + int(y), xa + int(x)) for y, x in zip(*np.nonzero(differs)))
-        if bad == 0:       # float32 chain of up to 10 000 records against float64: sanity only (parity is the C++ oracle's job)
-            assert np.abs(res["out"][:, : yb - ya, : xb - xa] - r.out_color[:, ya:yb, xa:xb].cpu().numpy()).max() <= 3e-3
-        rows = row_of[ids.cpu().numpy()]
-        hit = rows >= 0
-        np.add.at(sums["dL_dmean2D"], rows[hit], res["d_mean"][hit])
-        np.add.at(sums["dL_dconic"], rows[hit], res["d_conic"][hit])
-        np.add.at(sums["dL_dcov2D"], rows[hit], res["d_cov"][hit])
-        np.add.at(sums["dL_dopacity"], rows[hit], res["d_op"][hit][:, None])
-        np.add.at(sums["dL_dcolors"], rows[hit], res["d_col"][hit])
-    return sums, mismatch
-
-
 def _compare_gradients(got_dev, targets, exp, allowed_outliers, what):
-    import torch
-    idx = torch.from_numpy(np.asarray(targets)).to(got_dev["dL_dcolors"].device)
-    got = {"dL_dmean2D": got_dev["dL_dmean2D"][idx].cpu().numpy(),
-           "dL_dconic": got_dev["dL_dconic_opacity"][idx][:, :3].cpu().numpy(),
-           "dL_dcov2D": got_dev["dL_dcov2D"][idx][:, :3].cpu().numpy(),
-           "dL_dopacity": got_dev["dL_dconic_opacity"][idx][:, 3:4].cpu().numpy(),
-           "dL_dcolors": got_dev["dL_dcolors"][idx].cpu().numpy()}
+    got = gradients_of(got_dev, targets)
     for k in exp:
         scale = max(1e-6, float(np.abs(exp[k]).max()))
         err = np.abs(got[k] - exp[k]).max(1)
@@ -336,7 +279,8 @@ def _check_pose(r, scene, cam, bg, seed, min_with_gradient, n_windows=40, max_ti
     cand = np.sort(np.concatenate([pick.permutation(pool_a)[:1000], pick.permutation(pool_b)[:1000]]))
     assert cand.size >= 500, (pool_a.size, pool_b.size)
     tiles = sorted({(wx + i, wy + j) for wx, wy in wins for i in (0, 1) for j in (0, 1)})
-    exp, mismatch = _oracle_gradients(r, dL, bg, tiles, cand, max_depth)
+    ref = oracle_gradients(r, dL, bg, tiles, cand, max_depth)
+    exp, mismatch = ref["exp"], len(ref["differs"])
     assert mismatch <= 8, mismatch              # exp implementations may flip a threshold on a handful of pixels
     _compare_gradients(got_dev, cand, exp, mismatch, "random Gaussians inside windows")
     n_grad = int((np.abs(exp["dL_dcolors"]).sum(1) > 0).sum())
@@ -357,7 +301,8 @@ def _check_pose(r, scene, cam, bg, seed, min_with_gradient, n_windows=40, max_ti
             break
     keep = np.asarray(sorted(keep))
     if keep.size:
-        exp2, mismatch2 = _oracle_gradients(r, dL, bg, sorted(tiles), keep, max_depth)
+        ref2 = oracle_gradients(r, dL, bg, sorted(tiles), keep, max_depth)
+        exp2, mismatch2 = ref2["exp"], len(ref2["differs"])
         assert mismatch2 <= 8, mismatch2
         _compare_gradients(got_dev, keep, exp2, mismatch2, "Gaussians with gradient")
         assert (np.abs(exp2["dL_dcolors"]).sum(1) > 0).all()
@@ -380,7 +325,7 @@ def _check_pose(r, scene, cam, bg, seed, min_with_gradient, n_windows=40, max_ti
         all_tiles = [(tx, ty) for ty in range(gy) for tx in range(gx)]
         bad_px = []
         # (the oracle's forward in float32, as the HIP forward computes it: the backward of one and the same function)
-        exp3, mismatch3 = _oracle_gradients(r, dL, bg, all_tiles, big, max_depth, bad_pixels=bad_px, f32_forward=True)
+        exp3 = oracle_gradients(r, dL, bg, all_tiles, big, max_depth, bad_pixels=bad_px, f32_forward=True)["exp"]
         assert len(bad_px) <= 8, len(bad_px)
         if bad_px:
             # The two forwards disagree on a few pixels that sit on a hard threshold; a Gaussian whose sum over two million
@@ -389,9 +334,9 @@ def _check_pose(r, scene, cam, bg, seed, min_with_gradient, n_windows=40, max_ti
             dL = dL.clone()
             ys, xs = (torch.tensor(v, device=dL.device) for v in zip(*bad_px))
             sub = sorted({(x // 16, y // 16) for y, x in bad_px})
-            before, _ = _oracle_gradients(r, dL, bg, sub, big, max_depth, f32_forward=True)
+            before = oracle_gradients(r, dL, bg, sub, big, max_depth, f32_forward=True)["exp"]
             dL[:, ys, xs] = 0.0
-            after, _ = _oracle_gradients(r, dL, bg, sub, big, max_depth, f32_forward=True)
+            after = oracle_gradients(r, dL, bg, sub, big, max_depth, f32_forward=True)["exp"]
             exp3 = {k: exp3[k] - before[k] + after[k] for k in exp3}
             got_dev = r.backward(dL)
         sel = torch.from_numpy(big).to("cuda:0")
