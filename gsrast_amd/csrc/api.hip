@@ -137,12 +137,7 @@ struct gsr_tile_history {
     int cur = 0;
     int dims[4] = {0, 0, 0, 0};               // width, height, tile rows [begin, end) the ticks belong to
     uint32_t order_serial = 0;                // the call whose blend took `order` (0: none)
-    bool wanted = false;                      // the last statistics say the frame ends on a few slow tiles (or is a light one)
-    bool decorrelated = false;                // ... and that the two last frames did not resemble each other
-    bool overlapped = false;                  // the last block-plan call ran its blend beside the emission
-    bool block_fed = false;                   // ... and read the block lists (else the sorted lists: a tile's time then says less about the block-fed blend)
-    uint32_t mean = 0, longest = 0;           // mean and longest tile time of the last statistics; mean 0: none yet for this size
-    uint32_t calls = 0;                       // calls since the ticks were last cleared
+    gsr::HistoryView view;                    // what the per-frame rules read of it (frame_policy.hpp)
     uint32_t last_serial = 0;                 // the owning thread's call counter at its last use (the library's own histories: which to give up)
     bool used = false;
     hipStream_t last_stream = nullptr;        // the stream of the call that used it last: what orders two calls' kernels
@@ -153,23 +148,6 @@ struct gsr_tile_history {
 namespace gsr {
 namespace {
 constexpr uint32_t kHistoryMagic = 0x54485347u;   // "GSHT"
-// Instances per visible Gaussian (R / V) at which the plans and the blend's feed change hands (each with the frames it was
-// measured on; `profiles/r05_trained_like.txt` has all of them on a scene of flat, opaque splats on surfaces):
-constexpr uint64_t kBlockPlanMinInstances = 6;    // block plan from here on, sort plan below
-constexpr uint64_t kBlockFeedMinInstances = 48;   // a SERIAL blend reads the block lists from here on, the sorted lists below
-constexpr uint32_t kBigSplatTiles = 256;          // "a big splat" (16 x 16 tiles and more) for the plan's choice
-constexpr uint64_t kOverlapMinInstances = 16;     // the blend may run beside the emission (block-fed) from here on — when the tile times say it is the shorter of the two
-// A blend fed from the sorted lists gives EVERY tile four waves (deep tiles, blend.hip) below this many instances per visible
-// Gaussian: short lists of small splats, where a frame ends on the lone waves of its few deep tiles and four waves per tile
-// cost the others next to nothing. Blend, one wave per tile -> four, bench scene (`profiles/r06_deep_tiles.txt`): R/V = 3.6: 0.66 ->
-// 0.30 ms, 5.3: 0.54 -> 0.31, 7.3: 0.54 -> 0.43, 11: 0.60 -> 0.59, 16: 0.63 -> 0.66, 23: 0.46 -> 0.56 (long lists that few
-// records of survive: the walk is the work, and the four waves meet at a barrier every 256 entries of it); on 49 unrelated
-// views of the same scene (bench.py's random views, serial blends): 0.57-0.97 of one wave's time up to 12, 0.83-1.00 at 12-16,
-// 0.94-1.06 at 16-24, up to 1.23 beyond. The switch is at 16 — where the blend may start to run beside the emission
-// (kOverlapMinInstances), fed from the block lists, which have no deep tiles. Above it: one
-// wave per tile (four for the history's slowest tiles only was built and measured neutral there: GSR_DEEP_BY_HISTORY).
-constexpr uint64_t kDeepAllMaxInstances = 16;
-constexpr unsigned long long kColorsTicksPerMega = 2040;   // colors_visible_kernel alone: 10 ns units per million Gaussians (50 M: 1.02 ms, 64 bytes fetched per Gaussian at the memory's request rate)
 constexpr size_t kMaxDefaultHistories = 8;        // streams per host thread and device that get a history of the library's own
 
 int tile_history_new(gsr_tile_history** out) {
@@ -276,19 +254,7 @@ struct ThreadResources {
 };
 static thread_local ThreadResources g_thread;
 
-// What the environment asks for, read once per process (A/B runs and the tests set these before the first call).
-struct EnvKnobs {
-    bool tile_history;         // GSR_TILE_HISTORY=0: no call reads or writes a tile history
-    int colors_beside;         // GSR_COLORS_BESIDE=0|1|2: geomState.rgb inside the preprocess / beside the depth sort / beside the blend; -1: by size
-    int fused_depth;           // GSR_FUSED_DEPTH=0|1: the depth order with / without the compaction whatever the size; -1: by size
-    int colors_early_pct;      // GSR_COLORS_EARLY_PCT=0..100: of the colours written beside the blend, the share that starts right behind the preprocess; -1: the default
-    int depth_records;         // GSR_DEPTH_RECORDS=0|1: the depth order's triples as three arrays / as 12-byte records between its passes; -1: records without the compaction
-    long block_feed_min;       // GSR_BLOCK_FEED_MIN=n: kBlockFeedMinInstances for this process (A/B runs); -1: the constant
-    long deep_all_max;         // GSR_DEEP_ALL_MAX=n: kDeepAllMaxInstances for this process (A/B runs); -1: the constant
-    bool deep_waves_auto;      // GSR_DEEP_WAVES_AUTO=0: deep tiles always get four waves (A/B runs)
-    bool deep_by_history;      // GSR_DEEP_BY_HISTORY=1: above that, the history's slowest tiles get four waves (tile_order_kernel's
-                               // count; measured neutral, `profiles/r06_deep_tiles.txt`: off by default)
-};
+// The environment switches (EnvKnobs, frame_policy.hpp): read once per process, before the first call needs them.
 EnvKnobs read_env_knobs() {
     EnvKnobs e;
     const char* h = getenv("GSR_TILE_HISTORY");
@@ -301,12 +267,6 @@ EnvKnobs read_env_knobs() {
     e.colors_early_pct = ce && ce[0] >= '0' && ce[0] <= '9' ? std::min(100, atoi(ce)) : -1;
     const char* dr = getenv("GSR_DEPTH_RECORDS");
     e.depth_records = dr && (dr[0] == '0' || dr[0] == '1') ? dr[0] - '0' : -1;
-    const char* b = getenv("GSR_BLOCK_FEED_MIN");
-    e.block_feed_min = b && b[0] ? atol(b) : -1;
-    const char* d = getenv("GSR_DEEP_ALL_MAX");
-    e.deep_all_max = d && d[0] ? atol(d) : -1;
-    const char* dw = getenv("GSR_DEEP_WAVES_AUTO");
-    e.deep_waves_auto = !(dw && dw[0] == '0');
     const char* dh = getenv("GSR_DEEP_BY_HISTORY");
     e.deep_by_history = dh && dh[0] == '1';
     return e;
@@ -334,6 +294,49 @@ void destroy_history(gsr_tile_history* h) {
     (void)hipEventDestroy(h->ev_order);
     (void)hipEventDestroy(h->ev_switch);
     delete h;
+}
+
+// The call's tile history: the caller's own, or this thread's for the call's stream (none: *out = nullptr).
+int history_of_call(const gsr_forward_args& a, const FrameDims& d, bool enabled, hipStream_t stream, Readback& rb,
+                    gsr_tile_history** out) {
+    gsr_tile_history*& hist = *out;
+    hist = nullptr;
+    if (!enabled || (a.flags & GSR_FLAG_NO_TILE_HISTORY) || tile_order_workgroups(d) > kTileOrderMax ||
+        d.grid_x * d.grid_y > kTileOrderMax)
+        return GSR_OK;
+    if (a.tile_history) {
+        int dev_now = -1;
+        GSR_HIP_TRY(hipGetDevice(&dev_now));
+        if (a.tile_history->magic != kHistoryMagic || a.tile_history->device != dev_now) return GSR_ERR_INVALID_ARG;
+        hist = a.tile_history;
+        if (hist->used && hist->last_stream != stream) {
+            // (the caller has taken its history to another stream: this call's kernels go behind what the old stream holds
+            // now — if that stream is gone, so is its work)
+            if (hipEventRecord(hist->ev_switch, hist->last_stream) == hipSuccess) GSR_HIP_TRY(hipStreamWaitEvent(stream, hist->ev_switch, 0));
+            else (void)hipGetLastError();
+        }
+    } else {
+        for (gsr_tile_history* h : rb.default_histories)
+            if (h->last_stream == stream) { hist = h; break; }
+        if (!hist && rb.default_histories.size() >= kMaxDefaultHistories) {
+            // A ninth stream: the history this thread has not used for the longest time goes — its stream may be gone
+            // (a caller that makes a stream per frame), so nothing is asked of that stream: freeing the history's memory
+            // waits for the device to be done with it (hipFree). Rare by construction; before round 6 the calls on
+            // further streams simply ran without a history, for good.
+            size_t lru = 0;
+            for (size_t i = 1; i < rb.default_histories.size(); ++i)
+                if ((int32_t)(rb.default_histories[i]->last_serial - rb.default_histories[lru]->last_serial) < 0) lru = i;
+            destroy_history(rb.default_histories[lru]);
+            rb.default_histories.erase(rb.default_histories.begin() + (long)lru);
+        }
+        if (!hist) {
+            // (a history is an accelerator: if the device has no memory left for one, the call runs without)
+            if (tile_history_new(&hist) == GSR_OK) rb.default_histories.push_back(hist);
+            else { hist = nullptr; (void)hipGetLastError(); g_hip_error[0] = 0; }
+        }
+    }
+    if (hist) { hist->last_stream = stream; hist->used = true; hist->last_serial = rb.serial; return rb.ensure_side(); }       // (the stream the sort of the order runs on)
+    return GSR_OK;
 }
 
 // Gives back what the calling thread's calls have made the library allocate, for every device: the second stream (drained
@@ -375,15 +378,6 @@ const uint32_t* tile_order_of_call(const gsr_forward_receipt& r, int row_begin, 
     for (const gsr_tile_history* h : rb->default_histories)
         if (fits(h)) return h->order;
     return nullptr;
-}
-
-DeviceShape device_shape_of(int cus) {
-    DeviceShape s;
-    s.cus = cus > 0 ? cus : 1;
-    s.blend_slots = (uint32_t)s.cus * 4u * 5u;
-    s.blend_slots_beside = (uint32_t)s.cus * 4u * 3u;
-    s.light_frame_ticks = 25000ull * (unsigned long long)s.blend_slots;
-    return s;
 }
 
 int current_device_shape(DeviceShape* out) {
@@ -574,12 +568,12 @@ void gsr_device_shape(int cus, uint32_t out[4]) {
 
 int gsr_tile_history_stats(const gsr_tile_history* h, uint32_t out[6]) {
     if (!h || h->magic != kHistoryMagic || !out) return fail(GSR_ERR_INVALID_ARG);
-    out[0] = h->stats[0] != 0u ? h->stats[2] : h->mean;          // (words the last sort has left and no call has read yet come first)
+    out[0] = h->stats[0] != 0u ? h->stats[2] : h->view.mean;          // (words the last sort has left and no call has read yet come first)
     out[1] = h->stats[1];
     out[2] = h->stats[3];
-    out[3] = (h->stats[0] != 0u ? h->stats[4] != 0u : h->decorrelated) ? 1u : 0u;
-    out[4] = h->calls;
-    out[5] = h->overlapped ? 1u : 0u;
+    out[3] = (h->stats[0] != 0u ? h->stats[4] != 0u : h->view.decorrelated) ? 1u : 0u;
+    out[4] = h->view.calls;
+    out[5] = h->view.overlapped ? 1u : 0u;
     return fail(GSR_OK);
 }
 
@@ -654,6 +648,8 @@ int gsr_forward(gsr_forward_args* a) {
         d.row_end = a->tile_row_end;
     }
     const int num_tiles = d.grid_x * d.grid_y;
+    const unsigned long long tiles = (unsigned long long)(d.row_end - d.row_begin) * (unsigned long long)d.grid_x;   // (this call's)
+    const bool xy_plan = d.grid_x <= 255 && d.grid_y <= 255;
 
     // GSCuda.cu:723-729
     char* geo_chunk = a->geometry_alloc(a->geometry_user, gsr_required_geometry(n));
@@ -707,89 +703,35 @@ int gsr_forward(gsr_forward_args* a) {
     GSR_STEP(current_device_shape(&shape));
     const EnvKnobs& env = env_knobs();
     gsr_tile_history* hist = nullptr;
-    if (env.tile_history && !(a->flags & GSR_FLAG_NO_TILE_HISTORY) && tile_order_workgroups(d) <= kTileOrderMax &&
-        d.grid_x * d.grid_y <= kTileOrderMax) {
-        if (a->tile_history) {
-            int dev_now = -1;
-            GSR_HIP_TRY(hipGetDevice(&dev_now));
-            if (a->tile_history->magic != kHistoryMagic || a->tile_history->device != dev_now) return fail(GSR_ERR_INVALID_ARG);
-            hist = a->tile_history;
-            if (hist->used && hist->last_stream != stream) {
-                // (the caller has taken its history to another stream: this call's kernels go behind what the old stream holds
-                // now — if that stream is gone, so is its work)
-                if (hipEventRecord(hist->ev_switch, hist->last_stream) == hipSuccess) GSR_HIP_TRY(hipStreamWaitEvent(stream, hist->ev_switch, 0));
-                else (void)hipGetLastError();
-            }
-        } else {
-            for (gsr_tile_history* h : g_rb.default_histories)
-                if (h->last_stream == stream) { hist = h; break; }
-            if (!hist && g_rb.default_histories.size() >= kMaxDefaultHistories) {
-                // A ninth stream: the history this thread has not used for the longest time goes — its stream may be gone
-                // (a caller that makes a stream per frame), so nothing is asked of that stream: freeing the history's memory
-                // waits for the device to be done with it (hipFree). Rare by construction; before round 6 the calls on
-                // further streams simply ran without a history, for good.
-                size_t lru = 0;
-                for (size_t i = 1; i < g_rb.default_histories.size(); ++i)
-                    if ((int32_t)(g_rb.default_histories[i]->last_serial - g_rb.default_histories[lru]->last_serial) < 0) lru = i;
-                destroy_history(g_rb.default_histories[lru]);
-                g_rb.default_histories.erase(g_rb.default_histories.begin() + (long)lru);
-            }
-            if (!hist) {
-                // (a history is an accelerator: if the device has no memory left for one, the call runs without)
-                if (tile_history_new(&hist) == GSR_OK) g_rb.default_histories.push_back(hist);
-                else { hist = nullptr; (void)hipGetLastError(); g_hip_error[0] = 0; }
-            }
-        }
-        if (hist) { hist->last_stream = stream; hist->used = true; hist->last_serial = g_rb.serial; GSR_STEP(g_rb.ensure_side()); }       // (the stream the sort of the order runs on)
-    }
-    const bool history = hist != nullptr;
-    // The order costs a launch on the second stream and the host a few microseconds, and it pays on frames that END on a
-    // few slow tiles and on light frames: it is sorted when the last statistics (the history's pinned host words, left by
-    // tile_order_kernel: fresh, the longest tile and the mean) say the longest tile takes 2.5 times what the tiles would take spread evenly over the chip's
-    // 5 120 wave slots — and every fourth call, to have fresh statistics (a camera that leaves the cloud is noticed within
-    // five frames). The ticks are recorded by every call.
+    GSR_STEP(history_of_call(*a, d, env.tile_history, stream, g_rb, &hist));
+    // The ticks are recorded by every call, the order is sorted when step_history says so (frame_policy.hpp)
+    HistoryView view;                                         // (what the rules read of the history from here on; none: zeros)
     bool order_now = false;
     uint32_t* t_ticks = nullptr;
-    if (history) {
+    if (hist) {
         const int dims_now[4] = {a->width, a->height, d.row_begin, d.row_end};
         if (memcmp(dims_now, hist->dims, sizeof(dims_now)) != 0) {
             GSR_HIP_TRY(hipMemsetAsync(hist->ticks[0], 0, sizeof(uint32_t) * 2 * (size_t)kTileOrderMax, stream));
             memcpy(hist->dims, dims_now, sizeof(dims_now));
-            hist->wanted = hist->decorrelated = hist->overlapped = false;
-            hist->calls = 0; hist->stats[0] = 0; hist->mean = hist->longest = 0; hist->order_serial = 0;
+            hist->view.wanted = hist->view.decorrelated = hist->view.overlapped = false;
+            hist->view.calls = 0; hist->stats[0] = 0; hist->view.mean = hist->view.longest = 0; hist->order_serial = 0;
         }
-        if (hist->stats[0] != 0u) {
-            const unsigned long long tiles = (unsigned long long)(d.row_end - d.row_begin) * (unsigned long long)d.grid_x;
-            hist->wanted = 2ull * (unsigned long long)shape.blend_slots * hist->stats[1] > 5ull * tiles * hist->stats[2] ||
-                           (hist->stats[2] != 0u && tiles * hist->stats[2] < shape.light_frame_ticks);      // (or a light frame: tile_order_kernel)
-            hist->mean = hist->stats[2];
-            hist->longest = hist->stats[1];
-            hist->decorrelated = hist->stats[4] != 0u;
-            hist->stats[0] = 0;
-        }
-        // (while the frames do not resemble each other the sort runs every call: it is what looks whether they do again — a
-        // camera cut is over after three frames — and it hands out the patch order as long as they do not)
-        order_now = hist->wanted || hist->decorrelated || (hist->calls % 4u) == 1u;       // (call 0 has no ticks yet)
-        ++hist->calls;
+        const bool fresh = hist->stats[0] != 0u;
+        const HistoryStep step = step_history(hist->view, fresh ? hist->stats : nullptr, tiles, shape);
+        if (fresh) hist->stats[0] = 0;
+        view = hist->view = step.view;
+        order_now = step.order_now;
+        ++hist->view.calls;
         t_ticks = hist->ticks[hist->cur];                 // (this call's times; the order is sorted from the other set)
         hist->cur ^= 1;
     }
     // geomState.rgb (GSCuda.cu:362-366) is a strided read nothing needs before the blend: by default it is written by a kernel
-    // of its own on the second stream while the scan and the depth sort run (launch_colors_visible, preprocess.hip). Whatever way the
-    // call ends, the caller's stream has waited for it (the chunk is the caller's).
-    // Up to 16 M Gaussians beside the depth sort: there its kernels wait on latency and the colours cost them 0.05 ms for the
-    // 0.10 ms the preprocess saves — bench frame 1.315 -> 1.268 ms. At 50 M they are bound by HBM themselves and lose what
-    // the preprocess gains (6.10 -> 6.19 ms): there the colours are written beside the BLEND — vector-bound —, which takes a
-    // record's colour straight from the SH array meanwhile (TileFeed::dc_stride). GSR_COLORS_BESIDE = 0 / 1 / 2 (environment,
-    // for A/B runs and the tests): inside the preprocess / beside the depth sort / beside the blend, whatever the size.
-    // ... where there IS a blend to hide behind: a frame whose blend runs beside the emission (the history's last frame did) would
-    // write its colours behind that blend, beside the rest of the emission — bound by the memory as well, and the frame ends with
-    // it; beside the depth sort they cost less (20 M Gaussians of the bench scene, 919 M instances: 3.87 -> 3.76 ms).
-    const int colors_forced = env.colors_beside;
-    const bool colors_movable = !inria && !a->colors_precomp && !(a->flags & GSR_FLAG_SERIAL_EMIT);
-    const bool blend_beside_emission = history && hist->mean != 0u && hist->overlapped;
-    const int colors_mode = !colors_movable ? 0 : (colors_forced >= 0 ? colors_forced : ((n <= (1 << 24) || blend_beside_emission) ? 1 : 2));
-    const bool colors_beside = colors_mode == 1;
+    // of its own on the second stream while the scan and the depth sort run (launch_colors_visible, preprocess.hip) — or
+    // beside the blend (choose_early, frame_policy.hpp). Whatever way the call ends, the caller's stream has waited for it
+    // (the chunk is the caller's).
+    const EarlyChoice early = choose_early(n, a->flags, a->colors_precomp != nullptr, xy_plan, view, tiles, env, shape);
+    const int colors_mode = early.colors_mode;
+    const size_t colors_early = early.colors_early;
     // (SideJoin: whatever way the call is left — a failing step included — the caller's stream waits for what this call
     // has put on the second stream: for `pending`, an event already recorded there, or, while `tail` is armed, for an
     // event recorded behind everything the second stream holds at that moment)
@@ -807,53 +749,36 @@ int gsr_forward(gsr_forward_args* a) {
             }
         }
     } colors_join{stream, nullptr, &g_rb, false};
+    // geomState.rgb of the Gaussians [first, first + count) on stream `s`
+    auto launch_colors = [&](size_t first, int count, hipStream_t s) {
+        return launch_colors_visible(count, geom.tiles_touched + first, a->shs ? a->shs + 48u * first : nullptr, geom.rgb + 3u * first, s);
+    };
+    // ... on the second stream, behind what the caller's stream holds now; `pending` for colors_join
+    auto fork_colors = [&](size_t first, int count) -> int {
+        GSR_HIP_TRY(hipEventRecord(g_rb.ev_pre_blend, stream));
+        GSR_HIP_TRY(hipStreamWaitEvent(g_rb.side, g_rb.ev_pre_blend, 0));
+        colors_join.tail = true;
+        const int rc_ = launch_colors(first, count, g_rb.side);
+        if (rc_ != GSR_OK) return rc_;
+        GSR_HIP_TRY(hipEventRecord(g_rb.ev_colors, g_rb.side));
+        colors_join.pending = g_rb.ev_colors;
+        colors_join.tail = false;
+        return GSR_OK;
+    };
     if (colors_mode != 0) GSR_STEP(g_rb.ensure_colors());
     GSR_BEGIN(GSR_STAGE_PREPROCESS);
-    const bool xy_plan = d.grid_x <= 255 && d.grid_y <= 255;
     if (inria)
         GSR_STEP(launch_preprocess_inria(*a, geom, radii, gs.depth_key, xy_plan ? gs.rect_idx : nullptr, d, stream, gs.wave_sums, kBigSplatTiles));
     else
         GSR_STEP(launch_preprocess(*a, geom, radii, gs.depth_key, xy_plan ? gs.rect_idx : nullptr, d, stream, gs.wave_sums,
                                    colors_mode != 0, kBigSplatTiles));   // :744-768
     GSR_END(GSR_STAGE_PREPROCESS);
-    // Colours beside the blend (mode 2) where the blend is SHORTER than the colours kernel (50 M Gaussians: 1.02 ms of colours
-    // alone, 1.37 beside a blend of 0.70 — the frame ended 0.65 ms after its blend): the Gaussians [0, colors_early) get theirs
-    // right behind the preprocess — beside the scan and the digit counts, which wait on LDS atomics and latency, and on into the
-    // first depth pass, which pays for it (336 -> 545 us with two fifths of them) —, the rest beside the blend, which then
-    // outlasts it or nearly: 50 M 4.93-5.07 -> 4.78-4.94 ms. The share: what the history's blend leaves uncovered of
-    // kColorsTicksPerMega x N, at most half; none without a history (GSR_COLORS_EARLY_PCT: a fixed share, A/B runs).
-    size_t colors_early = 0;
-    if (colors_mode == 2) {
-        unsigned long long pct = 0;
-        if (env.colors_early_pct >= 0) {
-            pct = (unsigned long long)env.colors_early_pct;
-        } else if (history && hist->mean != 0u && !hist->decorrelated) {
-            const unsigned long long tiles = (unsigned long long)(d.row_end - d.row_begin) * (unsigned long long)d.grid_x;
-            const unsigned long long blend_ticks = std::max((unsigned long long)hist->mean * tiles / (unsigned long long)shape.blend_slots,
-                                                            (unsigned long long)hist->longest);
-            const unsigned long long colors_ticks = kColorsTicksPerMega * (unsigned long long)n / 1000000ull;
-            if (colors_ticks > blend_ticks) pct = std::min(50ull, 100ull * (colors_ticks - blend_ticks) / colors_ticks);
-        }
-        colors_early = (size_t)n * (size_t)pct / 100u;
-    }
-    if (colors_beside || colors_early != 0u) {
-        // Forked right behind the preprocess (tilesTouched is final there): the scan's and the compaction's small launches
-        // leave most of the chip idle, and what the colours kernel gets done beside them it does not take from the depth passes
-        // (forked behind the read-back's event instead — no event of its own on the caller's stream — the three passes took
-        // 151 us for their 108: bench frame 1.215 -> 1.205 ms, from outside the cloud 1.52 -> 1.49, (0,0,-30) 1.42 -> 1.39).
-        GSR_HIP_TRY(hipEventRecord(g_rb.ev_pre_blend, stream));
-        GSR_HIP_TRY(hipStreamWaitEvent(g_rb.side, g_rb.ev_pre_blend, 0));
-        colors_join.tail = true;
-        GSR_STEP(launch_colors_visible(colors_beside ? n : (int)colors_early, geom.tiles_touched, a->shs, geom.rgb, g_rb.side));
-        GSR_HIP_TRY(hipEventRecord(g_rb.ev_colors, g_rb.side));
-        colors_join.pending = g_rb.ev_colors;
-        colors_join.tail = false;
-    }
-    // (mode 2: what is still to be written, by the launches further down)
-    const int colors_rest = n - (int)colors_early;
-    const uint32_t* const rest_tiles = geom.tiles_touched + colors_early;
-    const float* const rest_shs = a->shs ? a->shs + 48u * colors_early : nullptr;
-    float* const rest_rgb = geom.rgb + 3u * colors_early;
+    // Forked right behind the preprocess (tilesTouched is final there): the scan's and the compaction's small launches
+    // leave most of the chip idle, and what the colours kernel gets done beside them it does not take from the depth passes
+    // (forked behind the read-back's event instead — no event of its own on the caller's stream — the three passes took
+    // 151 us for their 108: bench frame 1.215 -> 1.205 ms, from outside the cloud 1.52 -> 1.49, (0,0,-30) 1.42 -> 1.39).
+    // Mode 2: the first colors_early of them only, the rest beside the blend further down.
+    if (colors_mode == 1 || colors_early != 0u) GSR_STEP(fork_colors(0, colors_mode == 1 ? n : (int)colors_early));
     GSR_BEGIN(GSR_STAGE_SCAN);
     // (the same pass counts the Gaussians with a tile per 4096: the offsets of the depth order's compaction below)
     // Its first launch also clears the depth order's four scratch areas (look-back words, tickets, the digit histograms:
@@ -887,12 +812,8 @@ int gsr_forward(gsr_forward_args* a) {
     side.main_partial = gs.main_partial;
     side.keys = gs.side_k; side.vals = gs.side_v; side.rects = xy_plan ? gs.side_r : nullptr;
     side.capacity = kDepthSideMax;
-    // Scenes beyond 16 M Gaussians (there every one of these kernels is bound by HBM): no compaction — its 20 N bytes buy
-    // nothing where nearly every Gaussian is visible (50 M: 0.20 ms). The digit counts come from a pass over the keys alone
-    // and the first depth pass reads the per-Gaussian arrays itself, leaving out what has no tile (onesweep_kernel, DROP).
-    // (GSR_FUSED_DEPTH = 0 / 1 in the environment, for A/B runs and the tests: never / whatever the size)
-    const bool fused_depth = xy_plan && (env.fused_depth >= 0 ? env.fused_depth == 1 : n > (1 << 24));
-    if (fused_depth)
+    // (beyond 16 M Gaussians, early.fused_depth: no compaction — the first depth pass leaves out what has no tile)
+    if (early.fused_depth)
         GSR_STEP(sort_u32_prepare_counts(gs.depth_key, (uint32_t)n, four, gs.sort_info, stream, g_rb.host_dev + 3, &side));
     else
         GSR_STEP(sort_u32_prepare(gs.depth_key, (uint32_t)n, gs.c_k, gs.c_v, gs.vis_partial, four, gs.sort_info, stream, true,
@@ -906,20 +827,16 @@ int gsr_forward(gsr_forward_args* a) {
     GSR_HIP_TRY(hipEventRecord(g_rb.ev_r, stream));
     // The first three depth passes are needed whatever the read-back says, so they are queued BEFORE the host waits
     // (grids sized for N keys, the true count V read on the device): the device sorts while the host sleeps.
-    // Between the passes the (key, index, rectangle) triples travel as 12-byte RECORDS — a digit's run leaves a tile as one
-    // piece instead of three, a lane fetches its key's triple with one load (50 M Gaussians: 347 + 2 x 322 -> 340 + 309 + 294 us)
-    // — in the room of the compaction's arrays where there is no compaction, else in that of the first pass's destination
-    // (dead before the last pass writes its three arrays there), and in the other pair's. Where the passes are bound by
-    // latency, not by the memory (up to 16 M Gaussians: with the compaction), it changes nothing (bench frame and the path's poses:
-    // +-0.003 ms) and the arrays stay. GSR_DEPTH_RECORDS=0 / 1: never / on both routes.
-    const bool depth_records = xy_plan && (env.depth_records >= 0 ? env.depth_records == 1 : fused_depth);
-    if (fused_depth)
+    // (early.depth_records: between the passes the triples travel as 12-byte records — in the room of the compaction's arrays
+    // where there is no compaction, else in that of the first pass's destination (dead before the last pass writes its three
+    // arrays there), and in the other pair's)
+    if (early.fused_depth)
         GSR_STEP(sort_u32_passes(gs.depth_key, nullptr, (uint32_t)n, gs.a_k, gs.a_v, gs.b_k, gs.b_v, four, 0, 3, stream, gs.sort_info + 1,
-                                 gs.rect_idx, gs.a_r, gs.b_r, &side, depth_records ? gs.c_k : nullptr, depth_records ? gs.b_k : nullptr));
+                                 gs.rect_idx, gs.a_r, gs.b_r, &side, early.depth_records ? gs.c_k : nullptr, early.depth_records ? gs.b_k : nullptr));
     else
         GSR_STEP(sort_u32_passes(gs.c_k, gs.c_v, (uint32_t)n, gs.a_k, gs.a_v, gs.b_k, gs.b_v, four, 0, 3, stream, gs.sort_info + 1,
                                  xy_plan ? gs.c_r : nullptr, xy_plan ? gs.a_r : nullptr, xy_plan ? gs.b_r : nullptr, nullptr,
-                                 depth_records ? gs.a_k : nullptr, depth_records ? gs.b_k : nullptr));
+                                 early.depth_records ? gs.a_k : nullptr, early.depth_records ? gs.b_k : nullptr));
     if (order_now) {
         // (behind the same event — it follows the history's last blend in stream order — and queued while the host would
         // only wait: nothing is added to the caller's stream, and by the time the blend is launched the order is there)
@@ -945,7 +862,7 @@ int gsr_forward(gsr_forward_args* a) {
     // (host[13]: the keys the compaction actually put on the side list — it must be the count the scan decided on, or
     // depth_side_kernel would rank entries of an earlier frame)
     // (without the compaction the side list is filled by the first depth pass, which may still be running: its count is not known here)
-    if (side_way && (four_passes || side_m > kDepthSideMax || side_lo > side_m || side_m > (uint32_t)nv || (!fused_depth && g_rb.host[13] != side_m)))
+    if (side_way && (four_passes || side_m > kDepthSideMax || side_lo > side_m || side_m > (uint32_t)nv || (!early.fused_depth && g_rb.host[13] != side_m)))
         return fail(GSR_ERR_INTERNAL);
     if (four_passes)
         GSR_STEP(sort_u32_passes(gs.c_k, gs.c_v, (uint32_t)nv, gs.a_k, gs.a_v, gs.b_k, gs.b_v, four, 3, 4, stream, nullptr,
@@ -962,7 +879,7 @@ int gsr_forward(gsr_forward_args* a) {
     const float t_cutoff = inria ? 0.0001f : 0.001f;                                        // :653 / upstream
     if (R == 0) {
         // (colours beside the blend: there is no blend — the zeros of a frame without a tile are written here)
-        if (colors_mode == 2) GSR_STEP(launch_colors_visible(colors_rest, rest_tiles, rest_shs, rest_rgb, stream));
+        if (colors_mode == 2) GSR_STEP(launch_colors(colors_early, n - (int)colors_early, stream));
         if (!inria) { issue_receipt((uint32_t)nv, nullptr); return fail(GSR_OK); }          // :775-778
         // upstream still runs the tile loop: every pixel gets the background
         GSR_HIP_TRY(hipMemsetAsync(img.ranges, 0, sizeof(uint32_t) * 2 * (size_t)num_tiles, stream));
@@ -984,31 +901,19 @@ int gsr_forward(gsr_forward_args* a) {
     // 8-bit digit passes over the tile bits.
     // Two binning plans give the same sorted lists. "blocks": the lists are written directly by
     // tile-block owners (blockbin.hip), nothing R-sized is sorted. "sort": column-major emission +
-    // one onesweep pass on the tile row. The block plan pays per (Gaussian, block) entry, so scenes
-    // of tiny splats (few tiles per Gaussian) stay on the sort plan unless a flag forces one.
-    bool use_blocks = xy_plan && blockbin_supported(d.grid_x, d.grid_y) && !(a->flags & GSR_FLAG_PLAN_SORT);
-    // The block plan pays per (Gaussian, block) entry and per unit, the sort plan 36 bytes per instance: what decides is
-    // the instances per VISIBLE Gaussian. Measured (binning without the blend, sort / blocks): R/V = 2.7 (50 M tiny splats)
-    // 5.6 / 5.9 ms, 5.3 (the bench scene from far away) 0.98 / 1.00 ms, 7.5: 2.08 / 1.81 ms, 11: 2.76 / 1.58 ms, 88: 2x.
-    // ... of the splats that ARE small: the sort plan's emission walks a Gaussian's columns and keys chunk by chunk of 512
-    // Gaussians, and a few hundred background splats that cover a thousand tiles each (any trained scene seen from outside)
-    // make its slowest chunks five times the others — 1 M flat splats + 500 huge ones from 48 units away, R/V = 2.8:
-    // 1.53 against 1.08 ms; 5.8 M: 2.46 / 2.14 (`profiles/r05_trained_like.txt`). The scan has counted the instances of the
-    // splats of kBigSplatTiles tiles and more (host words 14-15): with an eighth of the frame's instances in such splats the
-    // frame goes to the block plan whatever its average.
+    // one onesweep pass on the tile row. Which one, and the block plan's blend: choose_binning (frame_policy.hpp).
+    // (host words 14-15: the instances of the splats of kBigSplatTiles tiles and more, counted by the scan)
     const unsigned long long big_instances = (unsigned long long)g_rb.host[14] | ((unsigned long long)g_rb.host[15] << 32);
-    if (use_blocks && !(a->flags & GSR_FLAG_PLAN_BLOCKS))
-        use_blocks = (uint64_t)R >= kBlockPlanMinInstances * (uint64_t)nv || 8ull * big_instances >= (unsigned long long)R;
-    a->plan_used = use_blocks ? GSR_PLAN_BLOCKS : (xy_plan ? GSR_PLAN_SORT : GSR_PLAN_GENERIC);
+    const BinningChoice plan = choose_binning(R, (uint32_t)nv, big_instances, xy_plan, blockbin_supported(d.grid_x, d.grid_y),
+                                              a->flags, view, tiles, shape);
+    a->plan_used = plan.plan_used;
+    if (hist) { hist->view.overlapped = plan.overlap; hist->view.block_fed = plan.block_fed; }     // (what the next call reads of this one)
     // (the block plan has no R-sized sort: sortingSpace then holds its unit tables, not look-back words)
-    if (!use_blocks)
+    if (!plan.use_blocks)
         GSR_HIP_TRY(hipMemsetAsync(bs.sweep.error_word, 0, 128 + 256 * sizeof(uint32_t), stream));   // error word + tile-row histogram
     // (before the streams fork: the blend may run on the side stream)
     if (count_staged) GSR_HIP_TRY(hipMemsetAsync(g_rb.staged_dev, 0, sizeof(unsigned long long), stream));
-    bool forked = false, blend_from_lists = false;
-    // (the other plans' blends run behind their lists, fed from them: what the history says of THIS frame's blend)
-    if (history && !use_blocks) { hist->overlapped = false; hist->block_fed = false; }
-    if (use_blocks) {
+    if (plan.use_blocks) {
         // keysUnsorted / valuesUnsorted hold the block lists (rectangle | depth bits, index) in this plan
         GSR_STEP(launch_block_binning(nv, sorted_k, sorted_v, sorted_r, d.grid_x, d.grid_y, R, gs.block_scratch,
                                       bin.keys_unsorted, bin.values_unsorted, bin.sorting_space, img.ranges, inria, stream,
@@ -1020,88 +925,30 @@ int gsr_forward(gsr_forward_args* a) {
             GSR_HIP_TRY(hipEventRecord(g_rb.ev[2 * GSR_STAGE_SORT_PASS1 + 1], stream));
             g_rb.recorded[GSR_STAGE_DEPTH_ORDER] = g_rb.recorded[GSR_STAGE_SORT_PASS1] = true;
         }
-        // The blend of this plan reads the block lists, not the sorted lists, so it does not depend on the
-        // emission. With GSR_FLAG_OVERLAP_EMIT the emission (bound by the HBM write path) runs beside the
-        // blend (bound by vector ALU work) on a second stream, and the caller's stream waits for it before
-        // gsr_forward's work is complete: 5 % shorter frames, but each of the two kernels runs ~20 % longer
-        // while they share the chip, so per-kernel times are no longer those of the kernels alone.
-        // By default the library decides: beside each other when the blend — what the tiles of the last calls took, spread
-        // over the chip's 5 120 wave slots — is expected to be the shorter of the two (the emission: 12 R bytes at 5 TB/s);
-        // a blend already running beside the emission takes about twice as long per tile, hence the second threshold.
-        bool overlap = (a->flags & GSR_FLAG_OVERLAP_EMIT) != 0;
-        // (not while the history's frames do not resemble each other: the last frame's tile times then say nothing about this one)
-        if (!overlap && !(a->flags & GSR_FLAG_SERIAL_EMIT) && history && hist->mean != 0u && !hist->decorrelated &&
-            (uint64_t)R >= kOverlapMinInstances * (uint64_t)nv) {
-            const unsigned long long tiles = (unsigned long long)(d.row_end - d.row_begin) * (unsigned long long)d.grid_x;
-            // how long the blend will take: the tiles' times spread over the chip's 5 120 wave slots — beside the emission, whose
-            // persistent workgroups keep their registers, over the 3 072 it gets there —, but never less than the longest tile
-            // (frames of small splats end on a few lone waves: the mean alone said 0.16 ms for a blend of 0.36)
-            unsigned long long blend_ticks = std::max((unsigned long long)hist->mean * tiles /
-                                                          (unsigned long long)(hist->overlapped ? shape.blend_slots_beside : shape.blend_slots),
-                                                      (unsigned long long)hist->longest);
-            // (times of a blend fed from the SORTED lists: out of the block lists a tile walks every unit of its block for its
-            // entries — measured on the stand-in, block feed over sorted-list feed: 1.1 at 88 instances per visible Gaussian,
-            // 1.44 at 23, 3 at 5 = 1 + 10 V / R)
-            if (!hist->block_fed) blend_ticks = blend_ticks * ((unsigned long long)R + 10ull * (unsigned long long)nv) / (unsigned long long)R;
-            // The emission: 12 R bytes at 4 TB/s (measured 4.9 on the bench frame's 3.2 GB, 3.8 on 1 GB, 3.3-4.6 on 0.46 GB) — then the blend must be the shorter of the two, beside a kernel that fills
-            // the memory pipes it is throttled (the stand-in from outside the cloud, R/V = 22: 1.66 -> 1.99 ms) —, but never
-            // under the 0.07 ms a wave takes for its share of one unit: a light frame's emission leaves the chip idle, and a
-            // blend of up to twice that still gains beside it (1 M flat splats, frames of 0.4 ms; `profiles/r05_trained_like.txt`).
-            // Once overlapped, the times are those of a blend that shares the chip: while the emission runs it advances at 0.46
-            // of its pace (bench frame: 0.11 ms alone, 0.24 beside an emission that outlasts it), so b' = b / 0.46 if that ends
-            // inside the emission e, else e + (b - 0.46 e). The time it would take alone is taken back out of b' and held to
-            // the same limit, a tenth more (the stand-in from outside the cloud, entered from an overlapped pose, stayed
-            // overlapped under a looser bound: 1.48 -> 1.70 ms, for good).
-            const unsigned long long emit_bw = 12ull * (unsigned long long)R / 40000ull, emit_floor = 7000ull;
-            unsigned long long limit = emit_bw >= emit_floor ? emit_bw : 2ull * emit_floor;
-            // (a frame that is block-fed either way — 48 instances per visible Gaussian and more — changes nothing but the
-            // company its blend keeps: there a blend of up to twice the emission still gains, 1 M-splat stand-in, emission
-            // 0.10 ms, blend 0.13-0.24: 6-10 %; three times loses: the bench frame with faint splats)
-            if (hist->block_fed && (uint64_t)R >= kBlockFeedMinInstances * (uint64_t)nv) limit *= 2ull;
-            if (hist->overlapped) {
-                const unsigned long long e = std::max(emit_bw, emit_floor);
-                const unsigned long long alone = blend_ticks <= e ? blend_ticks * 46ull / 100ull : blend_ticks - e * 54ull / 100ull;
-                overlap = 10ull * alone < 11ull * limit;
-            } else {
-                overlap = blend_ticks < limit;
-            }
-        }
-        const bool serial = !overlap || (a->flags & GSR_FLAG_NO_SORTED_LISTS);
-        if (history) hist->overlapped = !serial;
-        if (!serial) a->plan_used |= GSR_PLAN_EMIT_OVERLAPPED;
-        // Which lists feed the blend. Out of the block lists a tile walks every unit of its block and picks its entries
-        // by mask: as good as the sorted list where a Gaussian covers most tiles of its blocks, but with small splats a
-        // tile owns a few of a unit's 2048 entries and pays a round trip to memory per unit for them (the bench scene
-        // from outside the cloud, R/V = 23: 0.65 against 0.45 ms; from far away, R/V = 5: 1.98 against 0.65 ms; bench
-        // frame, R/V = 88: equal). With the sorted lists written anyway, sparse frames blend from them.
-        blend_from_lists = serial && !(a->flags & GSR_FLAG_NO_SORTED_LISTS) &&
-                           (uint64_t)R < (env.block_feed_min >= 0 ? (uint64_t)env.block_feed_min : kBlockFeedMinInstances) * (uint64_t)nv;
-        if (history) hist->block_fed = !blend_from_lists;
+        // plan.overlap: the emission runs beside the blend, which goes to the second stream, and the caller's stream waits
+        // for it before gsr_forward's work is complete — each of the two kernels then runs ~20 % longer while they share the
+        // chip, so per-kernel times are no longer those of the kernels alone.
         // (the emission stays on the caller's stream and is launched first: its persistent workgroups must be resident
         // before the blend's thousands of waves arrive — the other way round the blend takes every register file and the
         // emission starts when the blend is nearly over: no gain)
-        if (!serial) {
+        if (plan.overlap) {
             GSR_STEP(g_rb.ensure_side());
             GSR_HIP_TRY(hipEventRecord(g_rb.ev_fork, stream));
             GSR_HIP_TRY(hipStreamWaitEvent(g_rb.side, g_rb.ev_fork, 0));
-            forked = true;
             colors_join.tail = true;                          // (until the join at the end of the call has been queued)
         }
-        hipStream_t emit_stream = stream;
         // (What a gsr_backward call after this one may use — the block lists and, for its per-entry gradient sums, the
         // bytes of keysUnsorted — it works out from the receipt: lists_of_receipt.)
-        if (blend_from_lists) a->plan_used |= GSR_PLAN_BLEND_FROM_LISTS;
         // GSR_FLAG_NO_SORTED_LISTS: this plan's blend reads the block lists, and no caller of the reference reads
         // BinningState (GSGaussians.cpp:214-219 maps GeometryState only): a forward-only caller may skip the 12 R
         // bytes of sorted keys / values altogether. keys / values are then left unwritten.
-        if (a->flags & GSR_FLAG_NO_SORTED_LISTS) {
-            a->plan_used |= GSR_PLAN_LISTS_SKIPPED;        // (values[0] = GSR_LISTS_SKIPPED_STAMP: written with the tile ranges)
-        } else {
-            if (profile) GSR_HIP_TRY(hipEventRecord(g_rb.ev[2 * GSR_STAGE_DUPLICATE], emit_stream));
+        // (plan_used then carries GSR_PLAN_LISTS_SKIPPED; values[0] = GSR_LISTS_SKIPPED_STAMP: written with the tile ranges)
+        if (!(a->flags & GSR_FLAG_NO_SORTED_LISTS)) {
+            if (profile) GSR_HIP_TRY(hipEventRecord(g_rb.ev[2 * GSR_STAGE_DUPLICATE], stream));
             GSR_STEP(launch_block_emit(nv, d.grid_x, d.grid_y, R, gs.block_scratch, bin.keys_unsorted, bin.values_unsorted,
-                                       bin.sorting_space, bin.keys, bin.values, emit_stream, forked, shape.cus));
+                                       bin.sorting_space, bin.keys, bin.values, stream, plan.overlap, shape.cus));
             if (profile) {
-                GSR_HIP_TRY(hipEventRecord(g_rb.ev[2 * GSR_STAGE_DUPLICATE + 1], emit_stream));
+                GSR_HIP_TRY(hipEventRecord(g_rb.ev[2 * GSR_STAGE_DUPLICATE + 1], stream));
                 g_rb.recorded[GSR_STAGE_DUPLICATE] = true;
             }
         }
@@ -1149,13 +996,13 @@ int gsr_forward(gsr_forward_args* a) {
         GSR_END(GSR_STAGE_SORT_PASS2);
     }
     // :800-801 — under the block plan the ranges are the tile starts it has already computed
-    if (!use_blocks) {
+    if (!plan.use_blocks) {
         GSR_BEGIN(GSR_STAGE_RANGES);
         GSR_STEP(launch_tile_ranges(bin.keys, R, img.ranges, num_tiles, inria, stream, gs.sort_info + 4));
         GSR_END(GSR_STAGE_RANGES);
     }
     const float* colors = a->colors_precomp ? a->colors_precomp : geom.rgb;                // :803
-    hipStream_t blend_stream = forked ? g_rb.side : stream;
+    hipStream_t blend_stream = plan.overlap ? g_rb.side : stream;
     // (the colours: long since written — the blend's stream is made to wait only if they are not; a blend on the side stream
     // follows them in stream order, and the caller's stream joins that stream below)
     if (colors_join.pending) {
@@ -1172,50 +1019,20 @@ int gsr_forward(gsr_forward_args* a) {
         GSR_HIP_TRY(hipStreamWaitEvent(blend_stream, hist->ev_order, 0));
     }
     const uint32_t* const t_order = order_now ? hist->order : nullptr;
-    if (order_now && !hist->decorrelated) a->plan_used |= GSR_PLAN_TILES_REORDERED;
-    if (history && hist->decorrelated) a->plan_used |= GSR_PLAN_TILE_ORDER_DROPPED;
+    if (order_now && !view.decorrelated) a->plan_used |= GSR_PLAN_TILES_REORDERED;
+    if (view.decorrelated) a->plan_used |= GSR_PLAN_TILE_ORDER_DROPPED;
     // Colours beside the blend (scenes beyond 16 M Gaussians): the blend takes them from the SH array; geomState.rgb is
     // written meanwhile on the other stream — or, where the blend itself runs on the second stream beside the emission,
     // behind it there — and the caller's stream waits for it before the call's work is complete.
     const bool colors_late = colors_mode == 2;
-    if (colors_late && !forked) {
-        GSR_HIP_TRY(hipEventRecord(g_rb.ev_pre_blend, stream));
-        GSR_HIP_TRY(hipStreamWaitEvent(g_rb.side, g_rb.ev_pre_blend, 0));
-        colors_join.tail = true;
-        GSR_STEP(launch_colors_visible(colors_rest, rest_tiles, rest_shs, rest_rgb, g_rb.side));
-        GSR_HIP_TRY(hipEventRecord(g_rb.ev_colors, g_rb.side));
-        colors_join.pending = g_rb.ev_colors;                 // (joined when this function is left)
-        colors_join.tail = false;
-    }
+    if (colors_late && !plan.overlap) GSR_STEP(fork_colors(colors_early, n - (int)colors_early));     // (joined when this function is left)
     if (colors_late) { colors = a->shs; a->plan_used |= GSR_PLAN_COLORS_BESIDE; }
-    // (deep tiles, blend.hip: the leading entries of an order sorted for THIS call; the block-fed blend has none)
-    const bool list_fed = !(use_blocks && !blend_from_lists);
-    const bool deep_wanted = env.deep_by_history && list_fed && t_order != nullptr && !hist->decorrelated && !(a->flags & GSR_FLAG_NO_DEEP_TILES);
-    const uint32_t deep_forced = a->flags & (GSR_FLAG_DEEP_TILES_ALL | GSR_FLAG_DEEP_WAVES_8 | GSR_FLAG_DEEP_WAVES_16);
-    // (not where geomState.rgb is written BESIDE the blend — scenes beyond 16 M Gaussians, colors_late above —: eight deep
-    // workgroups a CU hold every vector register of its SIMDs, the colours kernel waits for them to retire and the frame for
-    // the colours kernel: 50 M Gaussians 5.09 -> 5.33 ms, 5.13-5.22 with the blend kept to 5-6 workgroups a CU by idle LDS;
-    // with the colours passed as colorsPrecomp there is no such kernel: 4.37 -> 4.29)
-    const bool colours_beside_blend = colors_mode == 2;
-    const bool deep_by_rule = !colours_beside_blend && !(a->flags & GSR_FLAG_NO_DEEP_TILES) &&
-                              (uint64_t)R < (env.deep_all_max >= 0 ? (uint64_t)env.deep_all_max : kDeepAllMaxInstances) * (uint64_t)nv;
-    const bool deep_all = list_fed && (deep_forced != 0u || deep_by_rule);
-    // How many waves a deep tile gets: four — or eight, sixteen where the history says the frame's work sits in few tiles:
-    // tiles x mean / longest is how many tiles AS LONG AS THE LONGEST the frame amounts to; with fewer of them than the chip has
-    // SIMDs eight waves per tile win, with fewer than a quarter sixteen (measured, blend with 4 / 8 / 16 waves per tile,
-    // `profiles/r06_deep_tiles.txt` — a trained-like scene of 5.83 M splats from 32 / 48 / 70 units away, 358 / 200 / 96 such
-    // tiles: 1.15 / 1.01 / 1.03, 1.82 / 1.66 / 1.17, 3.20 / 2.88 / 2.20 ms (one wave per tile: 1.77, 3.06, 5.86); the bench
-    // scene from 40 / 50 units, 948 / 422: 0.297 / 0.283 / 0.68 and 0.240 / 0.212 / 0.30; from 30 units, 1 609: 0.31 / 0.38 / 1.03)
-    int deep_waves = (deep_forced & GSR_FLAG_DEEP_WAVES_16) ? 16 : ((deep_forced & GSR_FLAG_DEEP_WAVES_8) ? 8 : 4);
-    if (deep_all && deep_forced == 0u && env.deep_waves_auto && history && hist->mean != 0u && hist->longest != 0u && !hist->decorrelated) {
-        const unsigned long long tiles = (unsigned long long)(d.row_end - d.row_begin) * (unsigned long long)d.grid_x;
-        const unsigned long long as_longest = tiles * (unsigned long long)hist->mean / (unsigned long long)hist->longest;
-        const unsigned long long simds = 4ull * (unsigned long long)shape.cus;
-        deep_waves = 4ull * as_longest <= simds ? 16 : (as_longest <= simds ? 8 : 4);
-    }
-    if (deep_wanted || deep_all) a->plan_used |= GSR_PLAN_DEEP_TILES;
+    // Deep tiles (blend.hip): choose_blend, frame_policy.hpp — with the order as the sort's launch left it
+    const BlendChoice deep = choose_blend(R, (uint32_t)nv, plan.block_fed, order_now, colors_mode, a->flags, view, tiles,
+                                          env.deep_by_history, shape);
+    if (deep.deep_wanted || deep.deep_all) a->plan_used |= GSR_PLAN_DEEP_TILES;
     if (profile) GSR_HIP_TRY(hipEventRecord(g_rb.ev[2 * GSR_STAGE_BLEND], blend_stream));
-    if (use_blocks && !blend_from_lists)
+    if (plan.block_fed)
         GSR_STEP(launch_blend_blocks(nv, d, R, gs.block_scratch, bin.values_unsorted, bin.sorting_space, img.ranges, geom.means2D,
                                      colors, geom.conic_opacity, img.accum_alpha, img.n_contrib, a->background, a->out_color,
                                      count_staged ? g_rb.staged_dev : nullptr, t_cutoff, blend_stream, t_order, t_ticks, colors_late));
@@ -1223,11 +1040,11 @@ int gsr_forward(gsr_forward_args* a) {
         GSR_STEP(launch_blend(d, img.ranges, bin.values, geom.means2D, colors, geom.conic_opacity, img.accum_alpha,
                               img.n_contrib, a->background, a->out_color, count_staged ? g_rb.staged_dev : nullptr,
                               t_cutoff, blend_stream, gs.sort_info + 4, R, t_order, t_ticks, colors_late,
-                              deep_wanted ? hist->deep : nullptr, deep_all, deep_waves));   // :804-810
+                              deep.deep_wanted ? hist->deep : nullptr, deep.deep_all, deep.deep_waves));   // :804-810
     if (order_now) hist->order_serial = serial;               // (the blend that takes the order is in its stream: a backward of this call may take it too)
     if (profile) { GSR_HIP_TRY(hipEventRecord(g_rb.ev[2 * GSR_STAGE_BLEND + 1], blend_stream)); g_rb.recorded[GSR_STAGE_BLEND] = true; }
-    if (forked) {                                                           // the image is complete when the side stream is
-        if (colors_late) GSR_STEP(launch_colors_visible(colors_rest, rest_tiles, rest_shs, rest_rgb, g_rb.side));   // (beside the rest of the emission)
+    if (plan.overlap) {                                                     // the image is complete when the side stream is
+        if (colors_late) GSR_STEP(launch_colors(colors_early, n - (int)colors_early, g_rb.side));   // (beside the rest of the emission)
         GSR_HIP_TRY(hipEventRecord(g_rb.ev_join, g_rb.side));
         GSR_HIP_TRY(hipStreamWaitEvent(stream, g_rb.ev_join, 0));
         colors_join.tail = false;

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/gsrast_amd.h"
+#include "frame_policy.hpp"      // (DeviceShape, the launch heuristics' switch points)
 
 namespace gsr {
 
@@ -179,16 +180,6 @@ int launch_blend(const FrameDims& d, const uint32_t* ranges, const uint32_t* poi
                  int deep_waves = 4);                                                        // (... or 8 or 16: frames whose work sits in few tiles)
 // Longest tiles first: the order of this call's blend workgroups from the ticks the tiles of the call before left.
 constexpr int kTileOrderMax = 32768;      // workgroups (one per tile, patch grid padded) up to which the order is kept: 128 KB of LDS for its sort
-// What the launch heuristics need to know about the chip, derived from its CU count (hipDeviceAttributeMultiprocessorCount,
-// read once per device: an MI355X in a partitioned mode shows fewer CUs per device, and every figure below follows).
-struct DeviceShape {
-    int cus;                                 // compute units of the device
-    uint32_t blend_slots;                    // wave slots of the blend kernels: 4 SIMDs x 5 waves (96 VGPRs) per CU — 5 120 on 256 CUs
-    uint32_t blend_slots_beside;             // ... beside the emission's persistent workgroups, which keep their registers: 3 per SIMD — 3 072
-    unsigned long long light_frame_ticks;    // 250 us (in 10 ns) per blend wave slot, summed over the tiles: below it a frame counts as LIGHT
-    uint32_t persistent_workgroups(uint32_t per_cu) const { return (uint32_t)cus * per_cu; }
-};
-DeviceShape device_shape_of(int cus);                      // (pure: include/gsrast_amd.h gsr_device_shape, tests/test_capi_cpu.py)
 int current_device_shape(DeviceShape* out);                // the current device's, cached per device (api.hip)
 int tile_order_workgroups(const FrameDims& d);
 // ticks / ticks_before: the tile times of the history's last frame and of the one before it; *sorted = false (and nothing
