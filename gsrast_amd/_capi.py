@@ -35,6 +35,7 @@ GSR_FLAG_NO_DEEP_TILES = 0x200
 GSR_FLAG_DEEP_TILES_ALL = 0x400
 GSR_FLAG_DEEP_WAVES_8 = 0x800
 GSR_FLAG_DEEP_WAVES_16 = 0x1000
+GSR_FLAG_DEPTH_INVERSE = 0x2000
 GSR_PLAN_LISTS_SKIPPED = 0x100
 GSR_PLAN_BLEND_FROM_LISTS = 0x200
 GSR_PLAN_TILES_REORDERED = 0x400
@@ -105,6 +106,7 @@ class ForwardArgs(C.Structure):
         ("stage_ms", C.c_float * GSR_NUM_STAGES),
         ("plan_used", C.c_uint32),
         ("receipt", ForwardReceipt),
+        ("out_depth", C.c_void_p),
     ]
 
 
@@ -131,6 +133,7 @@ class BackwardArgs(C.Structure):
         ("stage_ms", C.c_float * 2),
         ("cam_pos", C.c_void_p), ("shs", C.c_void_p), ("clamped", C.c_void_p), ("sh_dims", C.c_int32),
         ("receipt", ForwardReceipt),
+        ("dL_dout_depth", C.c_void_p), ("dL_ddepths", C.c_void_p), ("depth_sums_f64", C.c_void_p),
     ]
 
 

@@ -877,7 +877,20 @@ int gsr_forward(gsr_forward_args* a) {
     const uint32_t R = (uint32_t)true_total;               // (= pointOffsets[N - 1], GSCuda.cu:772)
     a->num_rendered = R;
     const float t_cutoff = inria ? 0.0001f : 0.001f;                                        // :653 / upstream
+    // The depth channel (out_depth): the blend's DEPTH instantiations, chosen after every per-call rule has decided — the
+    // rules of frame_policy.hpp never see it, so a call chooses the same plan, feed, overlap and deep tiles with or without it.
+    DepthTarget depth;
+    depth.out = a->out_depth;
+    depth.means3D = a->means3D;
+    depth.view = a->view_matrix;
+    depth.inverse = (a->flags & GSR_FLAG_DEPTH_INVERSE) ? 1u : 0u;
     if (R == 0) {
+        // (no record: the channel is zero on every pixel of the processed rows)
+        if (a->out_depth) {
+            const int y0 = d.row_begin * kTile, y1 = std::min(d.row_end * kTile, a->height);
+            if (y1 > y0)
+                GSR_HIP_TRY(hipMemsetAsync(a->out_depth + (size_t)y0 * (size_t)a->width, 0, sizeof(float) * (size_t)(y1 - y0) * (size_t)a->width, stream));
+        }
         // (colours beside the blend: there is no blend — the zeros of a frame without a tile are written here)
         if (colors_mode == 2) GSR_STEP(launch_colors(colors_early, n - (int)colors_early, stream));
         if (!inria) { issue_receipt((uint32_t)nv, nullptr); return fail(GSR_OK); }          // :775-778
@@ -1035,12 +1048,12 @@ int gsr_forward(gsr_forward_args* a) {
     if (plan.block_fed)
         GSR_STEP(launch_blend_blocks(nv, d, R, gs.block_scratch, bin.values_unsorted, bin.sorting_space, img.ranges, geom.means2D,
                                      colors, geom.conic_opacity, img.accum_alpha, img.n_contrib, a->background, a->out_color,
-                                     count_staged ? g_rb.staged_dev : nullptr, t_cutoff, blend_stream, t_order, t_ticks, colors_late));
+                                     count_staged ? g_rb.staged_dev : nullptr, t_cutoff, blend_stream, t_order, t_ticks, colors_late, depth));
     else
         GSR_STEP(launch_blend(d, img.ranges, bin.values, geom.means2D, colors, geom.conic_opacity, img.accum_alpha,
                               img.n_contrib, a->background, a->out_color, count_staged ? g_rb.staged_dev : nullptr,
                               t_cutoff, blend_stream, gs.sort_info + 4, R, t_order, t_ticks, colors_late,
-                              deep.deep_wanted ? hist->deep : nullptr, deep.deep_all, deep.deep_waves));   // :804-810
+                              deep.deep_wanted ? hist->deep : nullptr, deep.deep_all, deep.deep_waves, depth));   // :804-810
     if (order_now) hist->order_serial = serial;               // (the blend that takes the order is in its stream: a backward of this call may take it too)
     if (profile) { GSR_HIP_TRY(hipEventRecord(g_rb.ev[2 * GSR_STAGE_BLEND + 1], blend_stream)); g_rb.recorded[GSR_STAGE_BLEND] = true; }
     if (plan.overlap) {                                                     // the image is complete when the side stream is

@@ -42,6 +42,13 @@ struct RenderBackwardParams {
     FrameDims dims;
     int num_tiles;
     const uint32_t* tile_order;  // the forward blend's workgroup order (slow tiles first), or null: patch order
+    // depth channel (read by render_backward_kernel<true> only; gsr_backward_args.dL_dout_depth)
+    const float* dL_dout_depth;  // f32[W H]
+    const float4* means3D;       // d_i is recomputed from these (blend_core.hpp: depth_value)
+    const float* view;           // the view matrix (row 2 is read)
+    uint32_t depth_inverse;      // GSR_FLAG_DEPTH_INVERSE
+    float* dL_ddepths;           // f32[N]: float atomics, unless depth_sums64 keeps the sums
+    double* depth_sums64;        // f64[N] or null (with sums64)
 };
 
 // Sums of TWELVE per-lane values over the 64 lanes in about half the steps of twelve separate reductions: v_permlane32_swap
@@ -99,19 +106,23 @@ __device__ __forceinline__ float wave_sum12(float a0, float a1, float a2, float 
 // block lists): with per-entry sums for every block that frame went from 1.26 to 1.38 ms, with a limit of four units
 // from 1.04 to 1.14 ms, with two it is unchanged.
 constexpr uint32_t kAccMaxUnits = 2;
-constexpr uint32_t kAccFloats = 12;     // sums per entry: mean2D (2), conic + opacity (4), colour (3), cov2D (3)
+constexpr uint32_t kAccFloats = 12;     // sums per entry: mean2D (2), conic + opacity (4), colour (3), cov2D (3) — also the layout of sums64
+// ... and a thirteenth with the depth channel (dL/dd_i): where 13 floats per entry do not fit, the direct atomics
+template <bool DEPTH> constexpr uint32_t kAccOf = DEPTH ? kAccFloats + 1u : kAccFloats;
+template <bool DEPTH>
 __device__ __forceinline__ bool block_acc_fits(const BlockFeed& f, uint32_t b) {
-    return f.acc != nullptr && (unsigned long long)kAccFloats * (unsigned long long)f.meta.list_start()[f.meta.nbp] <= f.acc_floats &&
+    return f.acc != nullptr && (unsigned long long)kAccOf<DEPTH> * (unsigned long long)f.meta.list_start()[f.meta.nbp] <= f.acc_floats &&
            f.meta.walked()[b] <= kAccMaxUnits;
 }
 
 // Both helpers: workgroup (b, part) of kAccParts takes a slice of the entries of block b that the forward blend
 // looked into (whole units from the front of the block's list; a pixel's last contributor lies there).
 constexpr uint32_t kAccParts = 4;
+template <bool DEPTH>
 __device__ __forceinline__ void walked_slice(const BlockFeed& f, size_t& e0, size_t& e1) {
     const uint32_t b = blockIdx.x / kAccParts, part = blockIdx.x % kAccParts;
     e0 = e1 = 0;
-    if (!block_acc_fits(f, b)) return;
+    if (!block_acc_fits<DEPTH>(f, b)) return;
     const size_t first = f.meta.list_start()[b], end = f.meta.list_start()[b + 1];
     const size_t upto = min(end, first + (size_t)f.meta.walked()[b] * kUnit);
     const size_t per = ((upto - first + kAccParts - 1) / kAccParts + 3) / 4 * 4;
@@ -119,27 +130,39 @@ __device__ __forceinline__ void walked_slice(const BlockFeed& f, size_t& e0, siz
     e1 = min(upto, e0 + per);
 }
 
+template <bool DEPTH>
 __global__ __launch_bounds__(256) void zero_block_acc_kernel(const BlockFeed f) {
+    constexpr uint32_t kAcc = kAccOf<DEPTH>;
     size_t e0, e1;
-    walked_slice(f, e0, e1);
-    for (size_t i = kAccFloats * e0 + threadIdx.x; i < kAccFloats * e1; i += 256) f.acc[i] = 0.0f;
+    walked_slice<DEPTH>(f, e0, e1);
+    for (size_t i = kAcc * e0 + threadIdx.x; i < kAcc * e1; i += 256) f.acc[i] = 0.0f;
 }
 
+// (DEPTH: the thirteenth sum goes to depth_sums64 beside sums64, or to dL_ddepths beside the float arrays)
+template <bool DEPTH>
 __global__ __launch_bounds__(256) void flush_block_acc_kernel(const BlockFeed f, float* __restrict__ dL_dmean2D,
                                                               float* __restrict__ dL_dconic_opacity, float* __restrict__ dL_dcolors,
-                                                              float* __restrict__ dL_dcov2D, double* __restrict__ sums64) {
+                                                              float* __restrict__ dL_dcov2D, double* __restrict__ sums64,
+                                                              float* __restrict__ dL_ddepths, double* __restrict__ depth_sums64) {
+    constexpr uint32_t kAcc = kAccOf<DEPTH>;
     size_t e0, e1;
-    walked_slice(f, e0, e1);
+    walked_slice<DEPTH>(f, e0, e1);
     for (size_t e = e0 + threadIdx.x; e < e1; e += 256) {
-        const float* a = f.acc + kAccFloats * e;
-        float v[kAccFloats];
+        const float* a = f.acc + kAcc * e;
+        float v[kAcc];
 #pragma unroll
-        for (int k = 0; k < (int)kAccFloats; ++k) v[k] = a[k];
+        for (int k = 0; k < (int)kAcc; ++k) v[k] = a[k];
         bool any = false;
 #pragma unroll
-        for (int k = 0; k < (int)kAccFloats; ++k) any = any || v[k] != 0.0f;
+        for (int k = 0; k < (int)kAcc; ++k) any = any || v[k] != 0.0f;
         if (!any) continue;
         const size_t id = f.ent_idx[e];
+        if constexpr (DEPTH) {
+            if (v[kAccFloats] != 0.0f) {
+                if (sums64) unsafeAtomicAdd(depth_sums64 + id, (double)v[kAccFloats]);
+                else unsafeAtomicAdd(dL_ddepths + id, v[kAccFloats]);
+            }
+        }
         if (sums64) {
 #pragma unroll
             for (int k = 0; k < (int)kAccFloats; ++k)
@@ -156,7 +179,20 @@ __global__ __launch_bounds__(256) void flush_block_acc_kernel(const BlockFeed f,
     }
 }
 
+// The staging slot of d_i (DEPTH only: the kernel without the depth channel keeps its LDS as it was)
+template <bool DEPTH> struct DepthSlots { __device__ static float* get() { return nullptr; } };
+template <> struct DepthSlots<true> {
+    __device__ static float* get() {
+        __shared__ float s_dep[kWave];
+        return s_dep;
+    }
+};
+
+// DEPTH: the depth channel too (gsr_backward_args.dL_dout_depth): d_i is staged beside the colour, its g_d joins the colour dot
+// product cg (and through it the sum S of what lies behind), and a thirteenth sum, dL/dd_i, leaves from lane 2.
+template <bool DEPTH>
 __global__ __launch_bounds__(64) void render_backward_kernel(const RenderBackwardParams p) {
+    float* const s_dep = DepthSlots<DEPTH>::get();
     __shared__ uint32_t s_id[kWave];
     __shared__ float2 s_xy[kWave];
     __shared__ float4 s_co[kWave];
@@ -178,6 +214,7 @@ __global__ __launch_bounds__(64) void render_backward_kernel(const RenderBackwar
 
     uint32_t last[4];
     float T[4], S[4], g0[4], g1[4], g2[4], fy[4];
+    float gd[4] = {0.0f, 0.0f, 0.0f, 0.0f};         // dL/d out_depth (DEPTH)
     uint32_t hi = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -190,6 +227,7 @@ __global__ __launch_bounds__(64) void render_backward_kernel(const RenderBackwar
             last[k] = p.n_contrib[pid];
             T[k] = p.final_t[pid];
             g0[k] = p.dL_dout[pid]; g1[k] = p.dL_dout[pid + plane]; g2[k] = p.dL_dout[pid + 2 * plane];
+            if constexpr (DEPTH) gd[k] = p.dL_dout_depth[pid];
         }
         S[k] = T[k] * (bg0 * g0[k] + bg1 * g1[k] + bg2 * g2[k]);     // what lies behind, dotted with dL/dC
         hi = max(hi, last[k]);
@@ -205,6 +243,7 @@ __global__ __launch_bounds__(64) void render_backward_kernel(const RenderBackwar
     // pixels; they are dropped here, one lane per record, instead of being walked by the whole wave.
     // Which of a record's twelve sums this lane files (wave_sum12 leaves them in lanes 0, 8, ..., 56 and 4, 20, 36, 52), and
     // where: one atomic instruction with twelve lanes instead of twelve instructions with one.
+    constexpr uint32_t kAcc = kAccOf<DEPTH>;          // per-entry sums: floats per entry
     constexpr int kSumOfRow[8] = {0, 4, 2, 6, 1, 5, 3, 7};
     constexpr int kSumOfRow4[4] = {8, 10, 9, 11};
     int my_sum = (lane & 7) == 0 ? kSumOfRow[lane >> 3] : ((lane & 15) == 4 ? kSumOfRow4[lane >> 4] : -1);
@@ -226,6 +265,12 @@ __global__ __launch_bounds__(64) void render_backward_kernel(const RenderBackwar
             s_co[slot] = co_l;
             const float* col = p.colors + 3 * (size_t)id;
             s_rgb[slot] = make_float4(col[0], col[1], col[2], __uint_as_float(idx_l));
+            if constexpr (DEPTH) {
+                // d_i as the forward blend computed it (blend_core.hpp: depth_value)
+                const float4 m = p.means3D[id];
+                const float z = (p.view[2] * m.x + p.view[6] * m.y) + (p.view[10] * m.z + p.view[14] * 1.0f);
+                s_dep[slot] = p.depth_inverse ? 1.0f / z : z;
+            }
             // A pixel can pass alpha >= 1/255 only where power >= -ln(255 opacity) (less a margin for the rounding of the
             // logarithm, the exponential and the product; NaN opacity: the reference's min(0.99, NaN) is 0.99, it counts)
             const float op = co_l.w;
@@ -239,6 +284,9 @@ __global__ __launch_bounds__(64) void render_backward_kernel(const RenderBackwar
             const float dx = xy.x - fx;
             float a_mx = 0.0f, a_my = 0.0f, a_A = 0.0f, a_B = 0.0f, a_C = 0.0f, a_op = 0.0f, a_r = 0.0f, a_g = 0.0f, a_b = 0.0f;
             float a_m00 = 0.0f, a_m01 = 0.0f, a_m11 = 0.0f;
+            float a_d = 0.0f;                                    // (DEPTH)
+            float dep = 0.0f;
+            if constexpr (DEPTH) dep = s_dep[j];
             bool any = false;
             // The reference's three per-pixel tests (GSCuda.cu:636-655) decide, as in the forward, with the forward's own
             // arithmetic; what they guard runs for the whole strip without branches — a lane that fails them adds zeros
@@ -269,9 +317,11 @@ __global__ __launch_bounds__(64) void render_backward_kernel(const RenderBackwar
                 const float inv = __builtin_amdgcn_rcpf(1.0f - alpha);
                 const float Tn = T[k] * inv;                     // transmittance in front of this record
                 T[k] = act ? Tn : T[k];
-                const float cg = __builtin_fmaf(col.x, g0[k], __builtin_fmaf(col.y, g1[k], col.z * g2[k]));
+                float cg = __builtin_fmaf(col.x, g0[k], __builtin_fmaf(col.y, g1[k], col.z * g2[k]));
+                if constexpr (DEPTH) cg = __builtin_fmaf(dep, gd[k], cg);
                 const float w = act ? alpha * Tn : 0.0f;
                 a_r = __builtin_fmaf(w, g0[k], a_r); a_g = __builtin_fmaf(w, g1[k], a_g); a_b = __builtin_fmaf(w, g2[k], a_b);
+                if constexpr (DEPTH) a_d = __builtin_fmaf(w, gd[k], a_d);
                 const float dL_dalpha = __builtin_fmaf(Tn, cg, -(S[k] * inv));
                 S[k] = __builtin_fmaf(cg, w, S[k]);
                 const bool live = __builtin_amdgcn_inverse_ballot_w64(act_mask & ~__ballot(raw > 0.99f));   // clamped: alpha does not move with the parameters
@@ -299,7 +349,18 @@ __global__ __launch_bounds__(64) void render_backward_kernel(const RenderBackwar
                 // fills the screen gets its sums from 8 160 tiles with terms of either sign: in float the order of arrival
                 // showed in the fourth digit of its gradients)
                 if (!per_entry && p.sums64) unsafeAtomicAdd(p.sums64 + kAccFloats * key + my_sum, (double)total);
-                else unsafeAtomicAdd(per_entry ? p.feed.acc + kAccFloats * key + my_sum : direct_base + direct_stride * key, total);
+                else unsafeAtomicAdd(per_entry ? p.feed.acc + kAcc * key + my_sum : direct_base + direct_stride * key, total);
+            }
+            if constexpr (DEPTH) {
+                float td = a_d;
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) td += __shfl_xor(td, off, kWave);
+                if (lane == 2 && td != 0.0f) {                  // (a lane wave_sum12 leaves idle)
+                    const size_t key = s_id[j];
+                    if (per_entry) unsafeAtomicAdd(p.feed.acc + kAcc * key + kAccFloats, td);
+                    else if (p.depth_sums64) unsafeAtomicAdd(p.depth_sums64 + key, (double)td);
+                    else unsafeAtomicAdd(p.dL_ddepths + key, td);
+                }
             }
         }
     };
@@ -315,7 +376,7 @@ __global__ __launch_bounds__(64) void render_backward_kernel(const RenderBackwar
     };
     const BlockFeed& f = p.feed;
     const uint32_t b = (uint32_t)(ty / kBH) * (uint32_t)f.nbx + (uint32_t)(tx / kBW);
-    per_entry = f.ent_idx != nullptr && block_acc_fits(f, b);
+    per_entry = f.ent_idx != nullptr && block_acc_fits<DEPTH>(f, b);
     const bool sorted = p.point_list && !per_entry;
     // -- sorted list: batch c = list positions [64 c, 64 c + 64) below hi
     int it_c = (int)((hi - 1) / kWave);
@@ -425,6 +486,12 @@ struct PreprocessBackwardParams {
     const float* shs;
     const float* cam_pos;
     const uint8_t* clamped;   // GeometryState::clamped of the forward call: channel c of Gaussian i was clamped at zero
+    // depth channel: dL/dd_i from depth_sums64 (rounded into out_ddepths, the doubles left zero) or from the float array dL_ddepths;
+    // d_i = z_i (or 1 / z_i) adds dL/dd_i (V[2], V[6], V[10]) (times -1 / z_i^2) to dL_dmeans3D
+    int depth, depth_inverse;
+    const float* dL_ddepths;
+    double* depth_sums64;
+    float* out_ddepths;
 };
 
 __constant__ float kShC2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f, -1.0925484305920792f,
@@ -490,6 +557,8 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(const Preproce
 #pragma unroll
         for (int k = 0; k < 6; ++k) { const double2 v2 = sp[k]; sum[2 * k] = v2.x; sum[2 * k + 1] = v2.y; }
     }
+    double gdep = 0.0;                                         // dL/dd_i (depth channel)
+    if (p.depth && has_tile) gdep = p.sums64 ? p.depth_sums64[idx] : (p.chain ? (double)p.dL_ddepths[idx] : 0.0);
     if (visible) {
         mean = p.means3D[idx];
         const float2* c3p = reinterpret_cast<const float2*>(p.cov3D + 6 * (size_t)idx);
@@ -616,6 +685,12 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(const Preproce
                 const R dx = 0.5 * (R)p.width * ((R)pm[4 * j + 0] * iw - hx * (R)pm[4 * j + 3] * iw2);
                 const R dy = 0.5 * (R)p.height * ((R)pm[4 * j + 1] * iw - hy * (R)pm[4 * j + 3] * iw2);
                 gmean[j] += dx * sum[0] + dy * sum[1];
+            }
+            if (p.depth) {
+                // d_i = z_i = row 2 of the view matrix applied to the mean; inverse depth: d(1/z) = -dz / z^2
+                const R gz = p.depth_inverse ? -gdep / (tz * tz) : gdep;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) gmean[j] += gz * v[4 * j + 2];
             }
         }
     }
@@ -753,6 +828,10 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(const Preproce
             oc[0] = (float)sum[6]; oc[1] = (float)sum[7]; oc[2] = (float)sum[8];
         }
         if (p.out_cov2D) p.out_cov2D[idx] = make_float4((float)sum[9], (float)sum[10], (float)sum[11], 0.0f);
+        if (p.depth) {
+            if (p.out_ddepths) p.out_ddepths[idx] = (float)gdep;
+            if (gdep != 0.0) p.depth_sums64[idx] = 0.0;
+        }
         // (most Gaussians with a tile lie behind every pixel's last contributor and received nothing: no write for those)
         bool touched = false;
 #pragma unroll
@@ -841,6 +920,9 @@ static int backward_impl(gsr_backward_args* a) {
     const bool inria = (a->flags & GSR_FLAG_SEMANTICS_INRIA) != 0;
     // the upstream profile's chain needs what its colour was computed from
     if (inria && a->dL_dshs && (!a->shs || !a->cam_pos || !a->clamped || !a->means3D)) return GSR_ERR_INVALID_ARG;
+    // the depth channel: d_i is recomputed from means3D and the view; its sums go to depth_sums_f64 beside sums_f64, else to dL_ddepths
+    const bool depth = a->dL_dout_depth != nullptr;
+    if (depth && (!a->means3D || !a->view_matrix || (wide ? !a->depth_sums_f64 : !a->dL_ddepths))) return GSR_ERR_INVALID_ARG;
     hipStream_t stream = (hipStream_t)a->stream;
     const bool profile = (a->flags & GSR_FLAG_PROFILE) != 0;
     CallEvents g_bw;
@@ -885,6 +967,7 @@ static int backward_impl(gsr_backward_args* a) {
         if (a->dL_dconic_opacity) GSR_HIP_TRY(hipMemsetAsync(a->dL_dconic_opacity, 0, sizeof(float) * 4 * (size_t)n, stream));
         if (a->dL_dcolors) GSR_HIP_TRY(hipMemsetAsync(a->dL_dcolors, 0, sizeof(float) * 3 * (size_t)n, stream));
         if (a->dL_dcov2D) GSR_HIP_TRY(hipMemsetAsync(a->dL_dcov2D, 0, sizeof(float) * 4 * (size_t)n, stream));
+        if (depth && a->dL_ddepths) GSR_HIP_TRY(hipMemsetAsync(a->dL_ddepths, 0, sizeof(float) * (size_t)n, stream));
     }
     if (nothing_rendered) {
         // R == 0: no Gaussian reached a pixel (the forward call left even the tile ranges unwritten, GSCuda.cu:775-778)
@@ -916,20 +999,33 @@ static int backward_impl(gsr_backward_args* a) {
     r.num_tiles = (d.row_end - d.row_begin) * d.grid_x;
     // (the tiles that were slow in the forward blend are the slow ones here: they go first, as they did there)
     r.tile_order = have_receipt ? tile_order_of_call(a->receipt, d.row_begin, d.row_end) : nullptr;
+    r.dL_dout_depth = a->dL_dout_depth;
+    r.means3D = reinterpret_cast<const float4*>(a->means3D);
+    r.view = a->view_matrix;
+    r.depth_inverse = (a->flags & GSR_FLAG_DEPTH_INVERSE) ? 1u : 0u;
+    r.dL_ddepths = a->dL_ddepths;
+    r.depth_sums64 = wide ? a->depth_sums_f64 : nullptr;
     // (all blocks of the frame, also in a sharded call: the blocks outside the band were not walked)
     const unsigned acc_wgs = (unsigned)(((d.grid_x + kBW - 1) / kBW) * ((d.grid_y + kBH - 1) / kBH)) * kAccParts;
     if (r.num_tiles > 0) {
-        if (from_blocks && feed.acc) {
-            hipLaunchKernelGGL(zero_block_acc_kernel, dim3(acc_wgs), dim3(256), 0, stream, feed);
-            GSR_LAUNCH_CHECK("zero_block_acc_kernel");
-        }
-        hipLaunchKernelGGL(render_backward_kernel, dim3((unsigned)patch_workgroups(d.grid_x, d.row_end - d.row_begin)), dim3(kWave), 0, stream, r);
-        GSR_LAUNCH_CHECK("render_backward_kernel");
-        if (from_blocks && feed.acc) {
-            hipLaunchKernelGGL(flush_block_acc_kernel, dim3(acc_wgs), dim3(256), 0, stream, feed, a->dL_dmean2D, a->dL_dconic_opacity,
-                               a->dL_dcolors, a->dL_dcov2D, a->sums_f64);
-            GSR_LAUNCH_CHECK("flush_block_acc_kernel");
-        }
+        const dim3 grid((unsigned)patch_workgroups(d.grid_x, d.row_end - d.row_begin));
+        auto launch = [&](auto with_depth) -> int {
+            constexpr bool D = decltype(with_depth)::value;
+            if (from_blocks && feed.acc) {
+                hipLaunchKernelGGL(zero_block_acc_kernel<D>, dim3(acc_wgs), dim3(256), 0, stream, feed);
+                GSR_LAUNCH_CHECK("zero_block_acc_kernel");
+            }
+            hipLaunchKernelGGL(render_backward_kernel<D>, grid, dim3(kWave), 0, stream, r);
+            GSR_LAUNCH_CHECK("render_backward_kernel");
+            if (from_blocks && feed.acc) {
+                hipLaunchKernelGGL(flush_block_acc_kernel<D>, dim3(acc_wgs), dim3(256), 0, stream, feed, a->dL_dmean2D, a->dL_dconic_opacity,
+                                   a->dL_dcolors, a->dL_dcov2D, a->sums_f64, r.dL_ddepths, r.depth_sums64);
+                GSR_LAUNCH_CHECK("flush_block_acc_kernel");
+            }
+            return GSR_OK;
+        };
+        const int rc = depth ? launch(std::true_type{}) : launch(std::false_type{});
+        if (rc != GSR_OK) return rc;
     }
     if (profile) GSR_HIP_TRY(hipEventRecord(g_bw_ev[1], stream));
     if (chain || wide) {
@@ -966,6 +1062,11 @@ static int backward_impl(gsr_backward_args* a) {
         q.focal_x = (float)a->width / (2.0f * a->tan_fovx);
         q.focal_y = (float)a->height / (2.0f * a->tan_fovy);
         q.w_eps = 0.0000001f;
+        q.depth = depth ? 1 : 0;
+        q.depth_inverse = (int)r.depth_inverse;
+        q.dL_ddepths = a->dL_ddepths;
+        q.depth_sums64 = r.depth_sums64;
+        q.out_ddepths = a->dL_ddepths;
         q.shs = a->shs; q.cam_pos = a->cam_pos; q.clamped = a->clamped;
         if (inria) hipLaunchKernelGGL(preprocess_backward_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, q);
         else hipLaunchKernelGGL(preprocess_backward_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, q);

@@ -45,6 +45,7 @@ struct BlendParams {
     const uint32_t* deep_count;    // device word: leading entries of the order that are DEEP tiles (four waves, one walk), or null
     int deep_all;                  // every tile is one (GSR_FLAG_DEEP_TILES_ALL)
     uint32_t dc_stride;            // 0, or 48: `colors` is the SH array (TileFeed::dc_stride)
+    DepthTarget depth;             // the depth channel (read by the DEPTH kernels only)
 };
 
 // One wave per tile leaves most of the chip idle when few tiles have a list, and the frame lasts as long as the slowest
@@ -101,7 +102,8 @@ enum { kBlendSingle = 0, kBlendGrouped = 1, kBlendDeepOnly = 2 };
 // W: the waves of a workgroup — 4; 8 or 16 in the deep-only kernel for frames whose work sits in a few hundred tiles (a far
 // view of a dense scene): strips of 16 x 2 or 16 x 1 pixels, the upper lanes of a wave idle — on a chip with a wave per
 // SIMD idle lanes cost nothing, and two waves on a SIMD issue twice what one does (`profiles/r06_micro_valu_issue.txt`).
-template <int MODE, int W = kGroupWaves>
+// DEPTH: the depth channel too (out_depth): d_i is staged beside the record, one more accumulator per pixel.
+template <int MODE, int W, bool DEPTH>
 __device__ __forceinline__ void blend_wave_body(const BlendParams& p) {
     constexpr bool GROUPED = MODE != kBlendSingle, DEEP_ONLY = MODE == kBlendDeepOnly;
     static_assert(W == kGroupWaves || DEEP_ONLY, "more than four waves: the deep-only kernel");
@@ -109,10 +111,11 @@ __device__ __forceinline__ void blend_wave_body(const BlendParams& p) {
     constexpr int kRows = kTile / (GROUPED ? W : 4);
     constexpr uint32_t kBuffers = DEEP_ONLY ? 1u : 2u;
     // (one area, two uses: a wave's own staging records in the ordinary mode; two rounds of four segments in the deep one)
-    constexpr size_t kStageBytes = !GROUPED ? sizeof(StagedRecords)
+    using Stage = Staged<DEPTH>;
+    constexpr size_t kStageBytes = !GROUPED ? sizeof(Stage)
                                    : DEEP_ONLY ? sizeof(DeepSegment) * W
-                                   : (sizeof(DeepSegment) * 2 * kGroupWaves > sizeof(StagedRecords) * kGroupWaves ? sizeof(DeepSegment) * 2 * kGroupWaves
-                                                                                                                : sizeof(StagedRecords) * kGroupWaves);
+                                   : (sizeof(DeepSegment) * 2 * kGroupWaves > sizeof(Stage) * kGroupWaves ? sizeof(DeepSegment) * 2 * kGroupWaves
+                                                                                                        : sizeof(Stage) * kGroupWaves);
     __shared__ __attribute__((aligned(16))) unsigned char s_stage[kStageBytes];
     __shared__ unsigned long long s_exp[kWavesHere][32];   // exp_ref's table, a copy per wave
     __shared__ uint32_t s_count[2][kWavesHere];            // deep: survivors per segment of a round
@@ -156,6 +159,7 @@ __device__ __forceinline__ void blend_wave_body(const BlendParams& p) {
     feed.dc_stride = p.dc_stride;
     feed.box = tile_box(tx, ty, p.dims.width, p.dims.height);
     feed.total = total; feed.t_cutoff = p.t_cutoff;
+    if constexpr (DEPTH) feed_depth(feed, p.depth);
     // batch k = list positions [64 k, 64 k + 64); ids are fetched two batches ahead, records one batch ahead
     auto next_batch = [&](uint32_t pos) {
         RecordBatch nb;
@@ -192,7 +196,7 @@ __device__ __forceinline__ void blend_wave_body(const BlendParams& p) {
                 const DeepSegment& seg = segs[half][g];
                 const unsigned long long slots = __ballot((uint32_t)lane < cnt && ((seg.touch[lane] >> wave) & 1u) != 0u);
                 uint32_t at = 0;
-                if (slots != 0ull && composite_strip(s, seg, slots, feed.t_cutoff, exp_tab, &at)) {
+                if (slots != 0ull && composite_strip<DEPTH>(s, seg, slots, feed.t_cutoff, exp_tab, &at)) {
                     my_done = true;
                     if (lane == 0) { s_done[wave] = 1u; s_done_at[wave] = at; }
                     break;
@@ -208,7 +212,7 @@ __device__ __forceinline__ void blend_wave_body(const BlendParams& p) {
             for (uint32_t pos = 0; pos < total; pos += kRound) {
                 fetch_records(b1, feed);
                 const RecordBatch b2 = next_batch(pos + 2 * kRound + (uint32_t)(wave * kWave));
-                const uint32_t kept = b0.valid ? stage_batch_deep<W>(feed, segs[0][wave], b0, p.dims.height) : 0u;
+                const uint32_t kept = b0.valid ? stage_batch_deep<W, DEPTH>(feed, segs[0][wave], b0, p.dims.height) : 0u;
                 if (lane == 0) s_count[0][wave] = kept;
                 round_barrier();                         // the round's four segments are staged
                 if (!my_done) composite_round(0u);
@@ -223,7 +227,7 @@ __device__ __forceinline__ void blend_wave_body(const BlendParams& p) {
             fetch_records(b1, feed);
             RecordBatch b2 = next_batch(2 * kRound + (uint32_t)(wave * kWave));
             {
-                const uint32_t kept = b0.valid ? stage_batch_deep<W>(feed, segs[0][wave], b0, p.dims.height) : 0u;
+                const uint32_t kept = b0.valid ? stage_batch_deep<W, DEPTH>(feed, segs[0][wave], b0, p.dims.height) : 0u;
                 if (lane == 0) s_count[0][wave] = kept;
             }
             round_barrier();
@@ -231,7 +235,7 @@ __device__ __forceinline__ void blend_wave_body(const BlendParams& p) {
                 // (b1: round r + 1, its records on their way since the round before; b2: round r + 2, its ids)
                 fetch_records(b2, feed);
                 const RecordBatch b3 = next_batch(pos + 3 * kRound + (uint32_t)(wave * kWave));
-                const uint32_t kept = b1.valid ? stage_batch_deep<W>(feed, segs[(r + 1u) & 1u][wave], b1, p.dims.height) : 0u;
+                const uint32_t kept = b1.valid ? stage_batch_deep<W, DEPTH>(feed, segs[(r + 1u) & 1u][wave], b1, p.dims.height) : 0u;
                 if (lane == 0) s_count[(r + 1u) & 1u][wave] = kept;
                 if (!my_done) composite_round(r & 1u);
                 round_barrier();                            // round r is composited, round r + 1 staged, the flags are visible
@@ -240,7 +244,7 @@ __device__ __forceinline__ void blend_wave_body(const BlendParams& p) {
                 b2 = b3;
             }
         }
-        strip_lanes_write(s, p.dims.width, p.dims.height, p.background, p.final_t, p.n_contrib, p.out_color);
+        strip_lanes_write<DEPTH>(s, p.dims.width, p.dims.height, p.background, p.final_t, p.n_contrib, p.out_color, p.depth.out);
         if (wave == 0 && lane == 0) {
             if (p.staged_counter) {
                 // (the loop was left through a barrier: the flags are final)
@@ -256,7 +260,7 @@ __device__ __forceinline__ void blend_wave_body(const BlendParams& p) {
         return;
     }
     if constexpr (!DEEP_ONLY) {
-    StagedRecords& mine = reinterpret_cast<StagedRecords*>(s_stage)[wave];
+    Stage& mine = reinterpret_cast<Stage*>(s_stage)[wave];
     TileLanes s;
     tile_lanes_init(s, tx, ty, lane, p.dims.width, p.dims.height, -1);
     unsigned long long staged = 0;
@@ -271,7 +275,7 @@ __device__ __forceinline__ void blend_wave_body(const BlendParams& p) {
         for (uint32_t pos = 2 * kWave; b0.valid && !all_done; pos += kWave) {
             fetch_records(b1, feed);
             RecordBatch b2 = next_batch(pos);
-            all_done = stage_and_composite(s, feed, mine, b0, staged, exp_tab);
+            all_done = stage_and_composite<DEPTH>(s, feed, mine, b0, staged, exp_tab);
             b0 = b1;
             b1 = b2;
             if (with_priority.value) set_tile_priority(total - min(total, pos));
@@ -279,17 +283,25 @@ __device__ __forceinline__ void blend_wave_body(const BlendParams& p) {
     };
     if (prioritise) walk(std::true_type{});
     else walk(std::false_type{});
-    tile_lanes_write(s, p.dims.width, p.dims.height, p.background, p.final_t, p.n_contrib, p.out_color);
+    tile_lanes_write<DEPTH>(s, p.dims.width, p.dims.height, p.background, p.final_t, p.n_contrib, p.out_color, p.depth.out);
     if (p.staged_counter && lane == 0) atomicAdd(p.staged_counter, staged);
     if (p.history.ticks && lane == 0) p.history.ticks[tile] = (tile_clock() - clock_begin) & ~kDeepFlag;
     }
 }
 
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(5))) void blend_wave_kernel(const BlendParams p) { blend_wave_body<kBlendSingle>(p); }
-__global__ __launch_bounds__(kGroupWaves * kWave) __attribute__((amdgpu_waves_per_eu(4))) void blend_group_kernel(const BlendParams p) { blend_wave_body<kBlendGrouped>(p); }
-__global__ __launch_bounds__(kGroupWaves * kWave) __attribute__((amdgpu_waves_per_eu(8))) void blend_deep_kernel(const BlendParams p) { blend_wave_body<kBlendDeepOnly>(p); }
-__global__ __launch_bounds__(8 * kWave) __attribute__((amdgpu_waves_per_eu(8))) void blend_deep8_kernel(const BlendParams p) { blend_wave_body<kBlendDeepOnly, 8>(p); }
-__global__ __launch_bounds__(16 * kWave) __attribute__((amdgpu_waves_per_eu(4))) void blend_deep16_kernel(const BlendParams p) { blend_wave_body<kBlendDeepOnly, 16>(p); }
+// (each twice: DEPTH = false is the kernel of the calls without out_depth, DEPTH = true writes the depth channel as well. The
+// depth kernels keep the same bounds where the extra accumulators fit them without spilling; where they do not — blend_wave_kernel's
+// 96 registers under five waves, blend_deep8_kernel's 64 under eight — one wave fewer per SIMD.)
+template <bool DEPTH>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(DEPTH ? 4 : 5))) void blend_wave_kernel(const BlendParams p) { blend_wave_body<kBlendSingle, kGroupWaves, DEPTH>(p); }
+template <bool DEPTH>
+__global__ __launch_bounds__(kGroupWaves * kWave) __attribute__((amdgpu_waves_per_eu(4))) void blend_group_kernel(const BlendParams p) { blend_wave_body<kBlendGrouped, kGroupWaves, DEPTH>(p); }
+template <bool DEPTH>
+__global__ __launch_bounds__(kGroupWaves * kWave) __attribute__((amdgpu_waves_per_eu(8))) void blend_deep_kernel(const BlendParams p) { blend_wave_body<kBlendDeepOnly, kGroupWaves, DEPTH>(p); }
+template <bool DEPTH>
+__global__ __launch_bounds__(8 * kWave) __attribute__((amdgpu_waves_per_eu(DEPTH ? 7 : 8))) void blend_deep8_kernel(const BlendParams p) { blend_wave_body<kBlendDeepOnly, 8, DEPTH>(p); }
+template <bool DEPTH>
+__global__ __launch_bounds__(16 * kWave) __attribute__((amdgpu_waves_per_eu(4))) void blend_deep16_kernel(const BlendParams p) { blend_wave_body<kBlendDeepOnly, 16, DEPTH>(p); }
 
 
 // Workgroup numbers of the patch order, the SLOW tiles of the frame before first — those that took more than twice the
@@ -463,8 +475,9 @@ int launch_blend(const FrameDims& d, const uint32_t* ranges, const uint32_t* poi
                  float* final_t, uint32_t* n_contrib, const float* background, float* out_color,
                  unsigned long long* staged_counter, float t_cutoff, hipStream_t stream, const uint32_t* nonempty_tiles,
                  uint32_t num_rendered, const uint32_t* tile_order, uint32_t* tile_ticks, bool colors_are_shs, const uint32_t* deep_count,
-                 bool deep_all, int deep_waves) {
+                 bool deep_all, int deep_waves, const DepthTarget& depth) {
     BlendParams p;
+    p.depth = depth;
     p.deep_count = tile_order ? deep_count : nullptr;      // (the deep tiles are the order's leading entries)
     p.deep_all = deep_all ? 1 : 0;
     p.dc_stride = colors_are_shs ? 48u : 0u;
@@ -493,17 +506,23 @@ int launch_blend(const FrameDims& d, const uint32_t* ranges, const uint32_t* poi
     // workgroup. Every other frame is launched a wave per workgroup, as ever.
     const bool few_tiles = p.nonempty != nullptr && ((uint32_t)p.num_tiles <= kStripTilesAny ||
                                                      (unsigned long long)num_rendered <= (unsigned long long)kStripMeanList * kStripTilesShort);
-    if (p.deep_all && deep_waves == 16)
-        hipLaunchKernelGGL(blend_deep16_kernel, dim3((unsigned)p.base_workgroups), dim3(16 * kWave), 0, stream, p);
-    else if (p.deep_all && deep_waves == 8)
-        hipLaunchKernelGGL(blend_deep8_kernel, dim3((unsigned)p.base_workgroups), dim3(8 * kWave), 0, stream, p);
-    else if (p.deep_all)
-        hipLaunchKernelGGL(blend_deep_kernel, dim3((unsigned)p.base_workgroups), dim3(kGroupWaves * kWave), 0, stream, p);
-    else if (p.deep_count || few_tiles)
-        hipLaunchKernelGGL(blend_group_kernel, dim3((unsigned)(p.base_workgroups + (p.base_workgroups + 31) / 32 * 8)),
-                           dim3(kGroupWaves * kWave), 0, stream, p);
-    else
-        hipLaunchKernelGGL(blend_wave_kernel, dim3((unsigned)p.base_workgroups), dim3(kWave), 0, stream, p);
+    // (the same choice with and without the depth channel: only the instantiation differs)
+    auto launch = [&](auto with_depth) {
+        constexpr bool D = decltype(with_depth)::value;
+        if (p.deep_all && deep_waves == 16)
+            hipLaunchKernelGGL(blend_deep16_kernel<D>, dim3((unsigned)p.base_workgroups), dim3(16 * kWave), 0, stream, p);
+        else if (p.deep_all && deep_waves == 8)
+            hipLaunchKernelGGL(blend_deep8_kernel<D>, dim3((unsigned)p.base_workgroups), dim3(8 * kWave), 0, stream, p);
+        else if (p.deep_all)
+            hipLaunchKernelGGL(blend_deep_kernel<D>, dim3((unsigned)p.base_workgroups), dim3(kGroupWaves * kWave), 0, stream, p);
+        else if (p.deep_count || few_tiles)
+            hipLaunchKernelGGL(blend_group_kernel<D>, dim3((unsigned)(p.base_workgroups + (p.base_workgroups + 31) / 32 * 8)),
+                               dim3(kGroupWaves * kWave), 0, stream, p);
+        else
+            hipLaunchKernelGGL(blend_wave_kernel<D>, dim3((unsigned)p.base_workgroups), dim3(kWave), 0, stream, p);
+    };
+    if (depth.out) launch(std::true_type{});
+    else launch(std::false_type{});
     GSR_LAUNCH_CHECK("blend_wave_kernel");
     return GSR_OK;
 }

@@ -4,6 +4,8 @@
 //
 // Semantics follow reference apps/gsrast/gscuda/GSCuda.cu:623-676 (the loop of renderCUDA); see blend.hip.
 #pragma once
+#include <type_traits>
+
 #include "gsr_common.hpp"
 
 namespace gsr {
@@ -129,6 +131,7 @@ struct TileLanes {                 // per-lane state of the four pixels a lane o
     bool inside[4];
     uint32_t done[4];              // 0 / 1, kept in vector registers (as lane masks they cost scalar merges at every branch join)
     float T[4], cr[4], cg[4], cb[4];
+    float cd[4];                   // depth channel (the DEPTH instantiations; dead in the others)
     uint32_t last[4];
 };
 
@@ -144,7 +147,7 @@ __device__ __forceinline__ void tile_lanes_init(TileLanes& s, int tx, int ty, in
     for (int k = 0; k < 4; ++k) {
         s.inside[k] = s.px < width && (s.py0 + 4 * k) < height && (only_strip < 0 || only_strip == k);
         s.done[k] = s.inside[k] ? 0u : 1u;
-        s.T[k] = 1.0f; s.cr[k] = s.cg[k] = s.cb[k] = 0.0f; s.last[k] = 0;
+        s.T[k] = 1.0f; s.cr[k] = s.cg[k] = s.cb[k] = s.cd[k] = 0.0f; s.last[k] = 0;
     }
     // a finished pixel's row coordinate is NaN: its power is NaN and fails the candidate range test without a test of its own
     const float qnan = __builtin_nanf("");
@@ -182,8 +185,10 @@ constexpr float kFilterSlack = 0.25f;      // in units of the power: covers the 
 // (A record whose power terms are too large for the filter's slack is staged with a zero filter conic and no floor: every
 // unfinished pixel is its candidate, stage_and_composite.)
 // One staged record (slot j) against the wave's pixels; true: some pixel finished on it (the caller then looks whether all have).
+// DEPTH: s_dep[j] is the record's d_i (stage_batch), accumulated into s.cd exactly as a colour channel.
+template <bool DEPTH>
 __device__ __forceinline__ bool composite_record(TileLanes& s, const float2* s_xy, const float4* s_co, const float4* s_rgb,
-                                                 const float4* s_raw, uint32_t j, float t_cutoff,
+                                                 const float4* s_raw, const float* s_dep, uint32_t j, float t_cutoff,
                                                  const unsigned long long* exp_tab) {
     const float qnan = __builtin_nanf("");
     constexpr float kAlphaMin = 1.0f / 255.0f;
@@ -241,6 +246,7 @@ __device__ __forceinline__ bool composite_record(TileLanes& s, const float2* s_x
                 s.cr[k] = __builtin_fmaf(col.x, w, s.cr[k]);
                 s.cg[k] = __builtin_fmaf(col.y, w, s.cg[k]);
                 s.cb[k] = __builtin_fmaf(col.z, w, s.cb[k]);
+                if constexpr (DEPTH) s.cd[k] = __builtin_fmaf(s_dep[j], w, s.cd[k]);
                 s.T[k] = test;
                 s.last[k] = contributor;
             }
@@ -259,11 +265,12 @@ __device__ __forceinline__ bool composite_record(TileLanes& s, const float2* s_x
     return newly_done != 0ull;
 }
 
+template <bool DEPTH>
 __device__ __forceinline__ bool composite_staged(TileLanes& s, const float2* s_xy, const float4* s_co, const float4* s_rgb,
-                                                 const float4* s_raw, uint32_t chunk, float t_cutoff,
+                                                 const float4* s_raw, const float* s_dep, uint32_t chunk, float t_cutoff,
                                                  const unsigned long long* exp_tab) {
     for (uint32_t j = 0; j < chunk; ++j)
-        if (composite_record(s, s_xy, s_co, s_rgb, s_raw, j, t_cutoff, exp_tab) && tile_lanes_all_done(s)) return true;
+        if (composite_record<DEPTH>(s, s_xy, s_co, s_rgb, s_raw, s_dep, j, t_cutoff, exp_tab) && tile_lanes_all_done(s)) return true;
     return false;
 }
 
@@ -282,7 +289,25 @@ struct TileFeed {
     uint32_t dc_stride = 0;         // 0: `colors` are colours, 12 bytes apart. 48: `colors` is the caller's SH array and a record's
                                     // colour is 0.5 + 0.4 DC (GSCuda.cu:362-366, the preprocess's two operations) — geomState.rgb
                                     // is then being written BESIDE this blend (api.hip), for whoever reads the chunk afterwards
+    // depth channel (read by the DEPTH instantiations only)
+    const float4* means3D = nullptr;
+    float4 view_z;                  // (V[2], V[6], V[10], V[14]): row 2 of the view matrix
+    uint32_t depth_inverse = 0;     // GSR_FLAG_DEPTH_INVERSE
 };
+
+__device__ __forceinline__ void feed_depth(TileFeed& f, const DepthTarget& t) {
+    f.means3D = reinterpret_cast<const float4*>(t.means3D);
+    f.view_z = make_float4(t.view[2], t.view[6], t.view[10], t.view[14]);
+    f.depth_inverse = t.inverse;
+}
+
+// d_i of the depth channel, computed when the record is staged (one 16-byte load): the view-space z of the header's definition
+// in its operation order (this file is compiled without contraction), or its reciprocal (an IEEE division).
+__device__ __forceinline__ float depth_value(const TileFeed& f, uint32_t id) {
+    const float4 m = f.means3D[id];
+    const float z = (f.view_z.x * m.x + f.view_z.y * m.y) + (f.view_z.z * m.z + f.view_z.w * 1.0f);
+    return f.depth_inverse ? 1.0f / z : z;
+}
 
 // One batch of up to 64 list entries on its way through the wave: lane l holds entry l. The loads of a batch are
 // issued ahead of its use (ids two batches ahead, records one batch ahead: see the kernels), so the three dependent
@@ -315,10 +340,16 @@ struct StagedRecords {
     float4 raw[kWave];             // conic + opacity as fetched: the reference-order evaluation of the lanes near a threshold
     unsigned long long exp_tab[32];   // exp_ref's table (exp_table_init at the top of the kernel)
 };
+// ... and with the depth channel: d_i of every slot behind it (the staging area of the DEPTH instantiations)
+struct StagedRecordsDepth : StagedRecords {
+    float dep[kWave];
+};
+template <bool DEPTH> using Staged = std::conditional_t<DEPTH, StagedRecordsDepth, StagedRecords>;
 
 // Stages the survivors of one batch (the footprint test, one lane per record) compacted into `st`; returns their number.
 // *before_boundary (optional): how many of them lie in front of the batch's first multiple-of-256 list position.
-__device__ __forceinline__ uint32_t stage_batch(const TileFeed& f, StagedRecords& st, const RecordBatch& b, uint32_t* before_boundary = nullptr) {
+template <bool DEPTH>
+__device__ __forceinline__ uint32_t stage_batch(const TileFeed& f, Staged<DEPTH>& st, const RecordBatch& b, uint32_t* before_boundary = nullptr) {
     float2* const s_xy = st.xy;
     float4* const s_co = st.co;
     float4* const s_rgb = st.rgb;
@@ -351,6 +382,7 @@ __device__ __forceinline__ uint32_t stage_batch(const TileFeed& f, StagedRecords
         float c0 = c[0], c1 = c[1], c2 = c[2];
         if (f.dc_stride != 0u) { c0 = 0.5f + 0.4f * c0; c1 = 0.5f + 0.4f * c1; c2 = 0.5f + 0.4f * c2; }
         s_rgb[slot] = make_float4(c0, c1, c2, __uint_as_float(pos + rank + 1u));
+        if constexpr (DEPTH) st.dep[slot] = depth_value(f, b.id);
     }
     if (before_boundary) {
         const uint32_t boundary = (pos + (uint32_t)kBatch - 1u) & ~((uint32_t)kBatch - 1u);   // first multiple of 256 >= pos
@@ -360,11 +392,14 @@ __device__ __forceinline__ uint32_t stage_batch(const TileFeed& f, StagedRecords
 }
 
 // exp_tab: exp_ref's table in LDS (null: the one in `st`)
-__device__ __forceinline__ bool stage_and_composite(TileLanes& s, const TileFeed& f, StagedRecords& st,
+template <bool DEPTH>
+__device__ __forceinline__ bool stage_and_composite(TileLanes& s, const TileFeed& f, Staged<DEPTH>& st,
                                                     const RecordBatch& b, unsigned long long& staged, const unsigned long long* exp_tab = nullptr) {
     if (!exp_tab) exp_tab = st.exp_tab;
     uint32_t before = 0;
-    const uint32_t kept = stage_batch(f, st, b, &before);
+    const uint32_t kept = stage_batch<DEPTH>(f, st, b, &before);
+    const float* dep = nullptr;
+    if constexpr (DEPTH) dep = st.dep;
     const uint32_t pos = b.pos, count = b.count();
     // wave-private LDS: the writes above and the reads of composite_staged are ordered inside the wave
     bool all_done = false;
@@ -372,12 +407,13 @@ __device__ __forceinline__ bool stage_and_composite(TileLanes& s, const TileFeed
     const uint32_t boundary = (pos + (uint32_t)kBatch - 1u) & ~((uint32_t)kBatch - 1u);   // first multiple of 256 >= pos
     if (boundary < pos + count) {
         // records in front of the boundary first; then the reference would test "whole tile done" and stage the next 256
-        if (before) all_done = composite_staged(s, st.xy, st.co, st.rgb, st.raw, before, f.t_cutoff, exp_tab);
+        if (before) all_done = composite_staged<DEPTH>(s, st.xy, st.co, st.rgb, st.raw, dep, before, f.t_cutoff, exp_tab);
         if (all_done) return true;
         staged += min((uint32_t)kBatch, f.total - boundary);
         first = before;
     }
-    if (kept > first) all_done = composite_staged(s, st.xy + first, st.co + first, st.rgb + first, st.raw + first, kept - first, f.t_cutoff, exp_tab);
+    if (kept > first) all_done = composite_staged<DEPTH>(s, st.xy + first, st.co + first, st.rgb + first, st.raw + first, DEPTH ? dep + first : nullptr,
+                                                         kept - first, f.t_cutoff, exp_tab);
     return all_done;
 }
 
@@ -388,7 +424,7 @@ struct DeepSegment {               // the survivors of a wave's 64 list entries,
     float4 head[kWave];            // centre x, y | the filter's floor in units of log2 (-inf: none) | its 1-based list position (bits)
     float4 filt[kWave];            // the filter's conic (pre-scaled as StagedRecords::co; zeros: the record goes unfiltered), w unused
     float4 raw[kWave];             // conic + opacity as fetched
-    float4 rgb[kWave];             // colour (w unused)
+    float4 rgb[kWave];             // colour | d_i of the depth channel (DEPTH; else 0)
     uint32_t touch[kWave];         // strips the record can reach at all (bit k: strip k)
 };
 // Which strips a record can reach: strip k is out of reach when even the power's maximum over dx, -0.5 dy^2 det / A, stays
@@ -412,7 +448,7 @@ __device__ __forceinline__ uint32_t strips_in_reach(const float2 xy, const float
     return bits;
 }
 // (the footprint test, the floor and the margins are stage_batch's)
-template <int STRIPS>
+template <int STRIPS, bool DEPTH>
 __device__ __forceinline__ uint32_t stage_batch_deep(const TileFeed& f, DeepSegment& seg, const RecordBatch& b, int height) {
     const bool present = b.present();
     const uint32_t rank = b.rank(), pos = b.pos;
@@ -432,7 +468,7 @@ __device__ __forceinline__ uint32_t stage_batch_deep(const TileFeed& f, DeepSegm
         seg.raw[slot] = b.co;
         float c0 = c[0], c1 = c[1], c2 = c[2];
         if (f.dc_stride != 0u) { c0 = 0.5f + 0.4f * c0; c1 = 0.5f + 0.4f * c1; c2 = 0.5f + 0.4f * c2; }
-        seg.rgb[slot] = make_float4(c0, c1, c2, 0.0f);
+        seg.rgb[slot] = make_float4(c0, c1, c2, DEPTH ? depth_value(f, b.id) : 0.0f);
         seg.touch[slot] = strips_in_reach<STRIPS>(b.xy, b.co, p0, terms, filtered, f.box.y_lo, height);
     }
     return (uint32_t)__popcll(m2);
@@ -443,6 +479,7 @@ struct StripLanes {                // one pixel per lane: lane l owns (x = l & 1
     float fx, fy;                  // (fy: NaN once the pixel is finished, as TileLanes' row coordinates)
     bool inside;
     float T, cr, cg, cb;
+    float cd;                      // depth channel (the DEPTH instantiations; dead in the others)
     uint32_t last;
 };
 __device__ __forceinline__ void strip_lanes_init(StripLanes& s, int tx, int ty, int strip, int lane, int width, int height, int rows = 4) {
@@ -451,7 +488,7 @@ __device__ __forceinline__ void strip_lanes_init(StripLanes& s, int tx, int ty, 
     s.fx = (float)s.px;
     s.inside = s.px < width && s.py < height && (lane >> 4) < rows;
     s.fy = s.inside ? (float)s.py : __builtin_nanf("");
-    s.T = 1.0f; s.cr = s.cg = s.cb = 0.0f; s.last = 0u;
+    s.T = 1.0f; s.cr = s.cg = s.cb = s.cd = 0.0f; s.last = 0u;
 }
 __device__ __forceinline__ bool strip_lanes_all_done(const StripLanes& s) { return __ballot(s.fy == s.fy) == 0ull; }
 // composite_record for one strip, over the slots of `slots` (a lane mask over the segment's slots) in order: the same filter,
@@ -460,6 +497,7 @@ __device__ __forceinline__ bool strip_lanes_all_done(const StripLanes& s) { retu
 // SIMDs, and with eight of these waves on every SIMD the loop's scalar instructions (45 % of all it issues) are what it
 // waits for: no call in it, one way through per record. *done_at: the list position of the record the strip's last
 // pixel finished on.
+template <bool DEPTH>
 __device__ __forceinline__ bool composite_strip(StripLanes& s, const DeepSegment& seg, unsigned long long slots, float t_cutoff,
                                                 const unsigned long long* exp_tab, uint32_t* done_at) {
     constexpr float kAlphaMin = 1.0f / 255.0f;
@@ -489,6 +527,7 @@ __device__ __forceinline__ bool composite_strip(StripLanes& s, const DeepSegment
                 s.cr = __builtin_fmaf(col.x, w, s.cr);
                 s.cg = __builtin_fmaf(col.y, w, s.cg);
                 s.cb = __builtin_fmaf(col.z, w, s.cb);
+                if constexpr (DEPTH) s.cd = __builtin_fmaf(col.w, w, s.cd);
                 s.T = test;
                 s.last = __float_as_uint(hd.w);
             }
@@ -501,8 +540,10 @@ __device__ __forceinline__ bool composite_strip(StripLanes& s, const DeepSegment
     }
     return finished;
 }
+template <bool DEPTH>
 __device__ __forceinline__ void strip_lanes_write(const StripLanes& s, int width, int height, const float* __restrict__ background,
-                                                  float* __restrict__ final_t, uint32_t* __restrict__ n_contrib, float* __restrict__ out_color) {
+                                                  float* __restrict__ final_t, uint32_t* __restrict__ n_contrib, float* __restrict__ out_color,
+                                                  float* __restrict__ out_depth) {
     if (!s.inside) return;
     const size_t plane = (size_t)width * (size_t)height;
     const size_t pid = (size_t)s.py * (size_t)width + (size_t)s.px;
@@ -511,11 +552,13 @@ __device__ __forceinline__ void strip_lanes_write(const StripLanes& s, int width
     out_color[pid] = s.cr + s.T * background[0];
     out_color[pid + plane] = s.cg + s.T * background[1];
     out_color[pid + 2 * plane] = s.cb + s.T * background[2];
+    if constexpr (DEPTH) out_depth[pid] = s.cd;          // (no background term)
 }
 
+template <bool DEPTH>
 __device__ __forceinline__ void tile_lanes_write(const TileLanes& s, int width, int height, const float* __restrict__ background,
                                                  float* __restrict__ final_t, uint32_t* __restrict__ n_contrib,
-                                                 float* __restrict__ out_color) {
+                                                 float* __restrict__ out_color, float* __restrict__ out_depth) {
     const size_t plane = (size_t)width * (size_t)height;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -526,6 +569,7 @@ __device__ __forceinline__ void tile_lanes_write(const TileLanes& s, int width, 
             out_color[pid] = s.cr[k] + s.T[k] * background[0];
             out_color[pid + plane] = s.cg[k] + s.T[k] * background[1];
             out_color[pid + 2 * plane] = s.cb[k] + s.T[k] * background[2];
+            if constexpr (DEPTH) out_depth[pid] = s.cd[k];     // (no background term)
         }
     }
 }

@@ -716,10 +716,14 @@ struct BlockBlendParams {
     int waves_per_tile;          // 1, or 4 (one 16 x 4 strip per wave) when the call has few tiles
     TileOrder history;           // longest tiles first (blend_core.hpp)
     uint32_t dc_stride;          // 0, or 48: `colors` is the SH array (TileFeed::dc_stride)
+    DepthTarget depth;           // the depth channel (read by the DEPTH kernel only)
 };
 
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(5))) void blend_blocks_kernel(const BlockBlendParams p) {
-    __shared__ StagedRecords s_staged;
+// DEPTH: the depth channel too (blend_core.hpp); its four more accumulators do not fit five waves' 96 registers without
+// spilling: four waves per SIMD for that instantiation.
+template <bool DEPTH>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(DEPTH ? 4 : 5))) void blend_blocks_kernel(const BlockBlendParams p) {
+    __shared__ Staged<DEPTH> s_staged;
     exp_table_init(s_staged.exp_tab, (int)threadIdx.x);      // (wave-private LDS: ordered inside the wave)
     const uint32_t clock_begin = tile_clock();
     const int wpt = p.waves_per_tile;
@@ -745,6 +749,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(5))) void
     feed.dc_stride = p.dc_stride;
     feed.box = tile_box(tx, ty, p.dims.width, p.dims.height);
     feed.total = total; feed.t_cutoff = p.t_cutoff;
+    if constexpr (DEPTH) feed_depth(feed, p.depth);
     // The tile's batches, in list order: batch w of unit u, for every (u, w) whose mask is not empty. An iterator walks
     // them; ids are fetched two batches ahead and records one batch ahead of the batch being composited.
     uint32_t it_u = u0, it_nz = 0, it_pos = 0;          // unit, its batches still to come (bit w), list positions handed out
@@ -787,11 +792,11 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(5))) void
     while (b0.valid && !all_done) {
         fetch_records(b1, feed);
         RecordBatch b2 = next_batch();
-        all_done = stage_and_composite(s, feed, s_staged, b0, staged);
+        all_done = stage_and_composite<DEPTH>(s, feed, s_staged, b0, staged);
         b0 = b1;
         b1 = b2;
     }
-    tile_lanes_write(s, p.dims.width, p.dims.height, p.background, p.final_t, p.n_contrib, p.out_color);
+    tile_lanes_write<DEPTH>(s, p.dims.width, p.dims.height, p.background, p.final_t, p.n_contrib, p.out_color, p.depth.out);
     if (p.staged_counter && lane == 0) atomicAdd(p.staged_counter, staged);
     // how far into the block's list this tile looked (gsr_backward after GSR_FLAG_NO_SORTED_LISTS keeps per-entry sums
     // for that part of the list only)
@@ -963,9 +968,10 @@ int launch_blend_blocks(int n, const FrameDims& d, uint32_t r_total, char* geo_s
                         const uint32_t* ranges, const float* means2D, const float* colors, const float* conic_opacity,
                         float* final_t, uint32_t* n_contrib, const float* background, float* out_color,
                         unsigned long long* staged_counter, float t_cutoff, hipStream_t stream,
-                        const uint32_t* tile_order, uint32_t* tile_ticks, bool colors_are_shs) {
+                        const uint32_t* tile_order, uint32_t* tile_ticks, bool colors_are_shs, const DepthTarget& depth) {
     const PlanTables t = plan_tables(n, d.grid_x, d.grid_y, r_total, geo_scratch, bin_scratch);
     BlockBlendParams p;
+    p.depth = depth;
     p.dc_stride = colors_are_shs ? 48u : 0u;
     p.history.order = tile_order; p.history.ticks = tile_ticks;
     p.meta = t.meta;
@@ -989,7 +995,11 @@ int launch_blend_blocks(int n, const FrameDims& d, uint32_t r_total, char* geo_s
     // tile: four waves per tile then, one 16 x 4 strip each. (Not when the staged records are counted:
     // that count is per tile, the reference's "whole tile done" test.)
     p.waves_per_tile = (p.num_tiles <= 1536 && !staged_counter) ? 4 : 1;     // (measured: 960 tiles 0.17 -> 0.13 ms, 4080 tiles 0.16 -> 0.29 ms)
-    hipLaunchKernelGGL(blend_blocks_kernel, dim3((unsigned)(patch_workgroups(d.grid_x, d.row_end - d.row_begin) * p.waves_per_tile)),
+    if (depth.out)
+        hipLaunchKernelGGL(blend_blocks_kernel<true>, dim3((unsigned)(patch_workgroups(d.grid_x, d.row_end - d.row_begin) * p.waves_per_tile)),
+                           dim3(kWave), 0, stream, p);
+    else
+    hipLaunchKernelGGL(blend_blocks_kernel<false>, dim3((unsigned)(patch_workgroups(d.grid_x, d.row_end - d.row_begin) * p.waves_per_tile)),
                        dim3(kWave), 0, stream, p);
     GSR_LAUNCH_CHECK("blend_blocks_kernel");
     return GSR_OK;

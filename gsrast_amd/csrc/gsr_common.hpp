@@ -64,6 +64,14 @@ struct FrameDims {
     int row_begin, row_end;        // tile rows this call bins / sorts / blends
 };
 
+// Where the depth channel of a blend comes from and goes to (gsr_forward_args.out_depth; out == null: no depth channel).
+struct DepthTarget {
+    float* out = nullptr;
+    const float* means3D = nullptr;      // vec4[N]
+    const float* view = nullptr;         // the view matrix (row 2 is read)
+    uint32_t inverse = 0;                // GSR_FLAG_DEPTH_INVERSE
+};
+
 // ---- stage launchers (each asynchronous on `stream`) ----
 int launch_preprocess(const gsr_forward_args& a, const gsr_geometry_state& g, int32_t* radii,
                       uint32_t* depth_keys, uint32_t* rect_packed, const FrameDims& d, hipStream_t stream,
@@ -162,7 +170,8 @@ int launch_blend_blocks(int n, const FrameDims& d, uint32_t r_total, char* geo_s
                         const uint32_t* ranges, const float* means2D, const float* colors, const float* conic_opacity,
                         float* final_t, uint32_t* n_contrib, const float* background, float* out_color,
                         unsigned long long* staged_counter, float t_cutoff, hipStream_t stream,
-                        const uint32_t* tile_order = nullptr, uint32_t* tile_ticks = nullptr, bool colors_are_shs = false);
+                        const uint32_t* tile_order = nullptr, uint32_t* tile_ticks = nullptr, bool colors_are_shs = false,
+                        const DepthTarget& depth = DepthTarget{});
 
 // nonempty (may be null): device word, zero before the launch; receives the number of tiles that got a list
 int launch_tile_ranges(const uint64_t* keys, size_t n, uint32_t* ranges, int num_tiles, bool close_single, hipStream_t stream,
@@ -177,7 +186,8 @@ int launch_blend(const FrameDims& d, const uint32_t* ranges, const uint32_t* poi
                  bool colors_are_shs = false,                                                // (`colors` = the SH array: TileFeed::dc_stride)
                  const uint32_t* deep_count = nullptr,                                       // (device word: the order's leading entries that get four waves, blend.hip)
                  bool deep_all = false,                                                      // (every tile gets four waves)
-                 int deep_waves = 4);                                                        // (... or 8 or 16: frames whose work sits in few tiles)
+                 int deep_waves = 4,                                                         // (... or 8 or 16: frames whose work sits in few tiles)
+                 const DepthTarget& depth = DepthTarget{});                                  // (out_depth: the depth channel too, blend_core.hpp)
 // Longest tiles first: the order of this call's blend workgroups from the ticks the tiles of the call before left.
 constexpr int kTileOrderMax = 32768;      // workgroups (one per tile, patch grid padded) up to which the order is kept: 128 KB of LDS for its sort
 int current_device_shape(DeviceShape* out);                // the current device's, cached per device (api.hip)

@@ -75,6 +75,8 @@ class SplatRasterizer:
         self.image = ChunkBuffer(self.device)
         self.background = _dev(np.asarray(background, np.float32), self.device)
         self.out_color = torch.zeros((3, self.height, self.width), dtype=torch.float32, device=self.device)
+        self.out_depth: torch.Tensor | None = None     # (H, W), allocated by the first draw(depth=...)
+        self.last_depth: "bool | str" = False          # the depth mode of the last draw(): False, True or "inverse"
         self.num_gaussians = 0
         self.use_rects = True
         self.last_num_rendered = 0
@@ -137,8 +139,9 @@ class SplatRasterizer:
     def draw(self, cam: Camera | None = None, *, profile: bool = False, count_staged: bool = False,
              tile_rows: tuple[int, int] | None = None, scale_modifier: float = 1.0,
              sync: bool = True, semantics: str = "gscuda", sh_degree: int = 3, plan: str = "auto",
-             overlap_emit: "bool | None" = None, sorted_lists: bool = True, colors_precomp: bool = False,
-             tile_history: "bool | str" = True, deep_tiles: "bool | str | None" = None) -> torch.Tensor:
+             overlap_emit: "bool | None" = None, sorted_lists: bool = True, colors_precomp: "bool | torch.Tensor" = False,
+             tile_history: "bool | str" = True, deep_tiles: "bool | str | None" = None,
+             depth: "bool | str" = False) -> torch.Tensor:
         """One `forward` call on the current torch stream. Returns the planar (3,H,W) image
         tensor owned by this object. `sync` adds the device synchronise the reference's caller
         performs after every call (CudaBuffer.hpp:8-12). semantics="inria" selects the upstream
@@ -157,7 +160,11 @@ class SplatRasterizer:
         waves per tile (GSR_FLAG_DEEP_WAVES_8 / _16).
         colors_precomp: pass the scene's colours as the reference's `colorsPrecomp` argument (GSCuda.cuh:111) — computed once
         per scene by gsr_colors_from_dc, bit-equal to what the preprocess writes to geomState.rgb per frame (gscuda semantics
-        only: there the colour does not depend on the view)."""
+        only: there the colour does not depend on the view). A device tensor [N, 3] instead is passed as it is (any colours,
+        either semantics); backward() then reads the same tensor.
+        depth: True = also the depth channel (gsr_forward_args.out_depth: sum of z_i alpha_i T_i per pixel, view-space z, no
+        background, not normalised — see opacity_map()), "inverse" = of 1 / z_i (GSR_FLAG_DEPTH_INVERSE); written to
+        self.out_depth, an (H, W) tensor owned by this object."""
         if cam is not None:
             self.set_camera(cam)
         a = _capi.ForwardArgs()
@@ -171,14 +178,22 @@ class SplatRasterizer:
                    | (0 if sorted_lists else _capi.GSR_FLAG_NO_SORTED_LISTS)
                    | (0 if tile_history else _capi.GSR_FLAG_NO_TILE_HISTORY)
                    | {"all": _capi.GSR_FLAG_DEEP_TILES_ALL, "all8": _capi.GSR_FLAG_DEEP_WAVES_8, "all16": _capi.GSR_FLAG_DEEP_WAVES_16,
-                      False: _capi.GSR_FLAG_NO_DEEP_TILES, None: 0}[deep_tiles])
+                      False: _capi.GSR_FLAG_NO_DEEP_TILES, None: 0}[deep_tiles]
+                   | (_capi.GSR_FLAG_DEPTH_INVERSE if depth == "inverse" else 0))
+        assert depth in (False, True, "inverse"), depth
         a.geometry_alloc, a.binning_alloc, a.image_alloc = self.geom.callback, self.binning.callback, self.image.callback
         a.num_gaussians, a.sh_dims, a.M = self.num_gaussians, (sh_degree if inria else 3), 16
         a.background = self.background.data_ptr()
         a.width, a.height = self.width, self.height
         a.means3D, a.shs = self.means3D.data_ptr(), self.shs.data_ptr()
-        a.colors_precomp = self.precomputed_colors().data_ptr() if colors_precomp else None
-        assert not (colors_precomp and inria), "upstream colour depends on the view direction"
+        if isinstance(colors_precomp, torch.Tensor):
+            assert colors_precomp.shape == (self.num_gaussians, 3) and colors_precomp.dtype == torch.float32
+            assert colors_precomp.device == self.device and colors_precomp.is_contiguous()
+            colors_used = colors_precomp
+        else:
+            assert not (colors_precomp and inria), "upstream colour depends on the view direction"
+            colors_used = self.precomputed_colors() if colors_precomp else None
+        a.colors_precomp = colors_used.data_ptr() if colors_used is not None else None
         a.opacities, a.scales = self.opacities.data_ptr(), self.scales.data_ptr()
         a.scale_modifier = scale_modifier
         a.rotations = self.rotations.data_ptr()
@@ -192,15 +207,20 @@ class SplatRasterizer:
         a.box_min = a.box_max = None
         a.stream = torch.cuda.current_stream(self.device).cuda_stream
         a.tile_history = self._history if tile_history is True else None
+        if depth:
+            if self.out_depth is None:
+                self.out_depth = torch.zeros((self.height, self.width), dtype=torch.float32, device=self.device)
+            a.out_depth = self.out_depth.data_ptr()
         if tile_rows is not None:
             a.tile_row_begin, a.tile_row_end = int(tile_rows[0]), int(tile_rows[1])
         with torch.cuda.device(self.device):
             rc = self.lib.gsr_forward(C.byref(a))
         _capi.check(rc, "gsr_forward")
         self.last_receipt = a.receipt.copy()
-        self.last_colors_precomp = bool(colors_precomp)
+        self.last_colors_precomp = colors_used is not None
+        self.last_depth = depth
         # which colours THIS call composited (backward() reads the same ones): tied to the call's receipt, not to "the last call"
-        self._colors_of_call = (int(a.receipt.serial), self._colors_dc if colors_precomp else None)
+        self._colors_of_call = (int(a.receipt.serial), colors_used)
         self.last_num_rendered = int(a.num_rendered)
         self.last_records_staged = int(a.records_staged)
         self.last_plan = _capi.PLAN_NAMES[int(a.plan_used) & 0xFF]
@@ -217,6 +237,10 @@ class SplatRasterizer:
             torch.cuda.current_stream(self.device).synchronize()
             self.poll_async_error()
         return self.out_color
+
+    def opacity_map(self) -> torch.Tensor:
+        """(H, W) accumulated opacity of the last draw(), 1 - finalT: divide out_depth by it for expected depth."""
+        return 1.0 - self.map_image_state()["finalT"]
 
     def tile_history_stats(self) -> dict:
         """gsr_tile_history_stats of this object's history (host side; what the last sort of the blend's tile order found)."""
@@ -290,7 +314,8 @@ class SplatRasterizer:
     def backward(self, dL_dout: torch.Tensor, *, profile: bool = False, with_cov3D: bool = True,
                  tile_rows: tuple[int, int] | None = None, scale_modifier: float = 1.0, semantics: str = "gscuda",
                  sh_degree: int = 3, receipt: "_capi.ForwardReceipt | None | bool" = None, wide_sums: bool = True,
-                 outputs: "tuple[str, ...] | None" = None) -> dict:
+                 outputs: "tuple[str, ...] | None" = None, dL_ddepth: "torch.Tensor | None" = None,
+                 depth: "bool | str | None" = None) -> dict:
         """Gradients of sum(dL_dout * out_color) of the LAST draw() through gsr_backward; `semantics` / `sh_degree`
         must be those of that draw(). receipt: the gsr_forward_receipt of the draw() this is the backward of (default:
         this object's last draw(); any host thread may call); False = none, the reference's contract only (sorted lists
@@ -302,7 +327,11 @@ class SplatRasterizer:
         it —, zero between calls and dropped if a call fails) — the gradients of screen-filling splats then no longer depend on the order in which the
         tiles' atomics arrive. outputs (needs wide_sums): the names to compute, e.g. BASELINE config 5's ("dL_dmean2D",
         "dL_dcov3D", "dL_dshs"); the others are neither computed nor written (the chain is bound by its writes) and
-        absent from the result. The tensors are owned by this object and overwritten by the next call."""
+        absent from the result. The tensors are owned by this object and overwritten by the next call.
+        dL_ddepth: (H, W) gradient w.r.t. the depth channel (gsr_backward_args.dL_dout_depth); the result then also holds
+        dL_ddepths [N] (w.r.t. each Gaussian's d_i) and dL_dmeans3D includes the term through z. depth: the channel's mode,
+        True or "inverse" (default: that of the last draw(depth=...), else True) — the backward recomputes d_i, so any
+        draw() serves, whether or not it wrote out_depth."""
         assert semantics in ("gscuda", "inria")
         n, dev = self.num_gaussians, self.device
         g = dL_dout.to(device=dev, dtype=torch.float32).contiguous()
@@ -348,9 +377,26 @@ class SplatRasterizer:
         a.means3D, a.view_matrix = self.means3D.data_ptr(), self._view.data_ptr()
         a.tan_fovx, a.tan_fovy = self._tan
         a.dL_dout_color = g.data_ptr()
+        if dL_ddepth is not None:
+            gd = dL_ddepth.to(device=dev, dtype=torch.float32).contiguous()
+            assert gd.shape == (self.height, self.width)
+            mode = depth if depth is not None else (self.last_depth or True)
+            assert mode in (True, "inverse"), mode
+            if mode == "inverse":
+                a.flags |= _capi.GSR_FLAG_DEPTH_INVERSE
+            a.dL_dout_depth = gd.data_ptr()
+            if cache.get("dL_ddepths") is None or cache["dL_ddepths"].shape[0] != n:
+                cache["dL_ddepths"] = torch.empty((n,), dtype=torch.float32, device=dev)
+            a.dL_ddepths = cache["dL_ddepths"].data_ptr()
+            if wide_sums:
+                if getattr(self, "_depth_sums_f64", None) is None or self._depth_sums_f64.shape[0] != n:
+                    self._depth_sums_f64 = torch.zeros((n,), dtype=torch.float64, device=dev)     # (the library leaves it zero)
+                a.depth_sums_f64 = self._depth_sums_f64.data_ptr()
         if outputs is not None:
             assert wide_sums and set(outputs) <= set(cache), (outputs, sorted(cache))
             out = {k: cache[k] for k in outputs}
+            if dL_ddepth is not None:
+                out["dL_ddepths"] = cache["dL_ddepths"]
         ptr = lambda k: out[k].data_ptr() if k in out else None
         a.dL_dmean2D, a.dL_dconic_opacity = ptr("dL_dmean2D"), ptr("dL_dconic_opacity")
         a.dL_dcolors = ptr("dL_dcolors")
@@ -374,10 +420,13 @@ class SplatRasterizer:
         with torch.cuda.device(dev):
             rc = self.lib.gsr_backward(C.byref(a))
         if rc != _capi.GSR_OK and wide_sums:
+            self._depth_sums_f64 = None
             self._sums_f64 = None           # (a call that failed half way may have left sums behind: the next call starts from a zeroed scratch again)
         _capi.check(rc, "gsr_backward")
         self.last_backward_ms = (float(a.stage_ms[0]), float(a.stage_ms[1])) if profile else ()
         torch.cuda.current_stream(dev).synchronize()
+        if dL_ddepth is None and "dL_ddepths" in out:
+            return {k: v for k, v in out.items() if k != "dL_ddepths"}
         return out
 
     # -- state inspection (what the reference's Inspector does through fromChunk) ------

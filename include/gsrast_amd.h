@@ -192,6 +192,9 @@ enum {
  * like GSR_FLAG_DEEP_TILES_ALL, which they imply; same outputs bit for bit. */
 #define GSR_FLAG_DEEP_WAVES_8 0x800u
 #define GSR_FLAG_DEEP_WAVES_16 0x1000u
+/* Depth channel (gsr_forward_args.out_depth, gsr_backward_args.dL_dout_depth): the channel holds inverse depth 1 / z_i
+ * instead of z_i. Honoured by gsr_forward and gsr_backward (give both calls the same choice). */
+#define GSR_FLAG_DEPTH_INVERSE 0x2000u
 enum { GSR_PLAN_SORT = 1, GSR_PLAN_BLOCKS = 2, GSR_PLAN_GENERIC = 3 /* grids wider than 255 tiles */,
        GSR_PLAN_LISTS_SKIPPED = 0x100 /* or-ed in: GSR_FLAG_NO_SORTED_LISTS took effect */,
        GSR_PLAN_BLEND_FROM_LISTS = 0x200 /* or-ed in: block plan whose blend read the sorted lists (sparse frames: fewer
@@ -321,13 +324,26 @@ typedef struct gsr_forward_args {
     float stage_ms[GSR_NUM_STAGES];/* only with GSR_FLAG_PROFILE                           */
     uint32_t plan_used;            /* GSR_PLAN_* of this call (0 if R == 0), | GSR_PLAN_LISTS_SKIPPED */
     gsr_forward_receipt receipt;   /* hand it to gsr_backward / gsr_poll_async_error (magic = 0 unless GSR_OK is returned) */
+    /* ---- depth channel (appended: callers that set struct_size = sizeof recompile unchanged) ---- */
+    float* out_depth;              /* device f32[W H], or NULL: no depth channel, exactly the call without it. Definition:
+                                      per Gaussian, z_i is the view-space depth computed in float in this operation order
+                                      (no contraction): z = (V[2]*x + V[6]*y) + (V[10]*z3 + V[14]*1.0f), V = view_matrix,
+                                      (x, y, z3) = means3D[i] — positive in front of the camera in both semantics; it is NOT
+                                      geomState.depths (NDC z under the gscuda semantics). d_i = z_i, or with
+                                      GSR_FLAG_DEPTH_INVERSE d_i = 1.0f / z_i (IEEE division). Per pixel
+                                      out_depth[p] = sum d_i alpha_i T_i, accumulated as fmaf(d_i, alpha_i T_i, acc) in the order
+                                      and under the tests of the colour channels: no background term, no normalisation (the
+                                      accumulated opacity is 1 - accum_alpha: divide by it for expected depth). out_depth equals,
+                                      bit for bit, channel 0 of out_color of a call with colors_precomp[i] = (d_i, d_i, d_i) and
+                                      a zero background. Every pixel of the processed tile rows is written on every GSR_OK call
+                                      (zeros when R == 0, unlike out_color); pixels outside tile_row_begin / _end are not touched. */
 } gsr_forward_args;
 
 /* The forward pass. Calls geometry_alloc(required_geometry(N)), then
  * image_alloc(required_image(W*H)+128), then — only if R>0, after the scan —
  * binning_alloc(required_binning(R)+128): once each, in that order (GSCuda.cu:723-784).
  * Synchronises `stream` once mid-call to read R back (GSCuda.cu:772). Returns GSR_*.
- * R == 0 returns GSR_OK and leaves out_color untouched (GSCuda.cu:775-778). */
+ * R == 0 returns GSR_OK and leaves out_color untouched (GSCuda.cu:775-778); out_depth, if given, is zeroed. */
 int gsr_forward(gsr_forward_args* args);
 
 /* Sticky last error of the calling thread's most recent gsr_* call + its text. */
@@ -465,6 +481,17 @@ typedef struct gsr_backward_args {
                                       reads point_list[0] back (one stream sync) and refuses GSR_LISTS_SKIPPED_STAMP with
                                       GSR_ERR_INVALID_ARG. A receipt that does not fit the other arguments (sizes, rows,
                                       point_list): GSR_ERR_INVALID_ARG. */
+    /* ---- depth channel (appended; see gsr_forward_args.out_depth and GSR_FLAG_DEPTH_INVERSE, which flags must repeat) ----
+     * L gains sum_p dL_dout_depth[p] out_depth[p]. d_i is recomputed from means3D and view_matrix (both then required), so
+     * the receipt of any forward call serves, whether or not it wrote out_depth. Every other output receives the depth
+     * channel's share: the colour backward plus that of colours (d_i, 0, 0) against (dL_dout_depth, 0, 0), no background;
+     * dL_dmeans3D also gets dL_ddepths[i] (V[2], V[6], V[10]), times -1 / z_i^2 with GSR_FLAG_DEPTH_INVERSE. */
+    const float* dL_dout_depth;    /* device f32[W H], or NULL: no depth channel */
+    float* dL_ddepths;             /* f32[N]: dL/dd_i = sum alpha T dL_dout_depth. Required with dL_dout_depth unless sums_f64 is
+                                      given (then optional) */
+    double* depth_sums_f64;        /* f64[N] scratch, ZERO on entry, left zero on return: the dL_ddepths sums in double. Required
+                                      when sums_f64 is given and dL_dout_depth is not NULL (a separate array: the f64[12 N]
+                                      layout of sums_f64 stays as it is) */
 } gsr_backward_args;
 int gsr_backward(gsr_backward_args* args);
 
