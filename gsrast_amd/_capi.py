@@ -137,6 +137,20 @@ class BackwardArgs(C.Structure):
     ]
 
 
+class CameraBackwardArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flags", C.c_uint32),
+        ("num_gaussians", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+        ("means3D", C.c_void_p), ("view_matrix", C.c_void_p), ("proj_matrix", C.c_void_p), ("cam_pos", C.c_void_p),
+        ("tan_fovx", C.c_float), ("tan_fovy", C.c_float),
+        ("cov3D", C.c_void_p), ("radii", C.c_void_p),
+        ("shs", C.c_void_p), ("clamped", C.c_void_p), ("sh_dims", C.c_int32),
+        ("dL_dmean2D", C.c_void_p), ("dL_dcov2D", C.c_void_p), ("dL_ddepths", C.c_void_p), ("dL_dcolors", C.c_void_p),
+        ("dL_dview_matrix", C.c_void_p), ("dL_dproj_matrix", C.c_void_p), ("dL_dcam_pos", C.c_void_p),
+        ("scratch", C.c_void_p), ("stream", C.c_void_p), ("stage_ms", C.c_float),
+    ]
+
+
 # name -> (restype, argtypes); this is also the list the symbol test checks against the header.
 SIGNATURES = {
     "gsr_geometry_from_chunk": (C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(GeometryState)]),
@@ -147,6 +161,8 @@ SIGNATURES = {
     "gsr_required_binning": (C.c_size_t, [C.c_size_t]),
     "gsr_forward": (C.c_int, [C.POINTER(ForwardArgs)]),
     "gsr_backward": (C.c_int, [C.POINTER(BackwardArgs)]),
+    "gsr_camera_backward_scratch_bytes": (C.c_size_t, [C.c_int32]),
+    "gsr_camera_backward": (C.c_int, [C.POINTER(CameraBackwardArgs)]),
     "gsr_points_image_from_chunk": (C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(PointsImageState)]),
     "gsr_required_points_image": (C.c_size_t, [C.c_int]),
     "gsr_forward_points": (C.c_int, [C.POINTER(ForwardArgs)]),

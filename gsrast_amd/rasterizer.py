@@ -315,7 +315,7 @@ class SplatRasterizer:
                  tile_rows: tuple[int, int] | None = None, scale_modifier: float = 1.0, semantics: str = "gscuda",
                  sh_degree: int = 3, receipt: "_capi.ForwardReceipt | None | bool" = None, wide_sums: bool = True,
                  outputs: "tuple[str, ...] | None" = None, dL_ddepth: "torch.Tensor | None" = None,
-                 depth: "bool | str | None" = None) -> dict:
+                 depth: "bool | str | None" = None, camera: bool = False) -> dict:
         """Gradients of sum(dL_dout * out_color) of the LAST draw() through gsr_backward; `semantics` / `sh_degree`
         must be those of that draw(). receipt: the gsr_forward_receipt of the draw() this is the backward of (default:
         this object's last draw(); any host thread may call); False = none, the reference's contract only (sorted lists
@@ -331,7 +331,11 @@ class SplatRasterizer:
         dL_ddepth: (H, W) gradient w.r.t. the depth channel (gsr_backward_args.dL_dout_depth); the result then also holds
         dL_ddepths [N] (w.r.t. each Gaussian's d_i) and dL_dmeans3D includes the term through z. depth: the channel's mode,
         True or "inverse" (default: that of the last draw(depth=...), else True) — the backward recomputes d_i, so any
-        draw() serves, whether or not it wrote out_depth."""
+        draw() serves, whether or not it wrote out_depth.
+        camera: the result also holds the gradients w.r.t. the camera, dL_dview_matrix (16,), dL_dproj_matrix (16,) and
+        dL_dcam_pos (3,) in the layouts of Camera.view / .proj / .cam_pos (camera_backward(), right behind gsr_backward on the
+        same stream). gsr_backward then also writes what that pass reads — dL_dmean2D, dL_dcov2D, and under inria with SH
+        colours dL_dcolors — whatever `outputs` and `with_cov3D` say; arrays not asked for stay out of the result."""
         assert semantics in ("gscuda", "inria")
         n, dev = self.num_gaussians, self.device
         g = dL_dout.to(device=dev, dtype=torch.float32).contiguous()
@@ -397,7 +401,18 @@ class SplatRasterizer:
             out = {k: cache[k] for k in outputs}
             if dL_ddepth is not None:
                 out["dL_ddepths"] = cache["dL_ddepths"]
-        ptr = lambda k: out[k].data_ptr() if k in out else None
+        # camera=True: the per-Gaussian arrays the camera pass reads are written whether or not the result names them
+        need = {}
+        if camera:
+            sh_colour = semantics == "inria" and col is None        # (colours from SH move with the camera position)
+            for k in ("dL_dmean2D", "dL_dcov2D") + (("dL_dcolors",) if sh_colour else ()):
+                if k not in out:
+                    need[k] = cache.get(k)
+            if "dL_dcov2D" in need and need["dL_dcov2D"] is None:          # (with_cov3D=False: a buffer of its own)
+                if getattr(self, "_camera_cov2D", None) is None or self._camera_cov2D.shape[0] != n:
+                    self._camera_cov2D = torch.empty((n, 4), dtype=torch.float32, device=dev)
+                need["dL_dcov2D"] = self._camera_cov2D
+        ptr = lambda k: out[k].data_ptr() if k in out else (need[k].data_ptr() if k in need else None)
         a.dL_dmean2D, a.dL_dconic_opacity = ptr("dL_dmean2D"), ptr("dL_dconic_opacity")
         a.dL_dcolors = ptr("dL_dcolors")
         a.dL_dcov3D = ptr("dL_dcov3D")
@@ -424,10 +439,81 @@ class SplatRasterizer:
             self._sums_f64 = None           # (a call that failed half way may have left sums behind: the next call starts from a zeroed scratch again)
         _capi.check(rc, "gsr_backward")
         self.last_backward_ms = (float(a.stage_ms[0]), float(a.stage_ms[1])) if profile else ()
+        if camera:
+            grads = {k: out[k] if k in out else need[k] for k in ("dL_dmean2D", "dL_dcov2D") + (("dL_dcolors",) if sh_colour else ())}
+            if dL_ddepth is not None:
+                grads["dL_ddepths"] = cache["dL_ddepths"]
+            inverse = bool(a.flags & _capi.GSR_FLAG_DEPTH_INVERSE)
+            cam_out = self.camera_backward(grads, semantics=semantics, sh_degree=sh_degree, shs_colour=sh_colour,
+                                           depth=("inverse" if inverse else True) if dL_ddepth is not None else None,
+                                           profile=profile, sync=False)
+            torch.cuda.current_stream(dev).synchronize()
+            res = {k: v for k, v in out.items() if dL_ddepth is not None or k != "dL_ddepths"}
+            res.update(cam_out)
+            return res
         torch.cuda.current_stream(dev).synchronize()
         if dL_ddepth is None and "dL_ddepths" in out:
             return {k: v for k, v in out.items() if k != "dL_ddepths"}
         return out
+
+    def camera_backward(self, grads: dict, *, semantics: str = "gscuda", sh_degree: int = 3, depth: "bool | str | None" = None,
+                        shs_colour: "bool | None" = None, receipt: "_capi.ForwardReceipt | None" = None,
+                        profile: bool = False, sync: bool = True) -> dict:
+        """gsr_camera_backward alone, on the current stream: the gradients w.r.t. the camera of the last draw(), from the
+        per-Gaussian gradients its gsr_backward returned — grads["dL_dmean2D"] [N,2], grads["dL_dcov2D"] [N,4], with a depth
+        gradient grads["dL_ddepths"] [N] (depth: the channel's mode, True or "inverse"), and grads["dL_dcolors"] [N,3] when
+        the colours came from SH under semantics="inria" (shs_colour; default: from the draw() whose receipt is given — this
+        object's last draw() without one — as backward() decides it: colours from SH unless that draw took colors_precomp).
+        Returns float32 device tensors dL_dview_matrix (16,), dL_dproj_matrix (16,), dL_dcam_pos (3,) in the layouts of
+        Camera.view / .proj / .cam_pos, owned by this object and overwritten by the next call. The scratch
+        (gsr_camera_backward_scratch_bytes) is kept by this object. backward(camera=True) calls this."""
+        assert semantics in ("gscuda", "inria") and depth in (None, False, True, "inverse"), (semantics, depth)
+        n, dev = self.num_gaussians, self.device
+        inria = semantics == "inria"
+        if shs_colour is None:
+            serial, col = getattr(self, "_colors_of_call", (None, None))
+            rcpt = self.last_receipt if receipt is None else receipt
+            if rcpt is not None and int(rcpt.serial) != serial:
+                col = None                           # a receipt of another call: that call's colours are its geomState.rgb
+            shs_colour = inria and col is None
+        gst = _capi.GeometryState()
+        self.lib.gsr_geometry_from_chunk(self.geom.base(), n, C.byref(gst))
+        nbytes = int(self.lib.gsr_camera_backward_scratch_bytes(n))
+        if getattr(self, "_camera_scratch", None) is None or self._camera_scratch.numel() != nbytes:
+            self._camera_scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        if getattr(self, "_camera_grad", None) is None:
+            self._camera_grad = torch.empty((35,), dtype=torch.float32, device=dev)    # view 16 | proj 16 | cam_pos 3
+
+        def ptr(k):
+            t = grads[k]
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.device == dev and t.shape[0] == n, k
+            return t.data_ptr()
+        a = _capi.CameraBackwardArgs()
+        a.struct_size = C.sizeof(_capi.CameraBackwardArgs)
+        a.flags = ((_capi.GSR_FLAG_PROFILE if profile else 0) | (_capi.GSR_FLAG_SEMANTICS_INRIA if inria else 0)
+                   | (_capi.GSR_FLAG_DEPTH_INVERSE if depth == "inverse" else 0))
+        a.num_gaussians, a.width, a.height = n, self.width, self.height
+        a.means3D, a.view_matrix, a.proj_matrix = self.means3D.data_ptr(), self._view.data_ptr(), self._proj.data_ptr()
+        a.cam_pos = self._cam_pos.data_ptr()
+        a.tan_fovx, a.tan_fovy = self._tan
+        a.cov3D, a.radii = gst.cov3D, gst.internal_radii
+        if shs_colour:
+            a.shs, a.clamped, a.sh_dims = self.shs.data_ptr(), gst.clamped, int(sh_degree)
+            a.dL_dcolors = ptr("dL_dcolors")
+        a.dL_dmean2D, a.dL_dcov2D = ptr("dL_dmean2D"), ptr("dL_dcov2D")
+        if depth:
+            a.dL_ddepths = ptr("dL_ddepths")
+        g = self._camera_grad
+        a.dL_dview_matrix, a.dL_dproj_matrix, a.dL_dcam_pos = g[0:16].data_ptr(), g[16:32].data_ptr(), g[32:35].data_ptr()
+        a.scratch = self._camera_scratch.data_ptr()
+        a.stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            rc = self.lib.gsr_camera_backward(C.byref(a))
+        _capi.check(rc, "gsr_camera_backward")
+        self.last_camera_ms = float(a.stage_ms) if profile else None
+        if sync:
+            torch.cuda.current_stream(dev).synchronize()
+        return {"dL_dview_matrix": g[0:16], "dL_dproj_matrix": g[16:32], "dL_dcam_pos": g[32:35]}
 
     # -- state inspection (what the reference's Inspector does through fromChunk) ------
     def map_geometry_state(self) -> dict:

@@ -495,6 +495,62 @@ typedef struct gsr_backward_args {
 } gsr_backward_args;
 int gsr_backward(gsr_backward_args* args);
 
+/* ---- camera gradients: the backward pass on to the camera (after gsr_backward, on the same stream) ----
+ * The derivatives of the same scalar L that gsr_backward differentiates (the colour term sum dL_dout_color * out_color,
+ * plus sum dL_dout_depth * out_depth when that call had a depth gradient) w.r.t. the 16 + 16 + 3 floats exactly as passed
+ * to gsr_forward: view_matrix and proj_matrix column-major (the view's row 2 negated, as the reference's caller builds it),
+ * cam_pos. Entry (row r, column c) of a matrix is element 4 c + r. Only visible Gaussians (radii[i] > 0) contribute, and the
+ * camera reaches L only through each one's
+ *   pixel centre means2D_i  proj rows 0, 1, 3 (h = proj (x, y, z, mean.w); the upstream profile: (x, y, z, 1))
+ *   cov2D_i = J(t) W Sigma W^T J(t)^T + 0.3 I, t = V (x, y, z, 1), W the upper 3 x 3 of V: view rows 0-2. The clamps of
+ *                           t.x / t.z and t.y / t.z to +-1.3 tan_fov are decided in float32 as gsr_forward decides them; a
+ *                           clamped ratio passes its gradient to t.z only
+ *   depth d_i = t.z (1 / t.z with GSR_FLAG_DEPTH_INVERSE)  view row 2, only when dL_ddepths is given
+ *   upstream colour through dir = (mean - cam_pos) / |mean - cam_pos|  cam_pos, only with shs (a channel clamped at zero
+ *                           passes nothing; the reference's colour and colors_precomp do not depend on the camera)
+ * Entries nothing depends on are written as exact zeros: view row 3, proj row 2 (NDC depth only sorts and culls), cam_pos
+ * under the reference's semantics or without shs. Culling, radii, rectangles, tile membership, depth order and the alpha
+ * clamps are decisions with zero derivative; tan_fovx / tan_fovy are not differentiated.
+ * The call reads gsr_backward's per-Gaussian outputs: dL_dcov2D is required (the covariance gradient is not derived from
+ * dL_dconic_opacity). Per-Gaussian terms are formed in double and summed in double per thread, wave and block in an order
+ * fixed by num_gaussians alone (no atomics), then rounded to float once: two calls on the same arrays give the same bits on
+ * any device. Nothing visible: all outputs are zeros. A tile-row band (gsr_backward with tile_row_begin / _end) gives that
+ * band's share: the result is linear in the per-Gaussian gradients, so the bands' results add up to the whole frame's.
+ * Refused with GSR_ERR_INVALID_ARG before any HIP call: a wrong struct_size, a non-positive size, a missing required
+ * input or scratch, no output at all, shs without dL_dcolors / clamped / cam_pos. */
+size_t gsr_camera_backward_scratch_bytes(int32_t num_gaussians);   /* device scratch the call needs: a function of N only */
+typedef struct gsr_camera_backward_args {
+    uint32_t struct_size;          /* = sizeof(gsr_camera_backward_args) */
+    uint32_t flags;                /* GSR_FLAG_SEMANTICS_INRIA, GSR_FLAG_DEPTH_INVERSE (as the forward / backward calls),
+                                      GSR_FLAG_PROFILE (stage_ms) */
+    int32_t num_gaussians, width, height;
+    /* inputs of the forward call (device) */
+    const float* means3D;          /* vec4[N] */
+    const float* view_matrix;      /* 16 floats */
+    const float* proj_matrix;      /* 16 floats */
+    const float* cam_pos;          /* vec3; needed with shs only */
+    float tan_fovx, tan_fovy;
+    /* state of the forward call */
+    const float* cov3D;            /* f32[6 N]: geometry cov3D, or the cov3D_precomp given */
+    const int32_t* radii;          /* internal_radii or the radii buffer given */
+    const float* shs;              /* upstream profile with SH colour: f32[48 N], [16][3] per Gaussian; NULL: no colour term */
+    const uint8_t* clamped;        /* geometry chunk: bool[3 N] (with shs) */
+    int32_t sh_dims;               /* SH degree the forward call evaluated (0..3) */
+    /* per-Gaussian outputs of gsr_backward */
+    const float* dL_dmean2D;       /* vec2[N], required */
+    const float* dL_dcov2D;        /* vec4[N] (m00, m01, m11, 0), required */
+    const float* dL_ddepths;       /* f32[N], or NULL: no depth channel */
+    const float* dL_dcolors;       /* vec3[N], required with shs */
+    /* outputs (device, each optional, at least one): float32, always written in full */
+    float* dL_dview_matrix;        /* 16 floats, layout of view_matrix */
+    float* dL_dproj_matrix;        /* 16 floats, layout of proj_matrix */
+    float* dL_dcam_pos;            /* 3 floats */
+    void* scratch;                 /* device, gsr_camera_backward_scratch_bytes(num_gaussians) bytes, 8-byte aligned */
+    void* stream;
+    float stage_ms;                /* with GSR_FLAG_PROFILE: the camera pass's device time */
+} gsr_camera_backward_args;
+int gsr_camera_backward(gsr_camera_backward_args* args);
+
 /* ---- point-splat path (gscuda::forwardPoints, GSCuda.cuh:19-42 / GSCuda.cu:26-155; the reference never
  * calls it) ---- Same argument struct as gsr_forward; read: num_gaussians, width, height, background,
  * means3D (a stride of THREE floats here, GSCuda.cu:65), shs, proj_matrix, out_color, geometry_alloc (asked for
