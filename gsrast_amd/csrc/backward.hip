@@ -274,7 +274,7 @@ __global__ __launch_bounds__(64) void render_backward_kernel(const RenderBackwar
             // A pixel can pass alpha >= 1/255 only where power >= -ln(255 opacity) (less a margin for the rounding of the
             // logarithm, the exponential and the product; NaN opacity: the reference's min(0.99, NaN) is 0.99, it counts)
             const float op = co_l.w;
-            s_floor[slot] = op != op ? -__builtin_inff() : (op <= 0.0f ? __builtin_inff() : -__logf(255.0f * op) - 1e-3f);
+            s_floor[slot] = !(op > -__builtin_inff()) ? -__builtin_inff() : (op <= 0.0f ? __builtin_inff() : -__logf(255.0f * op) - 1e-3f);
         }
         // wave-private LDS: the writes above and the reads below are ordered inside the wave
         for (int j = (int)__popcll(kept_mask) - 1; j >= 0; --j) {

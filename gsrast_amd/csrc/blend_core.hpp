@@ -368,9 +368,10 @@ __device__ __forceinline__ uint32_t stage_batch(const TileFeed& f, Staged<DEPTH>
         const float terms = fabsf(b.co.x) * dxm * dxm + fabsf(b.co.z) * dym * dym + 2.0f * fabsf(b.co.y) * dxm * dym;
         // the filter's floor for this record, in units of log2: -ln(255 opacity) less the margins (1e-3 for the rounding of the
         // exponential and the product, and the filter's own rounding). Opacity <= 0: +inf, no
-        // candidate (alpha <= 0 fails the 1/255 test); NaN opacity: -inf (the reference's min(0.99, NaN) is 0.99: it counts).
+        // candidate (alpha <= 0 fails the 1/255 test); NaN opacity: -inf (the reference's min(0.99, NaN) is 0.99: it counts),
+        // and so for an opacity of -inf: where the exponential underflows to 0 the product is NaN, and counts as well.
         const float p0 = -__logf(255.0f * b.co.w);
-        const float floor2 = b.co.w != b.co.w ? -__builtin_inff() : (b.co.w <= 0.0f ? __builtin_inff() : (p0 - 1e-3f - 1e-6f * terms) * kLog2e);
+        const float floor2 = !(b.co.w > -__builtin_inff()) ? -__builtin_inff() : (b.co.w <= 0.0f ? __builtin_inff() : (p0 - 1e-3f - 1e-6f * terms) * kLog2e);
         // The filter's slack covers the rounding of power terms up to 4e6 (kFilterSlack / 6e-8). A record whose terms can be
         // larger somewhere on the tile — a screen-filling needle seen along its axis at 4K: conic entries up to 3.3, |d| in the
         // thousands — gets a zero filter conic and no floor: its filter value is 0 for every unfinished pixel (NaN for the
@@ -460,7 +461,7 @@ __device__ __forceinline__ uint32_t stage_batch_deep(const TileFeed& f, DeepSegm
         const float dxm = fmaxf(fabsf(b.xy.x - f.box.x_lo), fabsf(b.xy.x - f.box.x_hi)), dym = fmaxf(fabsf(b.xy.y - f.box.y_lo), fabsf(b.xy.y - f.box.y_hi));
         const float terms = fabsf(b.co.x) * dxm * dxm + fabsf(b.co.z) * dym * dym + 2.0f * fabsf(b.co.y) * dxm * dym;
         const float p0 = -__logf(255.0f * b.co.w);
-        const float floor2 = b.co.w != b.co.w ? -__builtin_inff() : (b.co.w <= 0.0f ? __builtin_inff() : (p0 - 1e-3f - 1e-6f * terms) * kLog2e);
+        const float floor2 = !(b.co.w > -__builtin_inff()) ? -__builtin_inff() : (b.co.w <= 0.0f ? __builtin_inff() : (p0 - 1e-3f - 1e-6f * terms) * kLog2e);
         const bool filtered = terms < 1.0e6f;                                   // (NaN: not filtered)
         seg.head[slot] = make_float4(b.xy.x, b.xy.y, filtered ? floor2 : -__builtin_inff(), __uint_as_float(pos + rank + 1u));
         seg.filt[slot] = filtered ? make_float4((-0.5f * kLog2e) * b.co.x, -kLog2e * b.co.y, (-0.5f * kLog2e) * b.co.z, 0.0f)

@@ -157,7 +157,10 @@ __global__ __launch_bounds__(256) void preprocess_inria_kernel(const InriaParams
         const M3 cv = mul3(mul3(transpose3(tm), transpose3(vrk)), tm);
         ca = cv.m[0][0] + 0.3f; cb = cv.m[0][1]; cc = cv.m[1][1] + 0.3f;
         const float det = ca * cc - cb * cb;
-        if (det != 0.0f) {
+        // A covariance that overflowed (scales of 1e9 are finite floats) gives a determinant that is Inf or NaN — NaN != 0
+        // holds — and a radius that saturates (every tile of the frame) or converts to 0 (one tile, by the rectangle alone),
+        // with a conic of zeros or NaNs. Such a Gaussian has no tile, like one behind the camera (profiles/inria_parity.txt).
+        if (det != 0.0f && __builtin_isfinite(det)) {
             det_inv = 1.0f / det;
             const float mid = 0.5f * (ca + cc);
             const float root = sqrtf(fmaxr(0.1f, mid * mid - det));
@@ -170,7 +173,10 @@ __global__ __launch_bounds__(256) void preprocess_inria_kernel(const InriaParams
             fy0 = clampi((int)((piy - rf) / 16.0f), 0, p.dims.grid_y);
             x1 = clampi((int)((((pix + rf) + 16.0f) - 1.0f) / 16.0f), 0, p.dims.grid_x);
             fy1 = clampi((int)((((piy + rf) + 16.0f) - 1.0f) / 16.0f), 0, p.dims.grid_y);
-            has_tile = (uint32_t)(x1 - x0) * (uint32_t)(fy1 - fy0) != 0;
+            // (a tile-row band call: a Gaussian without a tile in the band is invisible, gsrast_amd.h)
+            fy0 = clampi(fy0, p.dims.row_begin, p.dims.row_end);
+            fy1 = clampi(fy1, p.dims.row_begin, p.dims.row_end);
+            has_tile = ri > 0 && (uint32_t)(x1 - x0) * (uint32_t)(fy1 - fy0) != 0;
         }
     }
 
@@ -237,14 +243,14 @@ __global__ __launch_bounds__(256) void preprocess_inria_kernel(const InriaParams
     if (!valid) return;
 
     // ---- stores from here on ---- every Gaussian stores every record, zeros where the upstream kernel stores nothing, as
-    // streaming stores: whole lines, no partial writes (preprocess.hip explains; here 0.42 -> 0.33 ms on the bench frame)
+    // streaming stores (a Gaussian without a tile: zeros in every array): whole lines, no partial writes (preprocess.hip explains; here 0.42 -> 0.33 ms on the bench frame)
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     if (!p.cov3D_precomp) {
         f32x2* dst = reinterpret_cast<f32x2*>(p.cov3Ds + 6 * (size_t)idx);
-        __builtin_nontemporal_store((f32x2){in_front ? c3[0] : 0.0f, in_front ? c3[1] : 0.0f}, dst);
-        __builtin_nontemporal_store((f32x2){in_front ? c3[2] : 0.0f, in_front ? c3[3] : 0.0f}, dst + 1);
-        __builtin_nontemporal_store((f32x2){in_front ? c3[4] : 0.0f, in_front ? c3[5] : 0.0f}, dst + 2);
+        __builtin_nontemporal_store((f32x2){has_tile ? c3[0] : 0.0f, has_tile ? c3[1] : 0.0f}, dst);
+        __builtin_nontemporal_store((f32x2){has_tile ? c3[2] : 0.0f, has_tile ? c3[3] : 0.0f}, dst + 1);
+        __builtin_nontemporal_store((f32x2){has_tile ? c3[4] : 0.0f, has_tile ? c3[5] : 0.0f}, dst + 2);
     }
     if (want_sh) {
 #pragma unroll
@@ -260,12 +266,11 @@ __global__ __launch_bounds__(256) void preprocess_inria_kernel(const InriaParams
                                         has_tile ? opacity : 0.0f},
                                 reinterpret_cast<f32x4*>(p.conic_opacity + idx));
     if (has_tile) {
-        const int y0 = clampi(fy0, p.dims.row_begin, p.dims.row_end), y1 = clampi(fy1, p.dims.row_begin, p.dims.row_end);
+        const int y0 = fy0, y1 = fy1;
         out_radius = ri;
         out_tiles = (uint32_t)(x1 - x0) * (uint32_t)(y1 - y0);
         view_z = pvz;
-        if (out_tiles)
-            out_rect = (uint32_t)x0 | ((uint32_t)(x1 - x0) << 8) | ((uint32_t)y0 << 16) | ((uint32_t)(y1 - y0) << 24);
+        out_rect = (uint32_t)x0 | ((uint32_t)(x1 - x0) << 8) | ((uint32_t)y0 << 16) | ((uint32_t)(y1 - y0) << 24);
     }
     p.radii[idx] = out_radius;
     p.tiles_touched[idx] = out_tiles;

@@ -529,6 +529,8 @@ class SplatRasterizer:
             "conicOpacity": v(st.conic_opacity, 4 * n, torch.float32).view(n, 4),
             "rgb": v(st.rgb, 3 * n, torch.float32).view(n, 3),
             "pointOffsets": v(st.point_offsets, n, torch.int32),
+            # bool[3 N]: colour channel clamped at zero (written under semantics="inria" with SH colours only)
+            "clamped": v(st.clamped, 3 * n, torch.uint8).view(torch.bool).view(n, 3),
         }
 
     def map_image_state(self) -> dict:

@@ -111,8 +111,10 @@ enum {
  * of the reference's gscuda variant (SURVEY.md §8a divergence table D1-D12, §8f-2): SH up to degree
  * `sh_dims` on shs laid out [N][16][3], view-space depth keys, cull at view z <= 0.2, half-pixel
  * centre, radius-based square rectangles (`rects` ignored), separate focal lengths, transmittance
- * cut-off 1e-4, R == 1 renders, R == 0 still writes the background. cam_pos is read. Parity of this
- * profile is unpinned (no upstream source in the reference tree). */
+ * cut-off 1e-4, R == 1 renders, R == 0 still writes the background. cam_pos is read. A Gaussian whose
+ * radius converts to 0 or whose 2-D determinant is not finite (an overflowed covariance) has no tile,
+ * like one behind the camera: zeros in every per-Gaussian array. Parity of this profile is unpinned
+ * (no upstream source in the reference tree). */
 #define GSR_FLAG_SEMANTICS_INRIA 0x4u
 /* Binning plan (both produce bit-identical sorted keys / values / ranges; default: chosen per frame: the block plan from 6
  * instances (numRendered) per visible Gaussian up, or when an eighth of the instances belongs to splats of 256 tiles and more —

@@ -34,6 +34,7 @@ def lib(contract: bool = False) -> ctypes.CDLL:
         L.gsro_preprocess.restype = ctypes.c_uint64
         L.gsro_preprocess_mt.restype = ctypes.c_uint64
         L.gsro_blend.restype = ctypes.c_uint64
+        L.gsro_blend_cutoff.restype = ctypes.c_uint64
         L.gsro_higher_msb.restype = ctypes.c_uint32
         L.gsro_hardware_concurrency.restype = ctypes.c_uint
         _libs[contract] = L
@@ -136,3 +137,24 @@ def blend_only(state: dict, cam, background=(0.0, 0.0, 0.0), threads: int = 1):
                               _p(state["means2D"]), _p(state["rgb"]), _p(state["conicOpacity"]), _p(bg),
                               _p(ft), _p(nc), _p(out), ctypes.c_int(threads)))
     return time.perf_counter() - t0, staged
+
+
+def blend_cutoff(state: dict, cam, background=(0.0, 0.0, 0.0), threads: int = 1, t_cutoff: float = 0.001) -> dict:
+    """The tile loop alone (libm's expf) over the lists of `state` (ranges, values, means2D, rgb, conicOpacity) with the
+    transmittance cut-off `t_cutoff`: the checker of the upstream profile's blend (oracle/inria_np.py passes 1e-4 and the
+    ranges its R == 1 / R == 0 rules give). Returns out_color, finalT, nContrib, records_staged."""
+    L = lib()
+    W, H = cam.width, cam.height
+    bg = np.asarray(background, dtype=np.float32)
+    c = lambda k, t: np.ascontiguousarray(state[k], dtype=t)
+    ranges, values = c("ranges", np.uint32), c("values", np.uint32)
+    means2d, rgb, conic = c("means2D", np.float32), c("rgb", np.float32), c("conicOpacity", np.float32)
+    if values.size == 0:
+        values = np.zeros(1, np.uint32)
+    out = np.zeros((3, H, W), np.float32)
+    ft = np.zeros((H, W), np.float32)
+    nc = np.zeros((H, W), np.uint32)
+    staged = int(L.gsro_blend_cutoff(ctypes.c_int(W), ctypes.c_int(H), _p(ranges), _p(values), _p(means2d), _p(rgb),
+                                     _p(conic), _p(bg), _p(ft), _p(nc), _p(out), ctypes.c_int(threads),
+                                     ctypes.c_float(t_cutoff)))
+    return dict(out_color=out, finalT=ft, nContrib=nc, records_staged=staged)

@@ -388,7 +388,7 @@ void gsro_bin_mt(int n, int width, int height, const int* radii, const float* me
 static uint64_t blend_rows(int ty0, int ty1, int width, int height, const uint32_t* ranges,
                            const uint32_t* point_list, const float* means2d, const float* colors,
                            const float* conic_opacity, const float* background, float* final_t,
-                           uint32_t* n_contrib, float* out_color) {
+                           uint32_t* n_contrib, float* out_color, float t_cutoff) {
     const int grid_x = (width + kTile - 1) / kTile;
     const size_t plane = (size_t)width * (size_t)height;
     uint64_t staged = 0;
@@ -434,7 +434,7 @@ static uint64_t blend_rows(int ty0, int ty1, int width, int height, const uint32
                         const float alpha = gmin(0.99f, cc[j][3] * std::exp(power));
                         if (alpha < 1.0f / 255.0f) continue;
                         const float test = acc_t[t] * (1.0f - alpha);
-                        if (test < 0.001f) { done[t] = true; continue; }
+                        if (test < t_cutoff) { done[t] = true; continue; }
                         for (int c = 0; c < 3; ++c) col[t][c] += crgb[j][c] * alpha * acc_t[t];
                         acc_t[t] = test;
                         last[t] = contributor[t];
@@ -454,14 +454,16 @@ static uint64_t blend_rows(int ty0, int ty1, int width, int height, const uint32
 
 // threads <= 1: scalar single-thread loop. threads > 1: std::thread pool pulling tile
 // rows from an atomic counter (the CPU baseline of SURVEY.md §8d). Returns R_f.
-uint64_t gsro_blend(int width, int height, const uint32_t* ranges, const uint32_t* point_list,
-                    const float* means2d, const float* colors, const float* conic_opacity,
-                    const float* background, float* final_t, uint32_t* n_contrib, float* out_color,
-                    int threads) {
+// t_cutoff: the transmittance below which a pixel stops (GSCuda.cu:653 compares with 0.001f; the upstream profile's
+// restatement, oracle/inria_np.py, passes 0.0001f). What a caller does for R == 1 and R == 0 is in the ranges it passes.
+uint64_t gsro_blend_cutoff(int width, int height, const uint32_t* ranges, const uint32_t* point_list,
+                           const float* means2d, const float* colors, const float* conic_opacity,
+                           const float* background, float* final_t, uint32_t* n_contrib, float* out_color,
+                           int threads, float t_cutoff) {
     const int grid_y = (height + kTile - 1) / kTile;
     if (threads <= 1)
         return blend_rows(0, grid_y, width, height, ranges, point_list, means2d, colors, conic_opacity,
-                          background, final_t, n_contrib, out_color);
+                          background, final_t, n_contrib, out_color, t_cutoff);
     std::atomic<int> next{0};
     std::atomic<uint64_t> staged{0};
     std::vector<std::thread> pool;
@@ -472,12 +474,21 @@ uint64_t gsro_blend(int width, int height, const uint32_t* ranges, const uint32_
                 const int ty = next.fetch_add(1);
                 if (ty >= grid_y) break;
                 mine += blend_rows(ty, ty + 1, width, height, ranges, point_list, means2d, colors,
-                                   conic_opacity, background, final_t, n_contrib, out_color);
+                                   conic_opacity, background, final_t, n_contrib, out_color, t_cutoff);
             }
             staged += mine;
         });
     for (auto& th : pool) th.join();
     return staged.load();
+}
+
+// The reference's tile loop: the cut-off of GSCuda.cu:653.
+uint64_t gsro_blend(int width, int height, const uint32_t* ranges, const uint32_t* point_list,
+                    const float* means2d, const float* colors, const float* conic_opacity,
+                    const float* background, float* final_t, uint32_t* n_contrib, float* out_color,
+                    int threads) {
+    return gsro_blend_cutoff(width, height, ranges, point_list, means2d, colors, conic_opacity, background, final_t,
+                             n_contrib, out_color, threads, 0.001f);
 }
 
 unsigned gsro_hardware_concurrency(void) { return std::thread::hardware_concurrency(); }

@@ -3,7 +3,15 @@ diff-gaussian-rasterization), the `inria` profile of SURVEY.md §8(f)-2 / Diverg
 
 TEST INFRASTRUCTURE. The upstream sources are not in this container (empty submodule), so this is
 written from the published algorithm: parity is UNPINNED — it checks that the HIP `inria` path and
-this restatement agree, and a few closed-form facts (SH basis constants, DC colour), nothing more.
+this restatement agree, and what can be pinned without the upstream text: that the sixteen polynomials
+are the real spherical harmonics and that the float32 colour agrees with the float64 one of
+oracle/backward_np.py (tests/test_inria_profile.py).
+
+One rule here is this project's choice, not upstream's: a Gaussian whose radius converts to 0 or whose
+2-D determinant is not finite (an overflowed covariance) has NO TILE, exactly like one behind the
+camera. Upstream counts a tile for it and emits nothing, leaving the counted slot unwritten: there is
+no defined behaviour to match. The count and the emission therefore use one rule: a tile means
+radii > 0, and num_rendered == len(keys) for every input.
 
 Inputs use the reference app's buffers: means3D / scales vec4-strided, rotations (real part first),
 shs [N][16][3] coefficient-major (upstream layout), view / proj 16 floats column-major.
@@ -52,7 +60,11 @@ def sh_to_rgb(deg, pos, campos, shs):
     return np.maximum(res, F(0.0)).astype(F), res < 0
 
 
-def preprocess(scene, cam, deg=3, scale_modifier=1.0):
+def preprocess(scene, cam, deg=3, scale_modifier=1.0, colors_precomp=None, tile_rows=None, focal=None):
+    """The per-Gaussian stage. colors_precomp: [N,3] colours composited as given (no SH, no clamp flags). tile_rows: (begin,
+    end) — the call bins these tile rows only, and a Gaussian without a tile in them is invisible (include/gsrast_amd.h).
+    focal: (focal_x, focal_y) instead of the camera's own; tests pass them swapped to show that the two are told apart."""
+    deg = min(3, max(0, int(deg)))
     with np.errstate(all="ignore"):
         means = scene["means3D"].astype(F)
         n = means.shape[0]
@@ -61,6 +73,8 @@ def preprocess(scene, cam, deg=3, scale_modifier=1.0):
         view, proj = cam.view.astype(F), cam.proj.astype(F)
         tfx, tfy = F(cam.tan_fovx), F(cam.tan_fovy)
         fx, fy = F(W) / (F(2.0) * tfx), F(H) / (F(2.0) * tfy)
+        if focal is not None:
+            fx, fy = F(focal[0]), F(focal[1])
         p = means[:, :3]
         pv = _p4x3(view, p)
         vis = ~(pv[:, 2] <= F(0.2))
@@ -97,7 +111,7 @@ def preprocess(scene, cam, deg=3, scale_modifier=1.0):
         C = _mm3(_mm3(_tr3(T), _tr3(V)), T)
         ca, cb, cc = C[(0, 0)] + F(0.3), C[(0, 1)], C[(1, 1)] + F(0.3)
         det = ca * cc - cb * cb
-        vis &= det != 0
+        vis &= (det != 0) & np.isfinite(det)
         det_inv = F(1.0) / det
         conic = np.stack([cc * det_inv, -cb * det_inv, ca * det_inv], axis=1)
         mid = F(0.5) * (ca + cc)
@@ -112,13 +126,21 @@ def preprocess(scene, cam, deg=3, scale_modifier=1.0):
         y0 = np.clip(_f2i((piy - rf) / F(16)), 0, gy).astype(np.uint32)
         x1 = np.clip(_f2i((((pix + rf) + F(16)) - F(1)) / F(16)), 0, gx).astype(np.uint32)
         y1 = np.clip(_f2i((((piy + rf) + F(16)) - F(1)) / F(16)), 0, gy).astype(np.uint32)
+        if tile_rows is not None:
+            y0 = np.clip(y0, tile_rows[0], tile_rows[1]).astype(np.uint32)
+            y1 = np.clip(y1, tile_rows[0], tile_rows[1]).astype(np.uint32)
         area = (x1 - x0) * (y1 - y0)
-        vis &= area != 0
-        rgb, clamped = sh_to_rgb(deg, p, cam.cam_pos.astype(F), scene["shs"].astype(F))
+        vis &= (area != 0) & (ri > 0)
+        if colors_precomp is None:
+            rgb, clamped = sh_to_rgb(deg, p, cam.cam_pos.astype(F), scene["shs"].astype(F))
+        else:
+            rgb, clamped = np.asarray(colors_precomp, F), np.zeros((n, 3), bool)
         o = {
             "radii": np.where(vis, ri, 0).astype(np.int32),
             "tilesTouched": np.where(vis, area, 0).astype(np.uint32),
             "rgb": np.where(vis[:, None], rgb, F(0)),
+            "clamped": vis[:, None] & clamped,
+            "cov3D": np.where(vis[:, None], cov3d, F(0)),
             "depths": np.where(vis, pv[:, 2], F(0)),
             "means2D": np.where(vis[:, None], np.stack([pix, piy], axis=1), F(0)),
             "conicOpacity": np.where(vis[:, None], np.concatenate([conic, scene["opacities"].astype(F)[:, None]], axis=1), F(0)),
@@ -130,8 +152,13 @@ def preprocess(scene, cam, deg=3, scale_modifier=1.0):
         return o
 
 
-def forward(scene, cam, background=(0.0, 0.0, 0.0), deg=3, scale_modifier=1.0):
-    o = preprocess(scene, cam, deg, scale_modifier)
+def forward(scene, cam, background=(0.0, 0.0, 0.0), deg=3, scale_modifier=1.0, blend_with="numpy", threads=1,
+            colors_precomp=None, tile_rows=None, focal=None):
+    """The whole frame. blend_with: "numpy" (oracle_np.blend, numpy's exp), "numpy-expf" (the same loop with libm's expf) or
+    "cpp" (the C++ oracle's tile loop: libm's expf, `threads` host threads) — all with this profile's cut-off 1e-4; the two
+    with libm's exponential give the HIP blend's finalT and nContrib bit for bit. The upstream rules stay here: R == 1 closes
+    its tile, R == 0 still composites the background."""
+    o = preprocess(scene, cam, deg, scale_modifier, colors_precomp, tile_rows, focal)
     gx, gy = (cam.width + 15) // 16, (cam.height + 15) // 16
     if o["num_rendered"] > 0:
         bin_and_sort(o, cam)
@@ -140,8 +167,19 @@ def forward(scene, cam, background=(0.0, 0.0, 0.0), deg=3, scale_modifier=1.0):
             o["ranges"][t] = (0, 1)
     else:
         o.update(keys=np.zeros(0, np.uint64), values=np.zeros(0, np.uint32), ranges=np.zeros((gx * gy, 2), np.uint32))
+    assert o["num_rendered"] == o["keys"].size
     # upstream runs the tile loop even when nothing was binned: every pixel then gets the background
-    res = blend(dict(o, num_rendered=max(1, o["num_rendered"])), cam, background, t_cutoff=1e-4)
+    if blend_with == "cpp":
+        from . import cpu_oracle
+        res = cpu_oracle.blend_cutoff(o, cam, background, threads=threads, t_cutoff=1e-4)
+    else:
+        kw = {}
+        if blend_with == "numpy-expf":
+            from . import cpu_oracle
+            kw["exp"] = cpu_oracle.expf
+        else:
+            assert blend_with == "numpy", blend_with
+        res = blend(dict(o, num_rendered=max(1, o["num_rendered"])), cam, background, t_cutoff=1e-4, **kw)
     o.update(res)
     o.pop("_rect", None)
     return o

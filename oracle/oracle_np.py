@@ -187,9 +187,11 @@ def bin_and_sort(o, cam):
     return o
 
 
-def blend(o, cam, background=(0.0, 0.0, 0.0), out_init=None, t_cutoff=0.001):
+def blend(o, cam, background=(0.0, 0.0, 0.0), out_init=None, t_cutoff=0.001, exp=np.exp):
     """Row a11 (GSCuda.cu:543-677): per tile, all 256 pixels advance together through
-    the sorted list, one record at a time, with boolean masks for skip/done."""
+    the sorted list, one record at a time, with boolean masks for skip/done.
+    exp: the float32 exponential (default numpy's, with which the committed fixture was minted; cpu_oracle.expf is libm's,
+    the C++ oracle's and the HIP blend's)."""
     W, H = cam.width, cam.height
     gx, gy = (W + 15) // 16, (H + 15) // 16
     bg = np.asarray(background, dtype=F)
@@ -228,7 +230,7 @@ def blend(o, cam, background=(0.0, 0.0, 0.0), out_init=None, t_cutoff=0.001):
                         gxy, con, rgb = o["means2D"][g], o["conicOpacity"][g], o["rgb"][g]
                         dx, dy = gxy[0] - fx, gxy[1] - fy
                         power = F(-0.5) * (con[0] * dx * dx + con[2] * dy * dy) - con[1] * dx * dy
-                        alpha = np.minimum(F(0.99), con[3] * np.exp(power))
+                        alpha = np.minimum(F(0.99), con[3] * exp(power))
                         test = T * (F(1.0) - alpha)
                         live = act & ~(power > 0) & ~(alpha < F(1.0) / F(255.0))
                         stop = live & (test < F(t_cutoff))

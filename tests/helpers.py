@@ -305,3 +305,97 @@ def assert_backward_per_gaussian(got, ref, float_tile_sums=False, what=""):
     print(f"[backward per Gaussian] {what}: {int((~none).sum())} composited ({int(clamped.sum())} clamped everywhere), worst "
           f"|err| / ((k + c{' + tiles' if float_tile_sums else ''}) M) = {worst:.3e} at {worst_at}")
     return worst
+
+
+# ---- the upstream profile (GSR_FLAG_SEMANTICS_INRIA) against its restatement, oracle/inria_np.py ----
+def inria_scene(n, seed, sh_scale=0.3, shrink=0.25):
+    """The garden-like scene drawn smaller, with all sixteen SH coefficient triples N(0, sh_scale): [N][16][3]."""
+    from gsrast_amd import scenes
+    sc = scenes.garden_like_scene(n, seed=seed)
+    sc["means3D"][:, :3] *= shrink
+    sc["shs"] = np.random.default_rng(seed).normal(0, sh_scale, (n, 48)).astype(np.float32)
+    return sc
+
+
+def opaque_stack_scene(n=900, seed=3, spread=1.2):
+    """Opaque splats (opacity 0.3 .. 0.99) stacked deep over the middle of the frame, faint ones (1/255 .. 0.05) around them:
+    pixels in the middle run into the transmittance cut-off after ten-odd records, those outside walk their lists to the end."""
+    rng = np.random.default_rng(seed)
+    sc = single_gaussian_scene(n=n)
+    sc["means3D"][:, 0] = rng.uniform(-spread, spread, n)
+    sc["means3D"][:, 1] = rng.uniform(-spread, spread, n)
+    sc["means3D"][:, 2] = rng.uniform(-1.0, 1.0, n)
+    sc["scales"][:, :3] = rng.uniform(0.05, 0.3, (n, 3))
+    q = rng.normal(0, 1, (n, 4))
+    sc["rotations"] = (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
+    inner = np.hypot(sc["means3D"][:, 0], sc["means3D"][:, 1]) < 0.6 * spread
+    sc["opacities"] = np.where(inner, rng.uniform(0.3, 0.99, n), rng.uniform(1.0 / 255.0, 0.05, n)).astype(np.float32)
+    sc["shs"] = rng.normal(0, 0.3, (n, 48)).astype(np.float32)
+    sc["shs"][:, :3] += 1.0
+    return sc
+
+
+def stop_census(exp, cam):
+    """Of an inria_np.forward result: how many pixels stop at this profile's cut-off 1e-4, and how many would have stopped at
+    the other profile's 1e-3 but do not stop here. A pixel stops at cut-off c exactly if its transmittance, walked to the end
+    of its list without any cut-off, falls below c somewhere — it only falls, so: if it ends below c."""
+    from oracle import cpu_oracle
+    t_end = cpu_oracle.blend_cutoff(exp, cam, threads=4, t_cutoff=0.0)["finalT"]
+    return int((t_end < np.float32(1e-4)).sum()), int(((t_end < np.float32(1e-3)) & ~(t_end < np.float32(1e-4))).sum())
+
+
+def run_inria(scene, cam, bg=(0.0, 0.0, 0.0), **kw):
+    """A first draw, every chunk zeroed (so that what a call leaves unwritten compares equal to the restatement's zeros), and
+    the draw that is compared, with the staged records counted. Returns (rasterizer, image)."""
+    from gsrast_amd.rasterizer import SplatRasterizer
+    kw.setdefault("semantics", "inria")
+    r = SplatRasterizer(cam.width, cam.height, background=bg)
+    r.configure_from_scene(scene)
+    r.draw(cam, **kw)
+    for cb in (r.geom, r.image, r.binning):
+        if cb.tensor is not None:
+            cb.tensor.zero_()
+    r.out_color.zero_()
+    img = r.draw(cam, count_staged=True, **kw).cpu().numpy().copy()
+    return r, img
+
+
+def compare_inria(r, img, exp, what, lists=True, colors_given=False, rows=None):
+    """Everything one upstream-profile call leaves behind against oracle/inria_np.forward's (blend_with="cpp" or "numpy-expf":
+    libm's exponential): radii, tilesTouched, pointOffsets, means2D, depths, cov3D, conicOpacity, rgb and the clamp flags bit
+    for bit (a Gaussian without a tile: zeros in all of them), num_rendered, the sorted keys / values, the ranges, then
+    assert_blend_parity with finalT and nContrib bit for bit, and the staged records.
+    lists=False: the call ran with sorted_lists=False and left none (the stamp is checked instead). colors_given: the call took
+    colors_precomp, so rgb / clamped are not written (zeros). rows: (y0, y1) pixel rows a tile-row band call wrote."""
+    g = {k: v.cpu().numpy() for k, v in r.map_geometry_state().items()}
+    assert np.array_equal(g["radii"], exp["radii"]), what
+    assert np.array_equal(g["tilesTouched"].view(np.uint32), exp["tilesTouched"]), what
+    assert np.array_equal(g["pointOffsets"].view(np.uint32), exp["pointOffsets"]), what
+    bit_equal = {}
+    for k in ("means2D", "depths", "cov3D", "conicOpacity", "rgb"):
+        e = np.zeros_like(exp[k]) if (k == "rgb" and colors_given) else exp[k]
+        bit_equal[k] = bool(np.array_equal(g[k].view(np.uint32), np.ascontiguousarray(e, np.float32).view(np.uint32)))
+    print(f"[inria] {what}: " + ", ".join(f"{k} {'bit-equal' if v else 'DIFFERS'}" for k, v in bit_equal.items()))
+    for k, v in bit_equal.items():
+        assert v, (what, k, np.nonzero((g[k] != exp[k]).reshape(len(g[k]), -1).any(1))[0][:8])
+    assert np.array_equal(g["clamped"], np.zeros_like(exp["clamped"]) if colors_given else exp["clamped"]), what
+    no_tile = exp["tilesTouched"] == 0
+    for k in ("radii", "means2D", "depths", "cov3D", "conicOpacity", "rgb", "clamped"):
+        assert not g[k][no_tile].any(), (what, k, "a Gaussian without a tile keeps zeros")
+    R = exp["num_rendered"]
+    assert r.last_num_rendered == R == exp["keys"].size, (what, r.last_num_rendered, R)
+    if R > 0:
+        b = r.map_binning_state()
+        if lists:
+            assert r.last_lists_written, what
+            assert np.array_equal(b["keys"].cpu().numpy().view(np.uint64), exp["keys"]), what
+            assert np.array_equal(b["values"].cpu().numpy().view(np.uint32), exp["values"]), what
+        else:
+            assert not r.last_lists_written and (int(b["values"][0]) & 0xFFFFFFFF) == 0xFFFFFFFF, what
+    im = {k: v.cpu().numpy() for k, v in r.map_image_state().items()}
+    assert np.array_equal(im["ranges"].view(np.uint32), exp["ranges"]), what
+    ys = slice(None) if rows is None else slice(rows[0], rows[1])
+    sub = {k: exp[k][..., ys, :] for k in ("out_color", "finalT", "nContrib")}
+    err = assert_blend_parity(img[:, ys], im["finalT"][ys], im["nContrib"][ys], sub, what, bitwise_t=True)
+    assert r.last_records_staged == exp["records_staged"], (what, r.last_records_staged, exp["records_staged"])
+    return err
