@@ -15,14 +15,12 @@
 //      effect of the "last element closes its tile" test sitting inside the else branch.
 #include <stdlib.h>
 
-#include "gsr_common.hpp"
+#include "preprocess_common.hpp"      // (clampi)
 
 namespace gsr {
 namespace {
 
 constexpr int kOwnLaneMax = 4;
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(hi, max(lo, v)); }
 
 __device__ __forceinline__ void emit(uint64_t* __restrict__ keys, uint32_t* __restrict__ values, uint32_t pos,
                                      uint32_t tile, uint32_t depth_bits, uint32_t idx) {

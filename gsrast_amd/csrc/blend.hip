@@ -74,7 +74,7 @@ constexpr uint32_t kPriorityMeanList = 8192;     // entries per tile with a list
 // cycles where the SIMD could take one every two (scripts/micro/valu_issue.hip): from (0,0,-30) a tenth of the tiles runs
 // beyond 335 us, one wave each, while the rest of the chip has long finished (`profiles/r04_blend_tile_times.txt`). A deep
 // tile gets a whole workgroup — which tiles: every tile of a frame of fewer than 16 instances per visible Gaussian (the
-// host's rule, api.hip: kDeepAllMaxInstances), every tile of a call with few tiles (`strips`, above), or, behind
+// host's rule, frame_policy.hpp: kDeepAllMaxInstances), every tile of a call with few tiles (`strips`, above), or, behind
 // GSR_DEEP_BY_HISTORY, the `deep_count` leading entries of the history's order (tile_order_kernel) —: the four waves WALK
 // the list together — a round is 256 list entries, wave w fetches, culls and stages entries
 // [64 w, 64 w + 64) of it into segment w of the shared staging area, with every survivor the strips it can reach at all —
@@ -470,35 +470,18 @@ int launch_footprint_test(int n, const float* xy, const float* conic_opacity, co
     return GSR_OK;
 }
 
-int launch_blend(const FrameDims& d, const uint32_t* ranges, const uint32_t* point_list,
-                 const float* means2D, const float* colors, const float* conic_opacity,
-                 float* final_t, uint32_t* n_contrib, const float* background, float* out_color,
-                 unsigned long long* staged_counter, float t_cutoff, hipStream_t stream, const uint32_t* nonempty_tiles,
-                 uint32_t num_rendered, const uint32_t* tile_order, uint32_t* tile_ticks, bool colors_are_shs, const uint32_t* deep_count,
-                 bool deep_all, int deep_waves, const DepthTarget& depth) {
+int launch_blend(const FrameDims& d, const BlendIO& io, const uint32_t* point_list, hipStream_t stream, const uint32_t* nonempty_tiles,
+                 uint32_t num_rendered, const BlendOrder& order) {
     BlendParams p;
-    p.depth = depth;
-    p.deep_count = tile_order ? deep_count : nullptr;      // (the deep tiles are the order's leading entries)
-    p.deep_all = deep_all ? 1 : 0;
-    p.dc_stride = colors_are_shs ? 48u : 0u;
-    p.history.order = tile_order; p.history.ticks = tile_ticks;
+    fill_blend_params(p, d, io, order);
+    p.deep_count = order.tile_order ? order.deep_count : nullptr;      // (the deep tiles are the order's leading entries)
+    p.deep_all = order.deep_all ? 1 : 0;
     p.num_rendered = num_rendered;
-    p.ranges = reinterpret_cast<const uint2*>(ranges);
     p.point_list = point_list;
-    p.means2D = reinterpret_cast<const float2*>(means2D);
-    p.colors = colors;
-    p.conic_opacity = reinterpret_cast<const float4*>(conic_opacity);
-    p.final_t = final_t;
-    p.n_contrib = n_contrib;
-    p.background = background;
-    p.out_color = out_color;
-    p.staged_counter = staged_counter;
-    p.t_cutoff = t_cutoff;
-    p.dims = d;
-    p.num_tiles = (d.row_end - d.row_begin) * d.grid_x;
     if (p.num_tiles <= 0) return GSR_OK;
+    const int deep_waves = order.deep_waves;
     // (not when the staged records are counted: that count is per tile, the reference's "whole tile done" test)
-    p.nonempty = staged_counter ? nullptr : nonempty_tiles;
+    p.nonempty = io.staged_counter ? nullptr : nonempty_tiles;
     p.base_workgroups = patch_workgroups(d.grid_x, d.row_end - d.row_begin);
     // Deep tiles are possible when the host asks for them (deep_all), when the history may name some, or when the frame may
     // turn out to have few tiles with a list (the kernel's `strips`: at most 1 536 tiles, or lists of 1 024 entries on 4 096):
@@ -521,7 +504,7 @@ int launch_blend(const FrameDims& d, const uint32_t* ranges, const uint32_t* poi
         else
             hipLaunchKernelGGL(blend_wave_kernel<D>, dim3((unsigned)p.base_workgroups), dim3(kWave), 0, stream, p);
     };
-    if (depth.out) launch(std::true_type{});
+    if (io.depth.out) launch(std::true_type{});
     else launch(std::false_type{});
     GSR_LAUNCH_CHECK("blend_wave_kernel");
     return GSR_OK;

@@ -614,6 +614,25 @@ struct TileOrder {
     const uint32_t* order = nullptr;   // [workgroups of one wave per tile] or null: patch order
     uint32_t* ticks = nullptr;         // [tiles of the frame] (units of 10 ns) or null: nothing recorded
 };
+// The fields the parameter blocks of both blends (BlendParams, blend.hip; BlockBlendParams, blockbin.hip) take from the launchers' arguments
+template <typename Params>
+inline void fill_blend_params(Params& p, const FrameDims& d, const BlendIO& io, const BlendOrder& order) {
+    p.depth = io.depth;
+    p.dc_stride = io.colors_are_shs ? 48u : 0u;
+    p.history.order = order.tile_order; p.history.ticks = order.tile_ticks;
+    p.ranges = reinterpret_cast<const uint2*>(io.ranges);
+    p.means2D = reinterpret_cast<const float2*>(io.means2D);
+    p.colors = io.colors;
+    p.conic_opacity = reinterpret_cast<const float4*>(io.conic_opacity);
+    p.final_t = io.final_t;
+    p.n_contrib = io.n_contrib;
+    p.background = io.background;
+    p.out_color = io.out_color;
+    p.staged_counter = io.staged_counter;
+    p.t_cutoff = io.t_cutoff;
+    p.dims = d;
+    p.num_tiles = (d.row_end - d.row_begin) * d.grid_x;
+}
 // ~6 % steps (4 mantissa bits): tiles that took about as long keep their patch order among themselves
 __device__ __forceinline__ uint32_t quantise_ticks(uint32_t t) {
     if (t < 16u) return t;

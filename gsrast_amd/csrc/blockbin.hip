@@ -872,19 +872,17 @@ BlockFeed block_feed(int n, int grid_x, int grid_y, uint32_t r_total, char* geo_
 }
 
 // Everything of the block plan up to (not including) the emission: block lists, unit masks, prefixes and
-// the tile ranges. sorted_depth / sorted_idx / sorted_rect: the n visible Gaussians in depth order (depth bits, index,
-// packed rectangle). ent_rd / ent_idx: R-sized scratch for the block lists. ev_coarse_end: optional event recorded
+// the tile ranges. sorted: the l.n visible Gaussians in depth order (depth bits, index, packed rectangle).
+// l.ent_rd / l.ent_idx: R-sized scratch for the block lists. ev_coarse_end: optional event recorded
 // after the block lists (stage timing).
-int launch_block_binning(int n, const uint32_t* sorted_depth, const uint32_t* sorted_idx, const uint32_t* sorted_rect,
-                         int grid_x, int grid_y, uint32_t r_total, char* geo_scratch, uint64_t* ent_rd,
-                         uint32_t* ent_idx, char* bin_scratch, uint32_t* ranges, bool close_single, hipStream_t stream,
+int launch_block_binning(const BlockLists& l, const DepthTriple& sorted, uint32_t* ranges, bool close_single, hipStream_t stream,
                          hipEvent_t ev_coarse_end, uint32_t* nonempty_tiles, uint32_t* skipped_stamp, int cus) {
-    const PlanTables t = plan_tables(n, grid_x, grid_y, r_total, geo_scratch, bin_scratch);
+    const PlanTables t = plan_tables(l.n, l.grid_x, l.grid_y, l.r_total, l.geo_scratch, l.bin_scratch);
     if (t.chunk == kCoarse)
-        hipLaunchKernelGGL(coarse_count_kernel<kCoarse>, dim3(t.chunks), dim3(kCoarse), 0, stream, n, sorted_rect, t.nbx, t.nbp,
+        hipLaunchKernelGGL(coarse_count_kernel<kCoarse>, dim3(t.chunks), dim3(kCoarse), 0, stream, l.n, sorted.r, t.nbx, t.nbp,
                            t.table);
     else
-        hipLaunchKernelGGL(coarse_count_kernel<kCoarseSmall>, dim3(t.chunks), dim3(kCoarseSmall), 0, stream, n, sorted_rect, t.nbx,
+        hipLaunchKernelGGL(coarse_count_kernel<kCoarseSmall>, dim3(t.chunks), dim3(kCoarseSmall), 0, stream, l.n, sorted.r, t.nbx,
                            t.nbp, t.table);
     GSR_LAUNCH_CHECK("coarse_count_kernel");
     hipLaunchKernelGGL(blockscan_reduce_kernel, dim3(t.groups), dim3(t.nbp), 0, stream, t.table, t.chunks, t.nbp, t.partial);
@@ -920,12 +918,12 @@ int launch_block_binning(int n, const uint32_t* sorted_depth, const uint32_t* so
     } while (0)
     if (t.chunk == kCoarse) {
         if (mask_bytes > 48 * 1024) GSR_STEP_LDS(coarse_emit_kernel<kCoarse>, kCoarse);
-        hipLaunchKernelGGL(coarse_emit_kernel<kCoarse>, dim3(t.chunks), dim3(kCoarse), mask_bytes, stream, n, sorted_depth,
-                           sorted_idx, sorted_rect, t.table, t.nbx, t.nb, t.nbp, ent_rd, ent_idx);
+        hipLaunchKernelGGL(coarse_emit_kernel<kCoarse>, dim3(t.chunks), dim3(kCoarse), mask_bytes, stream, l.n, sorted.k,
+                           sorted.v, sorted.r, t.table, t.nbx, t.nb, t.nbp, l.ent_rd, l.ent_idx);
     } else {
         if (mask_bytes > 48 * 1024) GSR_STEP_LDS(coarse_emit_kernel<kCoarseSmall>, kCoarseSmall);
-        hipLaunchKernelGGL(coarse_emit_kernel<kCoarseSmall>, dim3(t.chunks), dim3(kCoarseSmall), mask_bytes, stream, n, sorted_depth,
-                           sorted_idx, sorted_rect, t.table, t.nbx, t.nb, t.nbp, ent_rd, ent_idx);
+        hipLaunchKernelGGL(coarse_emit_kernel<kCoarseSmall>, dim3(t.chunks), dim3(kCoarseSmall), mask_bytes, stream, l.n, sorted.k,
+                           sorted.v, sorted.r, t.table, t.nbx, t.nb, t.nbp, l.ent_rd, l.ent_idx);
     }
 #undef GSR_STEP_LDS
     GSR_LAUNCH_CHECK("coarse_emit_kernel");
@@ -933,69 +931,49 @@ int launch_block_binning(int n, const uint32_t* sorted_depth, const uint32_t* so
 
     // persistent grid: enough waves to fill the chip, never more than there can be units
     const uint32_t count_wgs = std::min<uint32_t>((t.max_units + 3) / 4, (uint32_t)cus * 8u);
-    hipLaunchKernelGGL(unit_masks_kernel, dim3(count_wgs), dim3(256), 0, stream, t.meta, t.nb, t.nbx, ent_rd, t.unit_masks, t.cnt);
+    hipLaunchKernelGGL(unit_masks_kernel, dim3(count_wgs), dim3(256), 0, stream, t.meta, t.nb, t.nbx, l.ent_rd, t.unit_masks, t.cnt);
     GSR_LAUNCH_CHECK("unit_masks_kernel");
-    hipLaunchKernelGGL(block_prefix_kernel, dim3(t.nb), dim3(256), 0, stream, t.meta, t.nbx, grid_x, grid_y, t.cnt, t.tile_count);
+    hipLaunchKernelGGL(block_prefix_kernel, dim3(t.nb), dim3(256), 0, stream, t.meta, t.nbx, l.grid_x, l.grid_y, t.cnt, t.tile_count);
     GSR_LAUNCH_CHECK("block_prefix_kernel");
     hipLaunchKernelGGL(tile_start_kernel, dim3(1), dim3(1024), 0, stream, t.tile_count, t.tiles, t.tile_start,
-                       reinterpret_cast<uint2*>(ranges), r_total, close_single, nonempty_tiles, skipped_stamp);
+                       reinterpret_cast<uint2*>(ranges), l.r_total, close_single, nonempty_tiles, skipped_stamp);
     GSR_LAUNCH_CHECK("tile_start_kernel");
     return GSR_OK;
 }
 
 // The emission: the sorted keys / values written from the tables launch_block_binning left.
-int launch_block_emit(int n, int grid_x, int grid_y, uint32_t r_total, char* geo_scratch, const uint64_t* ent_rd,
-                      const uint32_t* ent_idx, char* bin_scratch, uint64_t* keys, uint32_t* values, hipStream_t stream, bool beside_blend,
-                      int cus) {
-    const PlanTables t = plan_tables(n, grid_x, grid_y, r_total, geo_scratch, bin_scratch);
+int launch_block_emit(const BlockLists& l, uint64_t* keys, uint32_t* values, hipStream_t stream, bool beside_blend, int cus) {
+    const PlanTables t = plan_tables(l.n, l.grid_x, l.grid_y, l.r_total, l.geo_scratch, l.bin_scratch);
     // Workgroups (of four waves) per CU: two where the Gaussians cover many tiles each (long, dense runs: three or four
     // measured 1.5 % slower on the bench frame and at 4K), four where they cover few (short runs, the waves wait more than
     // they store: 0.416 -> 0.366 ms from outside the cloud, R / V = 23 against 88 on the bench frame).
     // With the blend beside it (second stream) always two: four of these workgroups hold 448 of a SIMD's 512 vector registers
     // and no wave of the blend fits until they retire — the stand-in from outside the cloud, overlapped: blend 0.96 ms for
     // 0.45 alone, the frame 1.70 for 1.50.
-    const uint32_t per_cu = ((uint64_t)r_total >= 48ull * (uint64_t)n || beside_blend) ? 2u : 4u;
+    const uint32_t per_cu = ((uint64_t)l.r_total >= 48ull * (uint64_t)l.n || beside_blend) ? 2u : 4u;
     // (a unit may be dealt as four items, see the kernel: a wave per item on small frames)
     const uint32_t emit_wgs = std::min<uint32_t>(t.max_units, (uint32_t)cus * per_cu);
-    hipLaunchKernelGGL(block_emit_kernel, dim3(emit_wgs), dim3(kEmitWaves * kWave), 0, stream, t.meta, t.nb, t.nbx, grid_x, grid_y,
-                       ent_rd, ent_idx, t.unit_masks, t.cnt, t.tile_start, keys, values, r_total);
+    hipLaunchKernelGGL(block_emit_kernel, dim3(emit_wgs), dim3(kEmitWaves * kWave), 0, stream, t.meta, t.nb, t.nbx, l.grid_x, l.grid_y,
+                       l.ent_rd, l.ent_idx, t.unit_masks, t.cnt, t.tile_start, keys, values, l.r_total);
     GSR_LAUNCH_CHECK("block_emit_kernel");
     return GSR_OK;
 }
 
 // The blend, fed from the block lists (independent of launch_block_emit).
-int launch_blend_blocks(int n, const FrameDims& d, uint32_t r_total, char* geo_scratch, const uint32_t* ent_idx, char* bin_scratch,
-                        const uint32_t* ranges, const float* means2D, const float* colors, const float* conic_opacity,
-                        float* final_t, uint32_t* n_contrib, const float* background, float* out_color,
-                        unsigned long long* staged_counter, float t_cutoff, hipStream_t stream,
-                        const uint32_t* tile_order, uint32_t* tile_ticks, bool colors_are_shs, const DepthTarget& depth) {
-    const PlanTables t = plan_tables(n, d.grid_x, d.grid_y, r_total, geo_scratch, bin_scratch);
+int launch_blend_blocks(const FrameDims& d, const BlockLists& l, const BlendIO& io, hipStream_t stream, const BlendOrder& order) {
+    const PlanTables t = plan_tables(l.n, d.grid_x, d.grid_y, l.r_total, l.geo_scratch, l.bin_scratch);
     BlockBlendParams p;
-    p.depth = depth;
-    p.dc_stride = colors_are_shs ? 48u : 0u;
-    p.history.order = tile_order; p.history.ticks = tile_ticks;
+    fill_blend_params(p, d, io, order);
     p.meta = t.meta;
     p.nbx = t.nbx;
     p.unit_masks = t.unit_masks;
-    p.ent_idx = ent_idx;
-    p.ranges = reinterpret_cast<const uint2*>(ranges);
-    p.means2D = reinterpret_cast<const float2*>(means2D);
-    p.colors = colors;
-    p.conic_opacity = reinterpret_cast<const float4*>(conic_opacity);
-    p.final_t = final_t;
-    p.n_contrib = n_contrib;
-    p.background = background;
-    p.out_color = out_color;
-    p.staged_counter = staged_counter;
-    p.t_cutoff = t_cutoff;
-    p.dims = d;
-    p.num_tiles = (d.row_end - d.row_begin) * d.grid_x;
+    p.ent_idx = l.ent_idx;
     if (p.num_tiles <= 0) return GSR_OK;
     // A call with few tiles (one rank's band of a sharded frame) cannot fill the chip with one wave per
     // tile: four waves per tile then, one 16 x 4 strip each. (Not when the staged records are counted:
     // that count is per tile, the reference's "whole tile done" test.)
-    p.waves_per_tile = (p.num_tiles <= 1536 && !staged_counter) ? 4 : 1;     // (measured: 960 tiles 0.17 -> 0.13 ms, 4080 tiles 0.16 -> 0.29 ms)
-    if (depth.out)
+    p.waves_per_tile = (p.num_tiles <= 1536 && !io.staged_counter) ? 4 : 1;     // (measured: 960 tiles 0.17 -> 0.13 ms, 4080 tiles 0.16 -> 0.29 ms)
+    if (io.depth.out)
         hipLaunchKernelGGL(blend_blocks_kernel<true>, dim3((unsigned)(patch_workgroups(d.grid_x, d.row_end - d.row_begin) * p.waves_per_tile)),
                            dim3(kWave), 0, stream, p);
     else

@@ -41,7 +41,7 @@ struct BlockFeed {
 };
 BlockFeed block_feed(int n, int grid_x, int grid_y, uint32_t r_total, char* geo_scratch, const uint32_t* ent_idx, char* bin_scratch);
 
-// Which lists the forward call that issued `r` left for a backward call with these sizes / rows / point_list (api.hip):
+// Which lists the forward call that issued `r` left for a backward call with these sizes / rows / point_list (chunks.hip):
 // *lists_written — the sorted lists are in point_list; *from_blocks — it ran the block plan and blended from the block
 // lists: *feed says where they are. GSR_ERR_INVALID_ARG if the receipt does not fit the arguments or promises no list.
 // The order the gsr_forward call that issued `r` gave its blend workgroups (slow tiles first: TileOrder, blend_core.hpp), if

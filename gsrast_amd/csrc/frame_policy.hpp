@@ -1,4 +1,4 @@
-// gsr_forward's per-frame choices (api.hip): the switch points, what they read and the rules that apply them. Host C++17
+// gsr_forward's per-frame choices (the stages of api.hip call them): the switch points, what they read and the rules that apply them. Host C++17
 // only and pure — plain values in, small structs out; no HIP, no history pointer. gsr_forward copies what a rule reads out
 // of the tile history, calls the rule where the choice is made and writes back what it returns (tests/test_frame_policy.py).
 #pragma once
@@ -48,7 +48,7 @@ inline DeviceShape device_shape_of(int cus) {
     return s;
 }
 
-// What the environment asks for, read once per process (A/B runs and the tests set these before the first call; api.hip
+// What the environment asks for, read once per process (A/B runs and the tests set these before the first call; thread_state.hip
 // read_env_knobs).
 struct EnvKnobs {
     bool tile_history;         // GSR_TILE_HISTORY=0: no call reads or writes a tile history
@@ -60,7 +60,7 @@ struct EnvKnobs {
                                // count; measured neutral, `profiles/r06_deep_tiles.txt`: off by default)
 };
 
-// What the rules read of the call's tile history (gsr_tile_history, api.hip: the same fields, copied). A call without a
+// What the rules read of the call's tile history (gsr_tile_history, api_internal.hpp: the same fields, copied). A call without a
 // history reads the zeros of a HistoryView{}.
 struct HistoryView {
     bool wanted = false;        // the last statistics say the frame ends on a few slow tiles (or is a light one)

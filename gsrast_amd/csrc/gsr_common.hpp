@@ -6,6 +6,7 @@
 
 #include "../../include/gsrast_amd.h"
 #include "frame_policy.hpp"      // (DeviceShape, the launch heuristics' switch points)
+#include "shared_words.hpp"      // (the pinned host block, sort_info)
 
 namespace gsr {
 
@@ -24,6 +25,13 @@ int record_error(int code);
             ::gsr::set_hip_error(e_, #expr);                \
             return GSR_ERR_HIP;                             \
         }                                                   \
+    } while (0)
+
+// A step of a launch sequence: a GSR_* code other than GSR_OK ends the sequence.
+#define GSR_TRY(call)                                       \
+    do {                                                    \
+        const int rc_ = (call);                             \
+        if (rc_ != GSR_OK) return rc_;                      \
     } while (0)
 
 #define GSR_LAUNCH_CHECK(name)                              \
@@ -85,18 +93,25 @@ int launch_preprocess_inria(const gsr_forward_args& a, const gsr_geometry_state&
                             uint32_t* rect_packed, const FrameDims& d, hipStream_t stream, uint4* wave_sums = nullptr,
                             uint32_t big_from = 0xFFFFFFFFu);
 
-// nonzero (u32 per 4096 elements) / nonzero_total: optional — exclusive prefix of the per-tile counts of non-zero
-// elements and their total (the depth order's compaction offsets, radix_sort.hip)
-// host_words (mapped host memory, optional; needs total64): [0] = the non-zero total, [2..3] = the 64-bit total, written by the
-// scan itself. clear / clear_bytes (optional, 16-byte granules): device memory the first launch also zeroes.
-// wave_sums / main_count / side_max / side_words (all or none; need nonzero and big): the preprocess's per-wave records
-// (store_wave_sums) — the first launch then reads those instead of `in` — and the depth order's side list, see scan.hip.
+// What the depth order takes from the scan of tilesTouched on the way (gsr_forward; a plain scan leaves all of it null).
+struct ScanByproducts {
+    uint32_t* info = nullptr;            // sort_info (shared_words.hpp): gets kInfoTotal, the 64-bit total, and — with `nonzero` — kInfoVisible
+    uint32_t* host = nullptr;            // the pinned host block (needs info): kHostVisible = the non-zero total, kHostTotal = the 64-bit
+                                         // total, written by the scan itself
+    uint32_t* nonzero = nullptr;         // u32 per 4096 elements: the exclusive prefix of the tiles' counts of non-zero elements (the
+                                         // depth order's compaction offsets, radix_sort.hip); their total: kInfoVisible
+    void* clear = nullptr;               // device memory the first launch also zeroes (16-byte granules)
+    size_t clear_bytes = 0;
+    // wave_sums / main_count (both or neither; need nonzero and big): the preprocess's per-wave records (store_wave_sums) — the
+    // first launch then reads those instead of `in` — and the depth order's side list (kInfoSide, kHostSideWay, kHostSideCounted), see scan.hip
+    const uint4* wave_sums = nullptr;
+    uint32_t* main_count = nullptr;
+    uint32_t side_max = 0;
+    uint32_t* big = nullptr;             // u32 per 4096 elements (needs host): kHostBigInstances = the 64-bit sum of the elements >= big_from
+    uint32_t big_from = 0;
+};
 int launch_inclusive_scan(const uint32_t* in, uint32_t* out, size_t n, char* temp, hipStream_t stream,
-                          unsigned long long* total64 = nullptr, uint32_t* nonzero = nullptr, uint32_t* nonzero_total = nullptr,
-                          uint32_t* host_words = nullptr, void* clear = nullptr, size_t clear_bytes = 0,
-                          const uint4* wave_sums = nullptr, uint32_t* main_count = nullptr,
-                          uint32_t side_max = 0, uint32_t* side_words = nullptr,
-                          uint32_t* big = nullptr, uint32_t big_from = 0);     // big (u32 per 4096 elements, needs host_words): host_words[10..11] = the 64-bit sum of the elements >= big_from
+                          const ScanByproducts& by = ScanByproducts{});
 size_t scan_temp_bytes(size_t n);
 
 int launch_gather_counts(int n, const uint32_t* sorted_depth, const uint32_t* sorted_idx, const uint32_t* tiles_touched,
@@ -111,8 +126,7 @@ int launch_sort_pairs(const uint64_t* keys_in, uint64_t* keys_out, const uint32_
 size_t sort_temp_bytes(size_t n);
 struct SweepScratch;
 // The depth order's side list (radix_sort.hip, depth_side_kernel): the visible keys whose top byte is not main_top, when
-// the scan found few of them. words: [0] the side way is taken (decided by the scan), [1] keys on the list, [2] those of
-// them below main_top. main_partial: the compaction's offsets counted for the main keys only.
+// the scan found few of them. words: sort_info + kInfoSide, indexed by SideWord (shared_words.hpp). main_partial: the compaction's offsets counted for the main keys only.
 constexpr uint32_t kDepthSideMax = 1024;
 constexpr uint32_t kDepthMainTop = 0x3Fu;            // float bits of [0.5, 1)
 struct DepthSide {
@@ -126,25 +140,39 @@ int launch_depth_side(const DepthSide& side, uint32_t m, uint32_t m_lo, uint32_t
 // Depth order (radix_sort.hip). sc4: one scratch area per pass, already zeroed by the caller (look-back words,
 // tickets, error word, histograms); the error word and the digit histograms live in sc4[0].
 size_t depth_compact_scratch_bytes(size_t n);
-// offsets_ready: `partial` / info[1] already hold the compaction offsets per 4096 keys and the visible count (the scan of
-// tilesTouched produced them on the way: a key is the sentinel exactly where tilesTouched is 0)
-// host_top (optional, mapped host memory): gets info[0] too, for a host that reads it after an event.
-// rect_by_index / out_r (both or neither): the visible Gaussians' packed rectangles, compacted with the pairs; passed on as
-// second_in / a_s / b_s they travel through the passes with the indices and arrive in depth order (gathering them by
-// index afterwards is a random 4-byte read per Gaussian).
-int sort_u32_prepare(const uint32_t* keys_in, uint32_t n, uint32_t* out_k, uint32_t* out_v, uint32_t* partial,
-                     const SweepScratch* sc4, uint32_t* info, hipStream_t stream, bool offsets_ready = false,
-                     const uint32_t* rect_by_index = nullptr, uint32_t* out_r = nullptr, uint32_t* host_top = nullptr,
-                     const DepthSide* side = nullptr);
-int sort_u32_passes(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t n, uint32_t* a_k, uint32_t* a_v, uint32_t* b_k,
-                    uint32_t* b_v, const SweepScratch* sc4, int first, int last, hipStream_t stream,
-                    const uint32_t* n_dev = nullptr, const uint32_t* second_in = nullptr, uint32_t* a_s = nullptr,
-                    uint32_t* b_s = nullptr, const DepthSide* drop_side = nullptr, uint32_t* rec_a = nullptr,
-                    uint32_t* rec_b = nullptr);
-// Scenes beyond 16 M Gaussians: no compaction — the digit counts only (and info[0], info[4], host_top as sort_u32_prepare);
+// A depth pass's keys, values (Gaussian indices) and packed rectangles: three arrays of one length that travel together.
+struct DepthTriple { uint32_t *k = nullptr, *v = nullptr, *r = nullptr; };
+struct DepthPrepare {
+    const uint32_t* keys_in = nullptr;
+    // rect_by_index / out.r (both or neither): the visible Gaussians' packed rectangles, compacted with the pairs; passed on as
+    // the passes' `in.r` they travel with the indices and arrive in depth order (gathering them by index afterwards is a
+    // random 4-byte read per Gaussian).
+    const uint32_t* rect_by_index = nullptr;
+    DepthTriple out;
+    uint32_t* partial = nullptr;
+    // offsets_ready: `partial` / info[kInfoVisible] already hold the compaction offsets per 4096 keys and the visible count (the
+    // scan of tilesTouched produced them on the way: a key is the sentinel exactly where tilesTouched is 0)
+    bool offsets_ready = false;
+    const SweepScratch* sc4 = nullptr;
+    uint32_t* info = nullptr;            // sort_info
+    uint32_t* host = nullptr;            // optional, the pinned host block: gets the top digits too, for a host that reads them after an event
+    const DepthSide* side = nullptr;
+};
+int sort_u32_prepare(const DepthPrepare& p, uint32_t n, hipStream_t stream);
+// Passes [first, last): in -> a -> b -> a -> b (radix_sort.hip explains the optional members)
+struct DepthPasses {
+    DepthTriple in, a, b;                // in.v null: the value is the input index; in.r / a.r / b.r: all or none
+    const SweepScratch* sc4 = nullptr;
+    int first = 0, last = 0;
+    const uint32_t* n_dev = nullptr;
+    const DepthSide* drop_side = nullptr;
+    uint32_t *rec_a = nullptr, *rec_b = nullptr;
+};
+int sort_u32_passes(const DepthPasses& p, uint32_t n, hipStream_t stream);
+// Scenes beyond 16 M Gaussians: no compaction — the digit counts only (and the words of info and host as sort_u32_prepare);
 // the first pass then reads the per-Gaussian keys itself, dropping the sentinels (sort_u32_passes, drop_side).
 int sort_u32_prepare_counts(const uint32_t* keys_in, uint32_t n, const SweepScratch* sc4, uint32_t* info, hipStream_t stream,
-                            uint32_t* host_top, const DepthSide* side);
+                            uint32_t* host, const DepthSide* side);
 
 // Column-major emission (emit.hip): count, column scan and emission. The two events (may be null)
 // are recorded between the N-sized preparation and the emission kernel, for stage timing.
@@ -157,40 +185,59 @@ int launch_emit_columns(int n, const uint32_t* sorted_depth, const uint32_t* sor
 bool blockbin_supported(int grid_x, int grid_y);
 size_t blockbin_geo_bytes(size_t n);
 size_t blockbin_bin_bytes(size_t r);
-int launch_block_binning(int n, const uint32_t* sorted_depth, const uint32_t* sorted_idx, const uint32_t* sorted_rect,
-                         int grid_x, int grid_y, uint32_t r_total, char* geo_scratch, uint64_t* ent_rd,
-                         uint32_t* ent_idx, char* bin_scratch, uint32_t* ranges, bool close_single, hipStream_t stream,
+// What the block plan's launchers share: the frame's sizes, its tables' two scratch areas and the R-sized block lists.
+struct BlockLists {
+    int n = 0;                           // visible Gaussians
+    int grid_x = 0, grid_y = 0;
+    uint32_t r_total = 0;
+    char* geo_scratch = nullptr;
+    char* bin_scratch = nullptr;
+    uint64_t* ent_rd = nullptr;          // (rectangle | depth bits) of the block-list entries
+    uint32_t* ent_idx = nullptr;         // their Gaussians
+};
+// What both blend launchers read and write.
+struct BlendIO {
+    const uint32_t* ranges = nullptr;
+    const float* means2D = nullptr;
+    const float* colors = nullptr;
+    bool colors_are_shs = false;                 // (`colors` = the SH array: TileFeed::dc_stride)
+    const float* conic_opacity = nullptr;
+    float* final_t = nullptr;
+    uint32_t* n_contrib = nullptr;
+    const float* background = nullptr;
+    float* out_color = nullptr;
+    unsigned long long* staged_counter = nullptr;
+    float t_cutoff = 0.0f;
+    DepthTarget depth;                           // (out_depth: the depth channel too, blend_core.hpp)
+};
+// The order of a blend's workgroups and its deep tiles.
+struct BlendOrder {
+    const uint32_t* tile_order = nullptr;        // (longest tiles first: TileOrder, blend_core.hpp)
+    uint32_t* tile_ticks = nullptr;
+    const uint32_t* deep_count = nullptr;        // (device word: the order's leading entries that get four waves, blend.hip)
+    bool deep_all = false;                       // (every tile gets four waves)
+    int deep_waves = 4;                          // (... or 8 or 16: frames whose work sits in few tiles)
+};
+// sorted: the l.n visible Gaussians in depth order
+int launch_block_binning(const BlockLists& l, const DepthTriple& sorted, uint32_t* ranges, bool close_single, hipStream_t stream,
                          hipEvent_t ev_coarse_end, uint32_t* nonempty_tiles = nullptr, uint32_t* skipped_stamp = nullptr,
                          int cus = 256);
-int launch_block_emit(int n, int grid_x, int grid_y, uint32_t r_total, char* geo_scratch, const uint64_t* ent_rd,
-                      const uint32_t* ent_idx, char* bin_scratch, uint64_t* keys, uint32_t* values, hipStream_t stream,
+int launch_block_emit(const BlockLists& l, uint64_t* keys, uint32_t* values, hipStream_t stream,
                       bool beside_blend = false,           // (the blend runs on another stream meanwhile: leave it room)
                       int cus = 256);
-int launch_blend_blocks(int n, const FrameDims& d, uint32_t r_total, char* geo_scratch, const uint32_t* ent_idx, char* bin_scratch,
-                        const uint32_t* ranges, const float* means2D, const float* colors, const float* conic_opacity,
-                        float* final_t, uint32_t* n_contrib, const float* background, float* out_color,
-                        unsigned long long* staged_counter, float t_cutoff, hipStream_t stream,
-                        const uint32_t* tile_order = nullptr, uint32_t* tile_ticks = nullptr, bool colors_are_shs = false,
-                        const DepthTarget& depth = DepthTarget{});
+int launch_blend_blocks(const FrameDims& d, const BlockLists& l, const BlendIO& io, hipStream_t stream,
+                        const BlendOrder& order = BlendOrder{});          // (its deep_* members are not read: the block-fed blend has no deep tiles)
 
 // nonempty (may be null): device word, zero before the launch; receives the number of tiles that got a list
 int launch_tile_ranges(const uint64_t* keys, size_t n, uint32_t* ranges, int num_tiles, bool close_single, hipStream_t stream,
                        uint32_t* nonempty = nullptr);
 
-int launch_blend(const FrameDims& d, const uint32_t* ranges, const uint32_t* point_list,
-                 const float* means2D, const float* colors, const float* conic_opacity,
-                 float* final_t, uint32_t* n_contrib, const float* background, float* out_color,
-                 unsigned long long* staged_counter, float t_cutoff, hipStream_t stream,
+int launch_blend(const FrameDims& d, const BlendIO& io, const uint32_t* point_list, hipStream_t stream,
                  const uint32_t* nonempty_tiles = nullptr, uint32_t num_rendered = 0,       // (both: see blend.hip, four waves per tile)
-                 const uint32_t* tile_order = nullptr, uint32_t* tile_ticks = nullptr,       // (longest tiles first: TileOrder, blend_core.hpp)
-                 bool colors_are_shs = false,                                                // (`colors` = the SH array: TileFeed::dc_stride)
-                 const uint32_t* deep_count = nullptr,                                       // (device word: the order's leading entries that get four waves, blend.hip)
-                 bool deep_all = false,                                                      // (every tile gets four waves)
-                 int deep_waves = 4,                                                         // (... or 8 or 16: frames whose work sits in few tiles)
-                 const DepthTarget& depth = DepthTarget{});                                  // (out_depth: the depth channel too, blend_core.hpp)
+                 const BlendOrder& order = BlendOrder{});
 // Longest tiles first: the order of this call's blend workgroups from the ticks the tiles of the call before left.
 constexpr int kTileOrderMax = 32768;      // workgroups (one per tile, patch grid padded) up to which the order is kept: 128 KB of LDS for its sort
-int current_device_shape(DeviceShape* out);                // the current device's, cached per device (api.hip)
+int current_device_shape(DeviceShape* out);                // the current device's, cached per device (thread_state.hip)
 int tile_order_workgroups(const FrameDims& d);
 // ticks / ticks_before: the tile times of the history's last frame and of the one before it; *sorted = false (and nothing
 // launched): this device has no room for the sort's LDS

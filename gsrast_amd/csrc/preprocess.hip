@@ -7,33 +7,11 @@
 // float32 operation order (this file is compiled with -ffp-contract=off), including
 // the double intermediates of quatToMat, so every integer output (radii, rects,
 // tilesTouched) is reproducible bit for bit.
-#include "gsr_common.hpp"
+#include "preprocess_common.hpp"
 
 namespace gsr {
 namespace {
 
-struct M3 { float m[3][3]; };   // m[col][row]
-
-__device__ __forceinline__ float fminr(float a, float b) { return (b < a) ? b : a; }   // glm::min
-__device__ __forceinline__ float fmaxr(float a, float b) { return (a < b) ? b : a; }   // glm::max
-
-__device__ __forceinline__ M3 mul3(const M3& a, const M3& b) {
-    M3 r;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int row = 0; row < 3; ++row)
-            r.m[c][row] = a.m[0][row] * b.m[c][0] + a.m[1][row] * b.m[c][1] + a.m[2][row] * b.m[c][2];
-    return r;
-}
-__device__ __forceinline__ M3 transpose3(const M3& a) {
-    M3 r;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int row = 0; row < 3; ++row) r.m[c][row] = a.m[row][c];
-    return r;
-}
 __device__ __forceinline__ float4 mat4_vec4(const float* __restrict__ m, float x, float y, float z, float w) {
     float4 o;
     o.x = (m[0] * x + m[4] * y) + (m[8] * z + m[12] * w);
@@ -41,20 +19,6 @@ __device__ __forceinline__ float4 mat4_vec4(const float* __restrict__ m, float x
     o.z = (m[2] * x + m[6] * y) + (m[10] * z + m[14] * w);
     o.w = (m[3] * x + m[7] * y) + (m[11] * z + m[15] * w);
     return o;
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(hi, max(lo, v)); }
-
-// getRect with the y range clipped to the tile-row band of this call (the whole grid
-// when the call is not sharded: then it is exactly GSCuda.cu:249-259).
-__device__ __forceinline__ void tile_rect(float px, float py, int ex, int ey, const FrameDims& d,
-                                          int& x0, int& y0, int& x1, int& y1) {
-    x0 = clampi((int)((px - (float)ex) / 16.0f), 0, d.grid_x);
-    y0 = clampi((int)((py - (float)ey) / 16.0f), 0, d.grid_y);
-    x1 = clampi((int)((((px + (float)ex) + 16.0f) - 1.0f) / 16.0f), 0, d.grid_x);
-    y1 = clampi((int)((((py + (float)ey) + 16.0f) - 1.0f) / 16.0f), 0, d.grid_y);
-    y0 = clampi(y0, d.row_begin, d.row_end);
-    y1 = clampi(y1, d.row_begin, d.row_end);
 }
 
 struct PreprocessParams {
@@ -230,7 +194,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const PreprocessParams 
                 o_co[0] = cc * det_inv; o_co[1] = -cb * det_inv; o_co[2] = ca * det_inv; o_co[3] = opacity;
                 out_radius = (int)my_radius;
                 out_tiles = band_area;
-                out_rect = (uint32_t)x0 | ((uint32_t)(x1 - x0) << 8) | ((uint32_t)y0 << 16) | ((uint32_t)(y1 - y0) << 24);
+                out_rect = pack_rect(x0, y0, x1, y1);
             }
         }
     }
@@ -321,33 +285,9 @@ int launch_preprocess(const gsr_forward_args& a, const gsr_geometry_state& g, in
                       bool colors_elsewhere, uint32_t big_from) {
     PreprocessParams p;
     p.skip_colors = a.colors_precomp != nullptr || colors_elsewhere;
-    p.n = a.num_gaussians;
-    p.means3D = reinterpret_cast<const float4*>(a.means3D);
-    p.scales = reinterpret_cast<const float4*>(a.scales);
-    p.scale_modifier = a.scale_modifier;
-    p.rotations = reinterpret_cast<const float4*>(a.rotations);
-    p.opacities = a.opacities;
-    p.shs = a.shs;
-    p.cov3D_precomp = a.cov3D_precomp;
-    p.colors_precomp = a.colors_precomp;
-    p.view = a.view_matrix;
-    p.proj = a.proj_matrix;
-    p.tan_fovx = a.tan_fovx;
-    p.tan_fovy = a.tan_fovy;
+    fill_preprocess_params(p, a, g, radii, depth_keys, rect_packed, d, wave_sums, big_from);
     p.focal = (float)a.height / (2.0f * a.tan_fovy);   // GSCuda.cu:721
-    p.radii = radii;
-    p.means2D = reinterpret_cast<float2*>(g.means2D);
-    p.depths = g.depths;
-    p.cov3Ds = g.cov3D;
-    p.rgb = g.rgb;
-    p.conic_opacity = reinterpret_cast<float4*>(g.conic_opacity);
-    p.tiles_touched = g.tiles_touched;
-    p.depth_keys = depth_keys;
-    p.rect_packed = rect_packed;
-    p.wave_sums = wave_sums;
-    p.big_from = big_from;
     p.rects = reinterpret_cast<int2*>(a.rects);
-    p.dims = d;
     const unsigned blocks = (unsigned)((a.num_gaussians + 255) / 256);
     hipLaunchKernelGGL(preprocess_kernel, dim3(blocks), dim3(256), 0, stream, p);
     GSR_LAUNCH_CHECK("preprocess_kernel");

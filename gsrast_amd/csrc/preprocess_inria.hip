@@ -13,33 +13,10 @@
 //   D9   focal    : separate focal_x / focal_y
 //   cov3D         : quaternion not re-normalised, Sigma = (S R)^T (S R)
 // Inputs keep the reference app's buffers (means3D / scales vec4-strided).
-#include "gsr_common.hpp"
+#include "preprocess_common.hpp"
 
 namespace gsr {
 namespace {
-
-struct M3 { float m[3][3]; };   // m[col][row]
-
-__device__ __forceinline__ M3 mul3(const M3& a, const M3& b) {
-    M3 r;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int row = 0; row < 3; ++row)
-            r.m[c][row] = a.m[0][row] * b.m[c][0] + a.m[1][row] * b.m[c][1] + a.m[2][row] * b.m[c][2];
-    return r;
-}
-__device__ __forceinline__ M3 transpose3(const M3& a) {
-    M3 r;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int row = 0; row < 3; ++row) r.m[c][row] = a.m[row][c];
-    return r;
-}
-__device__ __forceinline__ float fminr(float a, float b) { return (b < a) ? b : a; }
-__device__ __forceinline__ float fmaxr(float a, float b) { return (a < b) ? b : a; }
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(hi, max(lo, v)); }
 
 constexpr float SH_C0 = 0.28209479177387814f;
 constexpr float SH_C1 = 0.4886025119029199f;
@@ -168,14 +145,8 @@ __global__ __launch_bounds__(256) void preprocess_inria_kernel(const InriaParams
             pix = (float)((((double)prx + 1.0) * (double)p.dims.width - 1.0) * 0.5);
             piy = (float)((((double)pry + 1.0) * (double)p.dims.height - 1.0) * 0.5);
             ri = (int)my_radius;
-            const float rf = (float)ri;
-            x0 = clampi((int)((pix - rf) / 16.0f), 0, p.dims.grid_x);
-            fy0 = clampi((int)((piy - rf) / 16.0f), 0, p.dims.grid_y);
-            x1 = clampi((int)((((pix + rf) + 16.0f) - 1.0f) / 16.0f), 0, p.dims.grid_x);
-            fy1 = clampi((int)((((piy + rf) + 16.0f) - 1.0f) / 16.0f), 0, p.dims.grid_y);
             // (a tile-row band call: a Gaussian without a tile in the band is invisible, gsrast_amd.h)
-            fy0 = clampi(fy0, p.dims.row_begin, p.dims.row_end);
-            fy1 = clampi(fy1, p.dims.row_begin, p.dims.row_end);
+            tile_rect(pix, piy, ri, ri, p.dims, x0, fy0, x1, fy1);
             has_tile = ri > 0 && (uint32_t)(x1 - x0) * (uint32_t)(fy1 - fy0) != 0;
         }
     }
@@ -270,7 +241,7 @@ __global__ __launch_bounds__(256) void preprocess_inria_kernel(const InriaParams
         out_radius = ri;
         out_tiles = (uint32_t)(x1 - x0) * (uint32_t)(y1 - y0);
         view_z = pvz;
-        out_rect = (uint32_t)x0 | ((uint32_t)(x1 - x0) << 8) | ((uint32_t)y0 << 16) | ((uint32_t)(y1 - y0) << 24);
+        out_rect = pack_rect(x0, y0, x1, y1);
     }
     p.radii[idx] = out_radius;
     p.tiles_touched[idx] = out_tiles;
@@ -285,36 +256,12 @@ __global__ __launch_bounds__(256) void preprocess_inria_kernel(const InriaParams
 int launch_preprocess_inria(const gsr_forward_args& a, const gsr_geometry_state& g, int32_t* radii, uint32_t* depth_keys,
                             uint32_t* rect_packed, const FrameDims& d, hipStream_t stream, uint4* wave_sums, uint32_t big_from) {
     InriaParams p;
-    p.n = a.num_gaussians;
+    fill_preprocess_params(p, a, g, radii, depth_keys, rect_packed, d, wave_sums, big_from);
     p.deg = a.sh_dims < 0 ? 0 : (a.sh_dims > 3 ? 3 : a.sh_dims);
-    p.means3D = reinterpret_cast<const float4*>(a.means3D);
-    p.scales = reinterpret_cast<const float4*>(a.scales);
-    p.scale_modifier = a.scale_modifier;
-    p.rotations = reinterpret_cast<const float4*>(a.rotations);
-    p.opacities = a.opacities;
-    p.shs = a.shs;
-    p.cov3D_precomp = a.cov3D_precomp;
-    p.colors_precomp = a.colors_precomp;
-    p.view = a.view_matrix;
-    p.proj = a.proj_matrix;
     p.cam_pos = a.cam_pos;
-    p.tan_fovx = a.tan_fovx;
-    p.tan_fovy = a.tan_fovy;
     p.focal_x = (float)a.width / (2.0f * a.tan_fovx);
     p.focal_y = (float)a.height / (2.0f * a.tan_fovy);
-    p.radii = radii;
-    p.means2D = reinterpret_cast<float2*>(g.means2D);
-    p.depths = g.depths;
-    p.cov3Ds = g.cov3D;
-    p.rgb = g.rgb;
     p.clamped = g.clamped;
-    p.conic_opacity = reinterpret_cast<float4*>(g.conic_opacity);
-    p.tiles_touched = g.tiles_touched;
-    p.depth_keys = depth_keys;
-    p.rect_packed = rect_packed;
-    p.wave_sums = wave_sums;
-    p.big_from = big_from;
-    p.dims = d;
     hipLaunchKernelGGL(preprocess_inria_kernel, dim3((unsigned)((a.num_gaussians + 255) / 256)), dim3(256), 0, stream, p);
     GSR_LAUNCH_CHECK("preprocess_inria_kernel");
     return GSR_OK;

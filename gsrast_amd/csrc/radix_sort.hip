@@ -280,14 +280,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(GSR_SO
     const uint32_t hist_c = (threadIdx.x < spec.nbins) ? digit_hist[threadIdx.x] : 0u;
     uint32_t live_bits = 0;                      // DROP: bit i = item i of this lane takes part
     if constexpr (DROP) {
-        const bool side_on = drop.side.words != nullptr && drop.side.words[0] != 0u;
+        const bool side_on = drop.side.words != nullptr && drop.side.words[kSideTaken] != 0u;
 #pragma unroll
         for (int i = 0; i < kItems; ++i) {
             const uint32_t local = (uint32_t)(wave * kWaveSpan + i * kWave + lane);
             bool live = local < valid && (uint32_t)key[i] != 0xFFFFFFFFu;
             if (live && side_on && ((uint32_t)key[i] >> 24) != drop.side.main_top) {
                 // (a handful per frame; any order: depth_side_kernel ranks them by key and index)
-                const uint32_t slot = atomicAdd(&drop.side.words[1], 1u);
+                const uint32_t slot = atomicAdd(&drop.side.words[kSideListed], 1u);
                 if (slot < drop.side.capacity) {
                     drop.side.keys[slot] = (uint32_t)key[i];
                     drop.side.vals[slot] = tile_base + local;
@@ -615,18 +615,18 @@ namespace {
 // How many distinct digits the top byte of the visible keys takes (one thread per digit; culled Gaussians'
 // 0xFFFFFFFF sentinels are compacted away before the histogram, so digit 255 is a real depth — the top byte
 // of a negative NaN, which passes the reference's frustum test — and counts like any other).
-// (out[4]: the frame's count of tiles with a list, accumulated later by the tile-range kernel, starts at zero here)
-// (host_top, may be null: mapped host memory that gets the count too — read by the host after an event, no copy command)
-// (side, may be null: the side list's words — [1] keys on it, [2] those of them below the main top byte; host_top[8] gets [2])
+// (out: sort_info; kInfoNonemptyTiles, the frame's count of tiles with a list, accumulated later by the tile-range kernel, starts at zero here)
+// (host, may be null: the pinned host block, which gets the count too — read by the host after an event, no copy command)
+// (side, may be null: the side list's words — kHostSideLo gets kSideBelow, kHostSideListed gets kSideListed)
 __global__ __launch_bounds__(256) void top_digit_count_kernel(const uint32_t* __restrict__ hist_top, uint32_t* __restrict__ out,
-                                                              uint32_t* __restrict__ host_top, const uint32_t* __restrict__ side) {
+                                                              uint32_t* __restrict__ host, const uint32_t* __restrict__ side) {
     const int c = __syncthreads_count(hist_top[threadIdx.x] != 0u);
     if (threadIdx.x == 0) {
-        out[0] = (uint32_t)c;
-        out[4] = 0u;
-        if (host_top) {
-            host_top[0] = (uint32_t)c;
-            if (side) { host_top[8] = side[2]; host_top[10] = side[1]; }     // (keys below the main top byte; keys the compaction PUT on the side list)
+        out[kInfoTopDigits] = (uint32_t)c;
+        out[kInfoNonemptyTiles] = 0u;
+        if (host) {
+            host[kHostTopDigits] = (uint32_t)c;
+            if (side) { host[kHostSideLo] = side[kSideBelow]; host[kHostSideListed] = side[kSideListed]; }     // (keys below the main top byte; keys the compaction PUT on the side list)
         }
     }
 }
@@ -718,7 +718,7 @@ __global__ __launch_bounds__(kCompactThreads) void visible_compact_kernel(const 
     // 1 024 words, and same-address atomics are served one at a time (about 17 ns each on this part).
     const uint32_t chunks = (n + kCompactChunk - 1) / kCompactChunk;
     // The side way (DepthSide): only the keys with the main top byte are compacted, with the offsets counted for them
-    const bool side_on = side.words != nullptr && side.words[0] != 0u;
+    const bool side_on = side.words != nullptr && side.words[kSideTaken] != 0u;
     if (side_on) partial = side.main_partial;
     for (uint32_t chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x) {
     const uint32_t base = chunk * kCompactChunk;
@@ -737,13 +737,13 @@ __global__ __launch_bounds__(kCompactThreads) void visible_compact_kernel(const 
         for (int r = 0; r < kCompactRows; ++r) {
             if (k[r] != 0xFFFFFFFFu && (k[r] >> 24) != side.main_top) {
                 const uint32_t e = base + (uint32_t)r * kCompactThreads + threadIdx.x;
-                const uint32_t slot = atomicAdd(&side.words[1], 1u);
+                const uint32_t slot = atomicAdd(&side.words[kSideListed], 1u);
                 if (slot < side.capacity) {              // (always: the scan counted them before it chose this way)
                     side.keys[slot] = k[r];
                     side.vals[slot] = e;
                     if (side.rects) side.rects[slot] = rect_by_index ? rect_by_index[e] : 0u;
                 }
-                if ((k[r] >> 24) < side.main_top) atomicAdd(&side.words[2], 1u);
+                if ((k[r] >> 24) < side.main_top) atomicAdd(&side.words[kSideBelow], 1u);
                 k[r] = 0xFFFFFFFFu;
             }
         }
@@ -842,7 +842,7 @@ __global__ __launch_bounds__(256) void depth_hist_kernel(const uint32_t* __restr
     for (int i = threadIdx.x; i < (3 + kByte2Copies) * 256; i += 256) lds[i] = 0;
     if (threadIdx.x == 0) s_below = 0;
     __syncthreads();
-    const bool side_on = side.words != nullptr && side.words[0] != 0u;
+    const bool side_on = side.words != nullptr && side.words[kSideTaken] != 0u;
     const int lane = threadIdx.x & (kWave - 1);
     const uint32_t vecs = (n + 3u) / 4u;
     uint32_t top_main = 0;                               // (wave-uniform) keys of this wave with the main top byte, side way
@@ -868,7 +868,7 @@ __global__ __launch_bounds__(256) void depth_hist_kernel(const uint32_t* __restr
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const bool vis = k[j] != 0xFFFFFFFFu && (!side_on || (k[j] >> 24) == side.main_top);
-                // (side way: the keys that will go to the side list and sort in FRONT of the stream — side.words[2], which the host reads)
+                // (side way: the keys that will go to the side list and sort in FRONT of the stream — side.words[kSideBelow], which the host reads)
                 if (side_on && k[j] != 0xFFFFFFFFu && (k[j] >> 24) < side.main_top) atomicAdd(&s_below, 1u);
                 if (vis) {
                     atomicAdd(&lds[k[j] & 255u], 1u);
@@ -890,7 +890,7 @@ __global__ __launch_bounds__(256) void depth_hist_kernel(const uint32_t* __restr
         else c = lds[512 + (i - 768)];
         if (c) atomicAdd(&hist[i], c);
     }
-    if (threadIdx.x == 0 && s_below) atomicAdd(&side.words[2], s_below);
+    if (threadIdx.x == 0 && s_below) atomicAdd(&side.words[kSideBelow], s_below);
 }
 }  // namespace
 
@@ -907,29 +907,27 @@ size_t depth_compact_scratch_bytes(size_t n) { return align_up(((n + kCompactChu
 
 // Depth keys of the visible Gaussians first (stable: index order), their count, the digit histograms of
 // the four sort passes, and (top_digits) the number of distinct top-byte digits: with at most one the
-// fourth pass would move nothing. info[0] = top_digits, info[1] = visible count (device words); info[4] is zeroed
-// (the frame's non-empty-tile counter; info must hold at least five words).
-int sort_u32_prepare(const uint32_t* keys_in, uint32_t n, uint32_t* out_k, uint32_t* out_v, uint32_t* partial,
-                     const SweepScratch* sc4, uint32_t* info, hipStream_t stream, bool offsets_ready,
-                     const uint32_t* rect_by_index, uint32_t* out_r, uint32_t* host_top, const DepthSide* side) {
+// fourth pass would move nothing. info (sort_info's words, shared_words.hpp): kInfoTopDigits = top_digits, kInfoVisible =
+// visible count; kInfoNonemptyTiles is zeroed (the frame's non-empty-tile counter).
+int sort_u32_prepare(const DepthPrepare& p, uint32_t n, hipStream_t stream) {
     if (n == 0) return GSR_OK;
     const uint32_t chunks = (n + kCompactChunk - 1) / kCompactChunk;
-    if (!offsets_ready) {
-        hipLaunchKernelGGL(visible_count_kernel, dim3(chunks), dim3(kCompactThreads), 0, stream, keys_in, n, partial);
+    if (!p.offsets_ready) {
+        hipLaunchKernelGGL(visible_count_kernel, dim3(chunks), dim3(kCompactThreads), 0, stream, p.keys_in, n, p.partial);
         GSR_LAUNCH_CHECK("visible_count_kernel");
-        hipLaunchKernelGGL(visible_scan_kernel, dim3(1), dim3(1024), 0, stream, partial, chunks, info + 1);
+        hipLaunchKernelGGL(visible_scan_kernel, dim3(1), dim3(1024), 0, stream, p.partial, chunks, p.info + kInfoVisible);
         GSR_LAUNCH_CHECK("visible_scan_kernel");
     }
-    if ((rect_by_index == nullptr) != (out_r == nullptr)) return GSR_ERR_INVALID_ARG;
+    if ((p.rect_by_index == nullptr) != (p.out.r == nullptr)) return GSR_ERR_INVALID_ARG;
     // (chunks per workgroup: bench frame, 1 425 chunks: 41 -> 32 us with two, no better with three to six; 50 M Gaussians,
     // 12 208 chunks: 288 -> 205 us with two to six)
     const uint32_t per_wg = chunks >= 4096u ? 4u : 2u;
     DepthSide no_side;
-    hipLaunchKernelGGL(visible_compact_kernel, dim3((chunks + per_wg - 1) / per_wg), dim3(kCompactThreads), 0, stream, keys_in, n, partial, rect_by_index,
-                       out_k, out_v, out_r, sc4[0].hist, side ? *side : no_side);
+    hipLaunchKernelGGL(visible_compact_kernel, dim3((chunks + per_wg - 1) / per_wg), dim3(kCompactThreads), 0, stream, p.keys_in, n, p.partial, p.rect_by_index,
+                       p.out.k, p.out.v, p.out.r, p.sc4[0].hist, p.side ? *p.side : no_side);
     GSR_LAUNCH_CHECK("visible_compact_kernel");
-    hipLaunchKernelGGL(top_digit_count_kernel, dim3(1), dim3(256), 0, stream, sc4[0].hist + 3 * 256, info, host_top,
-                       side ? side->words : nullptr);
+    hipLaunchKernelGGL(top_digit_count_kernel, dim3(1), dim3(256), 0, stream, p.sc4[0].hist + 3 * 256, p.info, p.host,
+                       p.side ? p.side->words : nullptr);
     GSR_LAUNCH_CHECK("top_digit_count_kernel");
     return GSR_OK;
 }
@@ -937,13 +935,13 @@ int sort_u32_prepare(const uint32_t* keys_in, uint32_t n, uint32_t* out_k, uint3
 // The same without the compaction (scenes beyond 16 M Gaussians): only the digit counts of the keys that take part; the first
 // pass then reads keys_in itself (sort_u32_passes with `drop_side`).
 int sort_u32_prepare_counts(const uint32_t* keys_in, uint32_t n, const SweepScratch* sc4, uint32_t* info, hipStream_t stream,
-                            uint32_t* host_top, const DepthSide* side) {
+                            uint32_t* host, const DepthSide* side) {
     if (n == 0) return GSR_OK;
     DepthSide no_side;
     const uint32_t wgs = std::min<uint32_t>((n + 4095u) / 4096u, 2048u);
     hipLaunchKernelGGL(depth_hist_kernel, dim3(wgs), dim3(256), 0, stream, keys_in, n, sc4[0].hist, side ? *side : no_side);
     GSR_LAUNCH_CHECK("depth_hist_kernel");
-    hipLaunchKernelGGL(top_digit_count_kernel, dim3(1), dim3(256), 0, stream, sc4[0].hist + 3 * 256, info, host_top,
+    hipLaunchKernelGGL(top_digit_count_kernel, dim3(1), dim3(256), 0, stream, sc4[0].hist + 3 * 256, info, host,
                        side ? side->words : nullptr);
     GSR_LAUNCH_CHECK("top_digit_count_kernel");
     return GSR_OK;
@@ -952,44 +950,39 @@ int sort_u32_prepare_counts(const uint32_t* keys_in, uint32_t n, const SweepScra
 // Passes [first, last) of the stable sort of n (key, value) u32 pairs: in -> a -> b -> a -> b. After P
 // passes the result is in (a_k, a_v) if P is odd, else in (b_k, b_v).
 // n_dev (may be null): the true key count on the device, n then being an upper bound that only sizes the grids.
-// second_in / a_s / b_s (all null, or none): a second value per key that takes the same path (in -> a -> b -> ...).
+// in.r / a.r / b.r (all null, or none): a second value per key that takes the same path (in -> a -> b -> ...).
 // rec_a / rec_b (both null, or none; with second values and first == 0 only): room for 3 n words each — the triples then travel
 // BETWEEN the passes as 12-byte records (in -> rec_a -> rec_b -> rec_a ...), and the LAST pass of the call writes the three
 // arrays of its turn (a_* / b_*) as without them. rec_a may overlap the arrays of the last pass's turn (dead by then), rec_b not.
-int sort_u32_passes(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t n, uint32_t* a_k, uint32_t* a_v, uint32_t* b_k,
-                    uint32_t* b_v, const SweepScratch* sc4, int first, int last, hipStream_t stream, const uint32_t* n_dev,
-                    const uint32_t* second_in, uint32_t* a_s, uint32_t* b_s, const DepthSide* drop_side, uint32_t* rec_a,
-                    uint32_t* rec_b) {
+int sort_u32_passes(const DepthPasses& ps, uint32_t n, hipStream_t stream) {
     if (n == 0) return GSR_OK;
-    if ((rec_a == nullptr) != (rec_b == nullptr) || (rec_a && (!second_in || first != 0))) return GSR_ERR_INVALID_ARG;
-    // drop_side (pass 0 only): keys_in is the per-Gaussian array of n keys with sentinels (sort_u32_prepare_counts); vals_in must
-    // be null, second_in the per-Gaussian second values, n_dev the number of keys that take part
-    if (drop_side && (vals_in || !second_in || !n_dev)) return GSR_ERR_INVALID_ARG;
-    for (int p = first; p < last; ++p) {
-        const uint32_t* src_k = (p == 0) ? keys_in : ((p % 2 == 1) ? a_k : b_k);
-        const uint32_t* src_v = (p == 0) ? vals_in : ((p % 2 == 1) ? a_v : b_v);
-        uint32_t* dst_k = (p % 2 == 0) ? a_k : b_k;
-        uint32_t* dst_v = (p % 2 == 0) ? a_v : b_v;
-        const uint32_t* src_s = second_in ? ((p == 0) ? second_in : ((p % 2 == 1) ? a_s : b_s)) : nullptr;
-        uint32_t* dst_s = second_in ? ((p % 2 == 0) ? a_s : b_s) : nullptr;
+    const bool seconds = ps.in.r != nullptr;
+    if ((ps.rec_a == nullptr) != (ps.rec_b == nullptr) || (ps.rec_a && (!seconds || ps.first != 0))) return GSR_ERR_INVALID_ARG;
+    // drop_side (pass 0 only): in.k is the per-Gaussian array of n keys with sentinels (sort_u32_prepare_counts); in.v must
+    // be null, in.r the per-Gaussian second values, n_dev the number of keys that take part
+    if (ps.drop_side && (ps.in.v || !seconds || !ps.n_dev)) return GSR_ERR_INVALID_ARG;
+    for (int p = ps.first; p < ps.last; ++p) {
+        DepthTriple src = (p == 0) ? ps.in : ((p % 2 == 1) ? ps.a : ps.b);
+        DepthTriple dst = (p % 2 == 0) ? ps.a : ps.b;
+        if (!seconds) src.r = dst.r = nullptr;
         int rec = 0;
-        if (rec_a) {
-            if (p > 0) { rec |= kRecIn; src_k = (p % 2 == 1) ? rec_a : rec_b; src_v = nullptr; }
-            if (p < last - 1) { rec |= kRecOut; dst_k = (p % 2 == 0) ? rec_a : rec_b; }
+        if (ps.rec_a) {
+            if (p > 0) { rec |= kRecIn; src.k = (p % 2 == 1) ? ps.rec_a : ps.rec_b; src.v = nullptr; }
+            if (p < ps.last - 1) { rec |= kRecOut; dst.k = (p % 2 == 0) ? ps.rec_a : ps.rec_b; }
         }
         DigitSpec spec;
         spec.mode = kDigitBits; spec.shift = 8 * p; spec.nbins = 256; spec.grid_x = 1; spec.inv_grid_x = 1.0f;
-        SweepScratch sc = sc4[p];
-        sc.error_word = sc4[0].error_word;
-        sc.error_value = sc4[0].error_value;
+        SweepScratch sc = ps.sc4[p];
+        sc.error_word = ps.sc4[0].error_word;
+        sc.error_value = ps.sc4[0].error_value;
         int rc;
-        if (p == 0 && drop_side) {
+        if (p == 0 && ps.drop_side) {
             DropSpec drop;
-            drop.n_out = n_dev;
-            drop.side = *drop_side;
-            rc = launch_pass<uint32_t>(src_k, nullptr, dst_k, dst_v, n, spec, sc4[0].hist, sc, stream, true, nullptr, src_s, dst_s, &drop, rec);
+            drop.n_out = ps.n_dev;
+            drop.side = *ps.drop_side;
+            rc = launch_pass<uint32_t>(src.k, nullptr, dst.k, dst.v, n, spec, ps.sc4[0].hist, sc, stream, true, nullptr, src.r, dst.r, &drop, rec);
         } else {
-            rc = launch_pass<uint32_t>(src_k, src_v, dst_k, dst_v, n, spec, sc4[0].hist + 256 * p, sc, stream, true, n_dev, src_s, dst_s,
+            rc = launch_pass<uint32_t>(src.k, src.v, dst.k, dst.v, n, spec, ps.sc4[0].hist + 256 * p, sc, stream, true, ps.n_dev, src.r, dst.r,
                                        nullptr, rec);
         }
         if (rc != GSR_OK) return rc;

@@ -130,8 +130,8 @@ __global__ __launch_bounds__(kScanThreads) void wave_sums_reduce_kernel(const ui
 // whether the scan's last element is the true total (a tile's own sum cannot wrap: 4096 elements of at most
 // 2^20 tiles each).
 // nonzero / nonzero_total (may be null): the per-tile non-zero counts become their exclusive prefix, the total goes out.
-// host_words (may be null): mapped host memory; [0] also gets the non-zero total, [2..3] (8-byte aligned) the 64-bit total —
-// the caller's host thread reads them after an event, without a copy command in between.
+// host_words (may be null): the pinned host block (shared_words.hpp); kHostVisible also gets the non-zero total, kHostTotal the
+// 64-bit total — the caller's host thread reads them after an event, without a copy command in between.
 __global__ __launch_bounds__(1024) void partial_scan_kernel(uint32_t* __restrict__ partial, size_t tiles,
                                                             unsigned long long* __restrict__ total64,
                                                             uint32_t* __restrict__ nonzero, uint32_t* __restrict__ nonzero_total,
@@ -194,20 +194,20 @@ __global__ __launch_bounds__(1024) void partial_scan_kernel(uint32_t* __restrict
     }
     const uint32_t carry_nz = total_z, carry_main = total_m;
     // main_count / side_words (depth order, radix_sort.hip): the keys whose top byte is not the main one go a side way when
-    // there are few of them. side_words[0] = 1 if so, [1] and [2] = 0 (the side list's counters), and the count the sort
-    // passes read (*nonzero_total) is then that of the main keys; host_words[0] keeps the count of ALL non-zero elements,
-    // host_words[6] = the side flag, host_words[8] = how many keys go the side way.
+    // there are few of them. side_words[kSideTaken] = 1 if so, the side list's two counters = 0, and the count the sort
+    // passes read (*nonzero_total) is then that of the main keys; kHostVisible keeps the count of ALL non-zero elements,
+    // kHostSideWay = the side flag, kHostSideCounted = how many keys go the side way.
     if (nonzero && threadIdx.x == 0) {
         uint32_t stream = carry_nz, side = 0u;
         if (main_count) {
             const uint32_t others = carry_nz - carry_main;
             side = (carry_main != 0u && others != 0u && others <= side_max) ? 1u : 0u;
             if (side) stream = carry_main;
-            side_words[0] = side; side_words[1] = 0u; side_words[2] = 0u;
-            if (host_words) { host_words[6] = side; host_words[8] = side ? others : 0u; }
+            side_words[kSideTaken] = side; side_words[kSideListed] = 0u; side_words[kSideBelow] = 0u;
+            if (host_words) { host_words[kHostSideWay] = side; host_words[kHostSideCounted] = side ? others : 0u; }
         }
         *nonzero_total = stream;
-        if (host_words) host_words[0] = carry_nz;
+        if (host_words) host_words[kHostVisible] = carry_nz;
     }
     if (total64) {
 #pragma unroll
@@ -220,8 +220,8 @@ __global__ __launch_bounds__(1024) void partial_scan_kernel(uint32_t* __restrict
             for (int w = 0; w < 1024 / kWave; ++w) { t += wide_sums[w]; tb += big_sums[w]; }
             *total64 = t;
             if (host_words) {
-                *reinterpret_cast<unsigned long long*>(host_words + 2) = t;
-                if (big) *reinterpret_cast<unsigned long long*>(host_words + 10) = tb;      // (the instances of splats of big_from tiles and more)
+                *reinterpret_cast<unsigned long long*>(host_words + kHostTotal) = t;
+                if (big) *reinterpret_cast<unsigned long long*>(host_words + kHostBigInstances) = tb;      // (the instances of splats of big_from tiles and more)
             }
         }
     }
@@ -267,30 +267,30 @@ size_t scan_temp_bytes(size_t n) {
     return ((tiles + 1) * sizeof(uint32_t) + 127) / 128 * 128;
 }
 
-int launch_inclusive_scan(const uint32_t* in, uint32_t* out, size_t n, char* temp, hipStream_t stream,
-                          unsigned long long* total64, uint32_t* nonzero, uint32_t* nonzero_total, uint32_t* host_words,
-                          void* clear, size_t clear_bytes, const uint4* wave_sums, uint32_t* main_count,
-                          uint32_t side_max, uint32_t* side_words, uint32_t* big, uint32_t big_from) {
+int launch_inclusive_scan(const uint32_t* in, uint32_t* out, size_t n, char* temp, hipStream_t stream, const ScanByproducts& by) {
     if (n == 0) return GSR_OK;
     const size_t tiles = (n + kScanTile - 1) / kScanTile;
     uint32_t* partial = reinterpret_cast<uint32_t*>(temp);
-    if (clear_bytes % 16 != 0 || (reinterpret_cast<uintptr_t>(clear) & 15) != 0 || (host_words && !total64)) return GSR_ERR_INVALID_ARG;
-    if ((wave_sums != nullptr) != (main_count != nullptr) || (main_count && (!nonzero || !side_words || !big))) return GSR_ERR_INVALID_ARG;
-    if (big && !host_words) return GSR_ERR_INVALID_ARG;
-    if (wave_sums) {
+    if (by.clear_bytes % 16 != 0 || (reinterpret_cast<uintptr_t>(by.clear) & 15) != 0 || ((by.host || by.nonzero) && !by.info)) return GSR_ERR_INVALID_ARG;
+    if ((by.wave_sums != nullptr) != (by.main_count != nullptr) || (by.main_count && (!by.nonzero || !by.big))) return GSR_ERR_INVALID_ARG;
+    if (by.big && !by.host) return GSR_ERR_INVALID_ARG;
+    uint4* const clear = reinterpret_cast<uint4*>(by.clear);
+    const size_t clear_vecs = clear ? by.clear_bytes / 16 : (size_t)0;
+    if (by.wave_sums) {
         // (the preprocess has left the sums of every 64 elements: big_from is the one IT was given)
         constexpr unsigned kTilesPerGroup = kScanThreads / kWave;
         hipLaunchKernelGGL(wave_sums_reduce_kernel, dim3((unsigned)((tiles + kTilesPerGroup - 1) / kTilesPerGroup)), dim3(kScanThreads), 0, stream,
-                           wave_sums, (n + kWave - 1) / kWave, tiles, partial, nonzero, reinterpret_cast<uint4*>(clear),
-                           clear ? clear_bytes / 16 : (size_t)0, main_count, big);
+                           by.wave_sums, (n + kWave - 1) / kWave, tiles, partial, by.nonzero, clear, clear_vecs, by.main_count, by.big);
         GSR_LAUNCH_CHECK("wave_sums_reduce_kernel");
     } else {
-        hipLaunchKernelGGL(tile_reduce_kernel, dim3((unsigned)tiles), dim3(kScanThreads), 0, stream, in, n, partial, nonzero,
-                           reinterpret_cast<uint4*>(clear), clear ? clear_bytes / 16 : (size_t)0, big, big_from);
+        hipLaunchKernelGGL(tile_reduce_kernel, dim3((unsigned)tiles), dim3(kScanThreads), 0, stream, in, n, partial, by.nonzero,
+                           clear, clear_vecs, by.big, by.big_from);
         GSR_LAUNCH_CHECK("tile_reduce_kernel");
     }
-    hipLaunchKernelGGL(partial_scan_kernel, dim3(1), dim3(1024), 0, stream, partial, tiles, total64, nonzero, nonzero_total, host_words,
-                       main_count, side_max, side_words, big);
+    uint32_t* const no_word = nullptr;
+    hipLaunchKernelGGL(partial_scan_kernel, dim3(1), dim3(1024), 0, stream, partial, tiles,
+                       by.info ? reinterpret_cast<unsigned long long*>(by.info + kInfoTotal) : nullptr, by.nonzero,
+                       by.info ? by.info + kInfoVisible : no_word, by.host, by.main_count, by.side_max, by.info ? by.info + kInfoSide : no_word, by.big);
     GSR_LAUNCH_CHECK("partial_scan_kernel");
     hipLaunchKernelGGL(tile_scan_kernel, dim3((unsigned)tiles), dim3(kScanThreads), 0, stream, in, out, n, partial);
     GSR_LAUNCH_CHECK("tile_scan_kernel");

@@ -317,7 +317,7 @@ def test_forward_only_calls_may_skip_the_sorted_lists():
 
 
 def test_plan_and_blend_feed_follow_the_instances_per_visible_gaussian():
-    """The default choices (csrc/api.hip): the block plan from 6 instances per VISIBLE Gaussian up, or with an eighth of the
+    """The default choices (csrc/frame_policy.hpp, choose_binning): the block plan from 6 instances per VISIBLE Gaussian up, or with an eighth of the
     instances in splats of 256 tiles and more; under it a blend that does not run beside the emission reads the sorted lists
     on sparse frames (fewer than 48 per visible Gaussian) and the block lists on dense ones. Whatever is chosen, pixels,
     finalT, nContrib, ranges, R and R_f are those of every other choice."""
