@@ -1,7 +1,7 @@
 """ctypes front-end of the C++ oracle (oracle/gsr_oracle.cpp).
 
 TEST INFRASTRUCTURE: importable only from tests/, __graft_entry__.smoke() and
-bench.py's cpu_baseline leg. Parity is unpinned by the reference (see the .cpp header).
+bench.py's cpu_baseline leg. What pins it to the reference is in the .cpp header.
 """
 from __future__ import annotations
 
@@ -63,12 +63,15 @@ def hardware_concurrency() -> int:
 
 def forward(scene: dict, cam, background=(0.0, 0.0, 0.0), use_rects: bool = True, scale_modifier: float = 1.0,
             threads: int = 1, out_init: np.ndarray | None = None, timings: dict | None = None,
-            contract: bool = False) -> dict:
+            contract: bool = False, colors_precomp: np.ndarray | None = None,
+            cov3d_precomp: np.ndarray | None = None) -> dict:
     """Runs the whole reference pipeline (GSCuda.cu:695-811) on the CPU and returns every
     intermediate: GeometryState arrays, rects, keys/values (unsorted and sorted), tile
     ranges, the planar image, finalT, nContrib, R (num_rendered) and R_f (records staged).
     Arrays the reference leaves unwritten keep their zero initialisation.
-    contract=True runs the build with fused multiply-adds allowed (contraction sensitivity study only)."""
+    contract=True runs the build with fused multiply-adds allowed (contraction sensitivity study only).
+    colors_precomp [N,3] / cov3d_precomp [N,6]: the reference's optional inputs (GSCuda.cu:315-318, :362, :803): rgb / cov3D
+    are then not written."""
     L = lib(contract)
     n = int(scene["means3D"].shape[0])
     W, H = cam.width, cam.height
@@ -78,6 +81,8 @@ def forward(scene: dict, cam, background=(0.0, 0.0, 0.0), use_rects: bool = True
     means, scales, rots, opac, shs = f32("means3D"), f32("scales"), f32("rotations"), f32("opacities"), f32("shs")
     view = np.ascontiguousarray(cam.view, dtype=np.float32)
     proj = np.ascontiguousarray(cam.proj, dtype=np.float32)
+    colors = None if colors_precomp is None else np.ascontiguousarray(colors_precomp, dtype=np.float32)
+    cov_in = None if cov3d_precomp is None else np.ascontiguousarray(cov3d_precomp, dtype=np.float32)
     o = {
         "radii": np.zeros(n, np.int32), "means2D": np.zeros((n, 2), np.float32),
         "depths": np.zeros(n, np.float32), "cov3D": np.zeros((n, 6), np.float32),
@@ -88,7 +93,7 @@ def forward(scene: dict, cam, background=(0.0, 0.0, 0.0), use_rects: bool = True
     t0 = time.perf_counter()
     R = int(L.gsro_preprocess_mt(
         ctypes.c_int(n), _p(means), _p(scales), ctypes.c_float(scale_modifier), _p(rots), _p(opac), _p(shs),
-        None, None, _p(view), _p(proj), ctypes.c_int(W), ctypes.c_int(H),
+        _p(cov_in), _p(colors), _p(view), _p(proj), ctypes.c_int(W), ctypes.c_int(H),
         ctypes.c_float(cam.tan_fovx), ctypes.c_float(cam.tan_fovy),
         _p(o["radii"]), _p(o["means2D"]), _p(o["depths"]), _p(o["cov3D"]), _p(o["rgb"]),
         _p(o["conicOpacity"]), _p(o["tilesTouched"]), _p(o["rects"]), _p(o["pointOffsets"]), ctypes.c_int(threads)))
@@ -114,7 +119,8 @@ def forward(scene: dict, cam, background=(0.0, 0.0, 0.0), use_rects: bool = True
                       _p(o["ranges"]), ctypes.c_int(threads))
         t2 = time.perf_counter()
         o["records_staged"] = int(L.gsro_blend(
-            ctypes.c_int(W), ctypes.c_int(H), _p(o["ranges"]), _p(o["values"]), _p(o["means2D"]), _p(o["rgb"]),
+            ctypes.c_int(W), ctypes.c_int(H), _p(o["ranges"]), _p(o["values"]), _p(o["means2D"]),
+            _p(o["rgb"] if colors is None else colors),
             _p(o["conicOpacity"]), _p(bg), _p(o["finalT"]), _p(o["nContrib"]), _p(o["out_color"]),
             ctypes.c_int(threads)))
         t3 = time.perf_counter()

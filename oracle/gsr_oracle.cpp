@@ -4,11 +4,17 @@
 // the timed, non-target CPU baseline. Nothing under gsrast_amd/ may link, import
 // or call it; only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg do.
 //
-// PARITY UNPINNED BY THE REFERENCE: 42yeah/GSRast ships no tests, golden vectors or
-// fixtures for this path and its CUDA/glm/CUB sources cannot be
-// built in this image (no nvcc, no glm). The oracle is therefore pinned only by
-// (i) an independent numpy restatement (oracle/oracle_np.py), (ii) closed-form
-// known-answer tests (tests/test_oracle_kat.py) and (iii) fixtures minted from (i).
+// PINNED TO THE REFERENCE'S OWN TEXT, COMPILED FOR THE HOST: oracle/build_ref.py compiles GSCuda.cu, AuxBuffer.cu and
+// CudaHelpers.cu with g++ under this file's flags, and tests/test_reference_pin.py requires every output of this file to
+// equal that library's byte for byte (48 frames; recorded ones in tests/golden/reference_frames.npz).
+//   by what:    the stand-ins of oracle/ref_host/ for the CUDA runtime, cooperative_groups, cub and glm — this project's own
+//               text; glm's operation orders are restated there as they are below, not glm's own code;
+//   not pinned: float -> int conversions that leave int or start from NaN (undefined on the host, saturating on the device:
+//               f2i below is then the only statement of the device's conversion); nvcc's FMA contraction (bounded only by the
+//               contraction study, oracle/Makefile); CUDA's expf against glibc's; the upstream profile (no source in the
+//               reference tree); the reference's caller GSGaussians.cpp and its .ply loader.
+// Beside that: an independent numpy restatement (oracle/oracle_np.py, pinned the same way) and closed-form known-answer
+// tests (tests/test_oracle_kat.py).
 //
 // Every function cites the reference lines it follows, relative to
 // /root/reference/apps/gsrast/gscuda/.  Arithmetic is scalar float32 in the

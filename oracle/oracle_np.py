@@ -4,7 +4,9 @@ TEST INFRASTRUCTURE (same rules as gsr_oracle.cpp). Written from SURVEY.md §8(a
 (rows a3-a11, citing apps/gsrast/gscuda/GSCuda.cu), vectorised over Gaussians and over
 the pixels of a tile, so it shares no code or loop structure with the scalar C++
 oracle. Its job is to cross-check that oracle (integers exactly, floats to 1e-6) and
-to mint the golden fixtures under tests/golden/. Parity is unpinned by the reference.
+to mint the golden fixture tests/golden/config1.npz. Pinned, like that oracle, byte for byte to the reference's own text compiled
+for the host (tests/test_reference_pin.py, with exp=cpu_oracle.expf: libm's exponential); what that does not pin is listed at
+the top of gsr_oracle.cpp.
 """
 from __future__ import annotations
 
@@ -62,8 +64,9 @@ def _rect(px, py, ex, ey, gx, gy):
     return x0.astype(np.uint32), y0.astype(np.uint32), x1.astype(np.uint32), y1.astype(np.uint32)
 
 
-def preprocess(scene, cam, scale_modifier=1.0, use_rects=True):
-    """Rows a3-a7 (GSCuda.cu:261-375, :771)."""
+def preprocess(scene, cam, scale_modifier=1.0, use_rects=True, colors_precomp=None, cov3d_precomp=None):
+    """Rows a3-a7 (GSCuda.cu:261-375, :771). colors_precomp / cov3d_precomp: the reference's optional inputs (:315-318,
+    :362): cov3D / rgb are then not written (zeros here)."""
     with np.errstate(all="ignore"):
         means = scene["means3D"].astype(F)
         n = means.shape[0]
@@ -93,6 +96,8 @@ def preprocess(scene, cam, scale_modifier=1.0, use_rects=True):
         RS = _mm3(R, S)
         sig = _mm3(RS, _tr3(RS))
         cov3d = np.stack([sig[(0, 0)], sig[(1, 0)], sig[(2, 0)], sig[(1, 1)], sig[(2, 1)], sig[(2, 2)]], axis=1)
+        if cov3d_precomp is not None:
+            cov3d = np.asarray(cov3d_precomp, F)
 
         # a5: covariance in 2D
         mv = means.copy()
@@ -136,10 +141,11 @@ def preprocess(scene, cam, scale_modifier=1.0, use_rects=True):
         o = {
             "radii": np.where(vis, _f2i(radius), 0).astype(np.int32),
             "tilesTouched": np.where(vis, area, 0).astype(np.uint32),
-            "cov3D": np.where(in_frustum[:, None], cov3d, F(0)),
+            "cov3D": np.where(in_frustum[:, None], cov3d, F(0)) if cov3d_precomp is None else np.zeros((n, 6), F),
             "rects": (np.where(has_det[:, None], np.stack([ex, ey], axis=1), 0).astype(np.int32)
                       if use_rects else None),
-            "rgb": np.where(vis[:, None], F(0.5) + F(0.4) * scene["shs"][:, :3].astype(F), F(0)),
+            "rgb": (np.where(vis[:, None], F(0.5) + F(0.4) * scene["shs"][:, :3].astype(F), F(0)) if colors_precomp is None
+                    else np.zeros((n, 3), F)),
             "depths": np.where(vis, prz, F(0)),
             "means2D": np.where(vis[:, None], np.stack([pix, piy], axis=1), F(0)),
             "conicOpacity": np.where(vis[:, None], np.concatenate(
@@ -187,7 +193,7 @@ def bin_and_sort(o, cam):
     return o
 
 
-def blend(o, cam, background=(0.0, 0.0, 0.0), out_init=None, t_cutoff=0.001, exp=np.exp):
+def blend(o, cam, background=(0.0, 0.0, 0.0), out_init=None, t_cutoff=0.001, exp=np.exp, colors=None):
     """Row a11 (GSCuda.cu:543-677): per tile, all 256 pixels advance together through
     the sorted list, one record at a time, with boolean masks for skip/done.
     exp: the float32 exponential (default numpy's, with which the committed fixture was minted; cpu_oracle.expf is libm's,
@@ -195,6 +201,7 @@ def blend(o, cam, background=(0.0, 0.0, 0.0), out_init=None, t_cutoff=0.001, exp
     W, H = cam.width, cam.height
     gx, gy = (W + 15) // 16, (H + 15) // 16
     bg = np.asarray(background, dtype=F)
+    colors = o["rgb"] if colors is None else np.asarray(colors, F)       # GSCuda.cu:803
     out = np.zeros((3, H, W), F) if out_init is None else np.array(out_init, dtype=F)
     finalT = np.zeros((H, W), F)
     ncontrib = np.zeros((H, W), np.uint32)
@@ -227,7 +234,7 @@ def blend(o, cam, background=(0.0, 0.0, 0.0), out_init=None, t_cutoff=0.001, exp
                         g = int(o["values"][k])
                         act = ~done
                         contrib[act] += 1
-                        gxy, con, rgb = o["means2D"][g], o["conicOpacity"][g], o["rgb"][g]
+                        gxy, con, rgb = o["means2D"][g], o["conicOpacity"][g], colors[g]
                         dx, dy = gxy[0] - fx, gxy[1] - fy
                         power = F(-0.5) * (con[0] * dx * dx + con[2] * dy * dy) - con[1] * dx * dy
                         alpha = np.minimum(F(0.99), con[3] * exp(power))
@@ -248,8 +255,9 @@ def blend(o, cam, background=(0.0, 0.0, 0.0), out_init=None, t_cutoff=0.001, exp
     return dict(out_color=out, finalT=finalT, nContrib=ncontrib, records_staged=staged)
 
 
-def forward(scene, cam, background=(0.0, 0.0, 0.0), use_rects=True, scale_modifier=1.0, out_init=None):
-    o = preprocess(scene, cam, scale_modifier, use_rects)
+def forward(scene, cam, background=(0.0, 0.0, 0.0), use_rects=True, scale_modifier=1.0, out_init=None, exp=np.exp,
+            colors_precomp=None, cov3d_precomp=None):
+    o = preprocess(scene, cam, scale_modifier, use_rects, colors_precomp, cov3d_precomp)
     if o["num_rendered"] > 0:
         bin_and_sort(o, cam)
     else:
@@ -257,6 +265,6 @@ def forward(scene, cam, background=(0.0, 0.0, 0.0), use_rects=True, scale_modifi
         o.update(keys_unsorted=np.zeros(0, np.uint64), values_unsorted=np.zeros(0, np.uint32),
                  keys=np.zeros(0, np.uint64), values=np.zeros(0, np.uint32),
                  ranges=np.zeros((gx * gy, 2), np.uint32))
-    o.update(blend(o, cam, background, out_init))
+    o.update(blend(o, cam, background, out_init, exp=exp, colors=colors_precomp))
     o.pop("_rect", None)
     return o

@@ -4,7 +4,8 @@
 The reference's depth test is an atomicMin followed by an unordered colour write, so with several
 points on one pixel its image is timing dependent; this restatement (like the HIP path) takes the
 nearest point and, among equal depths, the lowest index — one of the reference's possible outcomes.
-Parity unpinned by the reference (no tests, never called)."""
+Pinned byte for byte to gscuda::forwardPoints compiled for the host, whose threads run in index order: this rule
+(tests/test_reference_pin.py::test_forward_points_against_the_numpy_restatement)."""
 import numpy as np
 
 F = np.float32

@@ -1,11 +1,12 @@
 """Mints tests/golden/config1.npz: BASELINE config 1 (1000 isotropic Gaussians, 128x128,
 reference default camera) inputs plus every intermediate and the image.
 
-Expected values come from the numpy restatement (oracle/oracle_np.py); the script refuses to
+Expected values come from the numpy restatement (oracle/oracle_np.py, numpy's float32 exp); the script refuses to
 write the file unless the independent C++ oracle agrees (integers exactly, floats to 1e-6).
-Neither is the reference itself — 42yeah/GSRast has no tests or vectors for this path and
-cannot be built here — so the fixture pins this repo's two restatements against each other,
-not against reference output. Run from the repo root:  python tests/golden/make_golden.py
+Neither is the reference itself: outputs recorded from the reference's own text compiled for the host are in
+tests/golden/reference_frames.npz (make_reference_frames.py), and tests/test_reference_pin.py holds both restatements to that
+binary byte for byte on this very scene (with libm's expf; out-of-range conversions, FMA contraction and CUDA's expf are
+not pinned by a host build). Run from the repo root:  python tests/golden/make_golden.py
 """
 import os
 import sys
