@@ -68,14 +68,97 @@ def assert_blend_parity(img, final_t, n_contrib, exp, what="", bitwise_t=True):
     return max_err
 
 
-def check_backward_chain(got, g, scene, cam, w, h, ids, upstream=None, tol_scale=1.0):
-    """gsr_backward's per-Gaussian chain (cov2D -> cov3D -> scales / rotations, pixel centre and Jacobian -> means3D)
-    for the Gaussians `ids`, against oracle/backward_np.py fed with the GPU's own upstream gradients — or, with `upstream`
-    (dict: dL_dmean2D, dL_dconic_opacity, dL_dcov2D indexable like `got`), with sums computed independently of the GPU: an
-    end-to-end check. `got`: the gradient arrays (numpy, full size or indexable by id), `g`: geometry state arrays (cov3D),
-    `scene`: host inputs. Returns the largest expected magnitude of (dL_dcov3D, dL_dmeans3D, dL_dscales, dL_drotations)."""
+def _rotate_about(v, axis, angle):
+    """Rodrigues: v turned by `angle` about the unit vector `axis` (float64)."""
+    v, k = np.asarray(v, np.float64), np.asarray(axis, np.float64)
+    return v * np.cos(angle) + np.cross(k, v) * np.sin(angle) + k * (k @ v) * (1.0 - np.cos(angle))
+
+
+def posed_camera(w, h, eye, target=(0.0, 0.0, 0.0), roll=0.0, kx=1.0, near=0.05, far=50.0):
+    """A camera at `eye` looking at `target`, rolled by `roll` about its viewing direction, prepared as
+    camera.first_person_camera prepares its arguments: proj = perspective . view in float32, then row 2 of the view matrix
+    negated, both column-major. The up vector is (0, -1, 0) turned by `roll` about the viewing direction. kx: non-square
+    pixels as in test_non_square_pixels_use_both_focal_lengths — tan_fovx = kx tan_fovy W / H with the matching projection,
+    so focal_x / focal_y = 1 / kx. The rotation block of the view matrix must not be symmetric (max |R - R^T| > 0.1):
+    under a symmetric one a transposed index in the backward chain changes nothing, and a test through this camera is blind."""
+    import math
+    from gsrast_amd import camera
+    F = np.float32
+    fov = math.radians(45.0)
+    eye = np.asarray(eye, F).reshape(3)
+    target = np.broadcast_to(np.asarray(target, F), (3,))
+    front = (target - eye).astype(np.float64)
+    front /= np.linalg.norm(front)
+    up = _rotate_about((0.0, -1.0, 0.0), front, roll).astype(F)
+    view = camera.look_at(eye, target, up)
+    aspect = F(w) / F(h) * F(kx)
+    proj = (camera.perspective(fov, aspect, near, far) @ view).astype(F)
+    view = view.copy()
+    view[2, :] *= F(-1.0)
+    tan_y = float(F(math.tan(F(fov) * F(0.5))))
+    cam = Camera(view=np.ascontiguousarray(view.T).reshape(16).copy(), proj=np.ascontiguousarray(proj.T).reshape(16).copy(),
+                 cam_pos=eye.copy(), tan_fovx=float(F(tan_y) * aspect), tan_fovy=tan_y, width=w, height=h)
+    R = view[:3, :3].astype(np.float64)
+    assert np.abs(R - R.T).max() > 0.1, ("the pose's rotation block is (nearly) symmetric", R)
+    return cam
+
+
+def view_rotation(cam):
+    """The rotation block R of cam.view (t = R m + T), float64 [3,3]."""
+    return np.asarray(cam.view, np.float64).reshape(4, 4).T[:3, :3].copy()
+
+
+def view_from_world(cam, m):
+    """t = V (m, 1) in float64: the view-space position computeCov2D clamps. m [n,3] -> [n,3]."""
+    V = np.asarray(cam.view, np.float64).reshape(4, 4).T
+    return np.asarray(m, np.float64).reshape(-1, 3) @ V[:3, :3].T + V[:3, 3]
+
+
+def world_from_view(cam, t):
+    """The world positions [n,3] (float64) whose view-space positions under cam.view are t [n,3]: scenes placed relative to
+    the frustum of a rotated camera."""
+    V = np.asarray(cam.view, np.float64).reshape(4, 4).T
+    return np.linalg.solve(V[:3, :3], (np.asarray(t, np.float64).reshape(-1, 3) - V[:3, 3]).T).T
+
+
+def with_transposed_rotation(cam):
+    """cam with the rotation block of its view matrix transposed: the reference input of a fault that indexes the view
+    matrix the wrong way round (blindness guards)."""
+    import dataclasses
+    V = np.asarray(cam.view, np.float32).reshape(4, 4).T.copy()
+    V[:3, :3] = V[:3, :3].T.copy()
+    return dataclasses.replace(cam, view=np.ascontiguousarray(V.T).reshape(16).copy())
+
+
+def _rows_differ(e, f, tol):
+    """Per row: does f differ from e by more than tol of the row's own largest component (floored as the chain checks
+    floor it, at 1e-3 of the largest over all rows)?"""
+    if len(e) == 0:
+        return np.zeros(0, bool)
+    mag = np.maximum(np.abs(e).max(1), 1e-3 * np.abs(e).max())
+    return np.abs(f - e).max(1) > tol * np.maximum(mag, 1e-30)
+
+
+CHAIN_TOL = {"dL_dcov3D": 2e-3, "dL_dmeans3D": 3e-3, "dL_dscales": 3e-3, "dL_drotations": 3e-3, "dL_dshs": 1e-4}
+
+
+def chain_seen(exp, faulted, factor=10.0, tol_scale=1.0):
+    """bool[len(ids)]: the Gaussians on which a reference computed from faulted inputs (`faulted`, keyed like `exp`: the
+    dicts of backward_chain_expected*) differs from the true one by more than `factor` times the chain check's tolerance in
+    some array, measured on the Gaussian's own largest component — where the chain check would see that fault."""
+    seen = None
+    for k, e in exp.items():
+        d = _rows_differ(e, faulted[k], factor * CHAIN_TOL[k] * tol_scale)
+        seen = d if seen is None else (seen | d)
+    return seen
+
+
+def backward_chain_expected(got, g, scene, cam, w, h, ids, upstream=None, scale_modifier=1.0, no_clamp=False):
+    """The float64 expectation of check_backward_chain: dict dL_dcov3D [m,6], dL_dmeans3D [m,3], dL_dscales [m,3],
+    dL_drotations [m,4] for the Gaussians `ids`. no_clamp: the +-1.3 tan(fov) limits replaced by 1e9 (blindness guards)."""
     from oracle import backward_np as B
     focal = h / (2.0 * cam.tan_fovy)
+    tanx, tany = (1e9, 1e9) if no_clamp else (cam.tan_fovx, cam.tan_fovy)
     m = len(ids)
     exp_cov, exp_mean, exp_scale, exp_rot = np.zeros((m, 6)), np.zeros((m, 3)), np.zeros((m, 3)), np.zeros((m, 4))
     for j, i in enumerate(ids):
@@ -85,11 +168,25 @@ def check_backward_chain(got, g, scene, cam, w, h, ids, upstream=None, tol_scale
         dconic = up["dL_dconic_opacity"][i, :3].astype(np.float64)
         # (the chain starts from the summed dL/dcov2D where the call produced it: gsr_backward_args.dL_dcov2D)
         dcov = up["dL_dcov2D"][i].astype(np.float64) if "dL_dcov2D" in up else None
-        exp_cov[j] = B.conic_backward(c3, m3, cam.view, focal, cam.tan_fovx, cam.tan_fovy, dconic, dcov)
+        exp_cov[j] = B.conic_backward(c3, m3, cam.view, focal, tanx, tany, dconic, dcov)
         exp_mean[j] = (B.project_mean2d_backward(m3, cam.proj, w, h, up["dL_dmean2D"][i].astype(np.float64)) +
-                       B.conic_backward_mean(c3, m3, cam.view, focal, cam.tan_fovx, cam.tan_fovy, dconic, dcov))
-        exp_scale[j], exp_rot[j] = B.cov3d_backward(scene["scales"][i, :3], scene["rotations"][i], 1.0,
+                       B.conic_backward_mean(c3, m3, cam.view, focal, tanx, tany, dconic, dcov))
+        exp_scale[j], exp_rot[j] = B.cov3d_backward(scene["scales"][i, :3], scene["rotations"][i], scale_modifier,
                                                     (got["dL_dcov3D"][i] if upstream is None else exp_cov[j]).astype(np.float64))
+    return {"dL_dcov3D": exp_cov, "dL_dmeans3D": exp_mean, "dL_dscales": exp_scale, "dL_drotations": exp_rot}
+
+
+def check_backward_chain(got, g, scene, cam, w, h, ids, upstream=None, tol_scale=1.0, scale_modifier=1.0, expected=None):
+    """gsr_backward's per-Gaussian chain (cov2D -> cov3D -> scales / rotations, pixel centre and Jacobian -> means3D)
+    for the Gaussians `ids`, against oracle/backward_np.py fed with the GPU's own upstream gradients — or, with `upstream`
+    (dict: dL_dmean2D, dL_dconic_opacity, dL_dcov2D indexable like `got`), with sums computed independently of the GPU: an
+    end-to-end check. `got`: the gradient arrays (numpy, full size or indexable by id), `g`: geometry state arrays (cov3D),
+    `scene`: host inputs. scale_modifier: that of the draw() and backward() calls. expected: the result of
+    backward_chain_expected for the same arguments, where the caller has it already. Returns the largest expected magnitude
+    of (dL_dcov3D, dL_dmeans3D, dL_dscales, dL_drotations)."""
+    m = len(ids)
+    exp = expected if expected is not None else backward_chain_expected(got, g, scene, cam, w, h, ids, upstream, scale_modifier)
+    exp_cov, exp_mean, exp_scale, exp_rot = (exp[k] for k in ("dL_dcov3D", "dL_dmeans3D", "dL_dscales", "dL_drotations"))
     ids = np.asarray(ids)
     # compared per Gaussian relative to its own magnitude (float32 outputs of a chain evaluated in double). End to end
     # (`upstream`): the rotation gradient of a nearly round splat is a difference of nearly equal products — it vanishes for a
@@ -108,38 +205,60 @@ def check_backward_chain(got, g, scene, cam, w, h, ids, upstream=None, tol_scale
     return [float(np.abs(e).max()) if m else 0.0 for e in (exp_cov, exp_mean, exp_scale, exp_rot)]
 
 
-def check_backward_chain_inria(got, g, scene, cam, w, h, ids, deg, clamped):
-    """The upstream profile's per-Gaussian chain for the Gaussians `ids` against oracle/backward_np.py (inria_*), fed with
-    the GPU's own upstream gradients. clamped: bool[N,3] of the forward call. Returns the largest expected magnitudes of
-    (dL_dcov3D, dL_dmeans3D, dL_dscales, dL_drotations, dL_dshs)."""
+def backward_chain_expected_inria(got, g, scene, cam, w, h, ids, deg, clamped, upstream=None, scale_modifier=1.0,
+                                  no_clamp=False, swap_focal=False):
+    """The float64 expectation of check_backward_chain_inria: dict dL_dcov3D, dL_dmeans3D, dL_dscales, dL_drotations,
+    dL_dshs [m,48]. no_clamp / swap_focal: faulted reference inputs (blindness guards) — the +-1.3 tan(fov) limits replaced
+    by 1e9; focal_x and focal_y exchanged."""
     from oracle import backward_np as B
     fx, fy = w / (2.0 * cam.tan_fovx), h / (2.0 * cam.tan_fovy)
+    if swap_focal:
+        fx, fy = fy, fx
+    tanx, tany = (1e9, 1e9) if no_clamp else (cam.tan_fovx, cam.tan_fovy)
     m = len(ids)
     exp_cov, exp_mean, exp_scale, exp_rot, exp_sh = np.zeros((m, 6)), np.zeros((m, 3)), np.zeros((m, 3)), np.zeros((m, 4)), np.zeros((m, 48))
+    up = got if upstream is None else upstream
     for j, i in enumerate(ids):
         c3 = g["cov3D"][i].astype(np.float64)
         m3 = scene["means3D"][i, :3].astype(np.float64)
-        dconic = got["dL_dconic_opacity"][i, :3].astype(np.float64)
-        dcov = got["dL_dcov2D"][i].astype(np.float64) if "dL_dcov2D" in got else None
-        exp_cov[j], g_mean_j = B.inria_conic_backward(c3, m3, cam.view, fx, fy, cam.tan_fovx, cam.tan_fovy, dconic, dcov)
-        g_sh, g_mean_c = B.inria_color_backward(m3, cam.cam_pos, scene["shs"][i].reshape(16, 3), deg, got["dL_dcolors"][i].astype(np.float64))
+        dconic = up["dL_dconic_opacity"][i, :3].astype(np.float64)
+        dcov = up["dL_dcov2D"][i].astype(np.float64) if "dL_dcov2D" in up else None
+        exp_cov[j], g_mean_j = B.inria_conic_backward(c3, m3, cam.view, fx, fy, tanx, tany, dconic, dcov)
+        g_sh, g_mean_c = B.inria_color_backward(m3, cam.cam_pos, scene["shs"][i].reshape(16, 3), deg, up["dL_dcolors"][i].astype(np.float64))
         # the oracle decides the clamp from its own float64 colour; the kernel uses the forward's flags: they must agree
         raw_negative = B.inria_color(m3, cam.cam_pos, scene["shs"][i].reshape(16, 3), deg) == 0.0
         assert (raw_negative == clamped[i]).all() or np.abs(g["rgb"][i]).min() < 1e-6
         exp_sh[j] = g_sh.reshape(48)
-        exp_mean[j] = (B.inria_project_mean2d_backward(m3, cam.proj, w, h, got["dL_dmean2D"][i].astype(np.float64)) + g_mean_j + g_mean_c)
-        exp_scale[j], exp_rot[j] = B.inria_cov3d_backward(scene["scales"][i, :3], scene["rotations"][i], 1.0,
-                                                          got["dL_dcov3D"][i].astype(np.float64))
+        exp_mean[j] = (B.inria_project_mean2d_backward(m3, cam.proj, w, h, up["dL_dmean2D"][i].astype(np.float64)) + g_mean_j + g_mean_c)
+        exp_scale[j], exp_rot[j] = B.inria_cov3d_backward(scene["scales"][i, :3], scene["rotations"][i], scale_modifier,
+                                                          (got["dL_dcov3D"][i] if upstream is None else exp_cov[j]).astype(np.float64))
+    return {"dL_dcov3D": exp_cov, "dL_dmeans3D": exp_mean, "dL_dscales": exp_scale, "dL_drotations": exp_rot, "dL_dshs": exp_sh}
+
+
+def check_backward_chain_inria(got, g, scene, cam, w, h, ids, deg, clamped, upstream=None, scale_modifier=1.0, expected=None):
+    """The upstream profile's per-Gaussian chain for the Gaussians `ids` against oracle/backward_np.py (inria_*), fed with
+    the GPU's own upstream gradients — or, with `upstream` (dict: dL_dmean2D, dL_dconic_opacity, dL_dcolors and optionally
+    dL_dcov2D, indexable like `got`), with sums computed independently of the GPU: end to end, under check_backward_chain's
+    tolerances for that case (the rotation gradient at ten times the others': see there; the SH gradient is B_k times the
+    colour sums, which the callers compare with the blend reference themselves: not repeated end to end). clamped: bool[N,3] of the forward call. scale_modifier: that of the draw() and
+    backward() calls. expected: the result of backward_chain_expected_inria for the same arguments, where the caller has
+    it already. Returns the largest expected magnitudes of (dL_dcov3D, dL_dmeans3D, dL_dscales, dL_drotations, dL_dshs)."""
+    m = len(ids)
+    exp = expected if expected is not None else backward_chain_expected_inria(got, g, scene, cam, w, h, ids, deg, clamped, upstream,
+                                                                              scale_modifier)
+    exp_cov, exp_mean, exp_scale, exp_rot, exp_sh = (exp[k] for k in ("dL_dcov3D", "dL_dmeans3D", "dL_dscales", "dL_drotations", "dL_dshs"))
     ids = np.asarray(ids)
     for name, e, gotv, tol in (("dL_dcov3D", exp_cov, got["dL_dcov3D"][ids], 2e-3),
                                ("dL_dmeans3D", exp_mean, got["dL_dmeans3D"][ids][:, :3], 3e-3),
                                ("dL_dscales", exp_scale, got["dL_dscales"][ids][:, :3], 3e-3),
-                               ("dL_drotations", exp_rot, got["dL_drotations"][ids], 3e-3),
+                               ("dL_drotations", exp_rot, got["dL_drotations"][ids], 3e-3 if upstream is None else 3e-2),
                                ("dL_dshs", exp_sh, got["dL_dshs"][ids], 1e-4)):
-        if m == 0:
+        if m == 0 or (upstream is not None and name == "dL_dshs"):
             continue
         err = np.abs(gotv - e).max(1)
         mag = np.maximum(np.abs(e).max(1), 1e-3 * np.abs(e).max())
+        if upstream is not None:
+            print(f"[backward] end to end (upstream profile), {name}: worst error {float((err / np.maximum(mag, 1e-30)).max()):.2e} of the Gaussian's own largest component")
         assert (err <= tol * np.maximum(mag, 1e-30)).all(), (name, float((err / np.maximum(mag, 1e-30)).max()))
     return [float(np.abs(e).max()) if m else 0.0 for e in (exp_cov, exp_mean, exp_scale, exp_rot, exp_sh)]
 

@@ -2,6 +2,7 @@
 functions it differentiates — the float64 restatement of the reference's blend loop (GSCuda.cu:623-676) and
 of computeCov2D + conic (GSCuda.cu:197-231, :329-335). The reference has no backward pass to compare with."""
 import numpy as np
+import pytest
 
 from oracle import backward_np as B
 
@@ -59,10 +60,37 @@ def test_background_and_empty_tiles():
     assert np.abs(g["dL_dcolor"] - fd).max() <= 1e-6 * max(1.0, np.abs(fd).max())
 
 
-def test_cov3d_to_conic_gradient_matches_finite_differences():
-    rng = np.random.default_rng(5)
+def _camera(pose, w=640, h=480, kx=1.0):
+    """default: camera.default_camera — yaw 0, pitch 0, no roll, whose rotation block is diag(1, -1, 1); posed: a rotated and
+    rolled one, whose rotation block is not symmetric (helpers.posed_camera asserts it), so that a transposed index or a
+    dropped off-diagonal product in the oracle would show."""
     from gsrast_amd import camera
-    cam = camera.default_camera(640, 480)
+    from helpers import posed_camera
+    if pose == "default":
+        assert kx == 1.0
+        return camera.default_camera(w, h)
+    return posed_camera(w, h, eye=(2.0, -1.2, -4.2), target=0.0, roll=0.4, kx=kx)
+
+
+def _clamp_state(cam, mean3):
+    """(t.x / t.z clamped, t.y / t.z clamped) of computeCov2D for the world position mean3, float64."""
+    from helpers import view_from_world
+    t = view_from_world(cam, mean3)[0]
+    assert t[2] > 0.2
+    return abs(t[0] / t[2]) > 1.3 * cam.tan_fovx, abs(t[1] / t[2]) > 1.3 * cam.tan_fovy
+
+
+def test_cov3d_to_conic_gradient_matches_finite_differences():
+    _cov3d_to_conic_gradient(pose="default")
+
+
+def test_cov3d_to_conic_gradient_matches_finite_differences_under_a_rotated_pose():
+    _cov3d_to_conic_gradient(pose="posed")
+
+
+def _cov3d_to_conic_gradient(pose):
+    rng = np.random.default_rng(5)
+    cam = _camera(pose)
     focal = 480 / (2.0 * cam.tan_fovy)
     for _ in range(6):
         a = rng.normal(size=(3, 3)) * 0.2
@@ -78,14 +106,26 @@ def test_cov3d_to_conic_gradient_matches_finite_differences():
 
 def test_input_chain_gradients_match_finite_differences():
     """means3D -> pixel centre, (scale, rotation) -> cov3D, means3D -> conic (through the Jacobian)."""
+    _input_chain_gradients(pose="default")
+
+
+def test_input_chain_gradients_match_finite_differences_under_a_rotated_pose():
+    _input_chain_gradients(pose="posed")
+
+
+def _input_chain_gradients(pose):
+    from helpers import world_from_view
     rng = np.random.default_rng(11)
-    from gsrast_amd import camera
-    cam = camera.default_camera(640, 480)
+    cam = _camera(pose)
     focal = 480 / (2.0 * cam.tan_fovy)
     for trial in range(8):
         mean3 = rng.uniform(-1.5, 1.5, 3)
         if trial >= 6:
-            mean3 = np.array([9.0, -7.0, 0.5])            # far off axis: t.x / t.z and t.y / t.z are clamped
+            # far off axis: t.x / t.z and t.y / t.z are clamped (placed in view space, so under either pose)
+            mean3 = world_from_view(cam, [[9.0, 7.0, 5.5]])[0]
+            assert _clamp_state(cam, mean3) == (True, True)
+            if pose == "default":
+                assert np.abs(mean3 - (9.0, -7.0, 0.5)).max() < 1e-5
         scale, rot = np.exp(rng.uniform(-3, -1, 3)), rng.normal(size=4)
         g2, g6, gk = rng.normal(size=2), rng.normal(size=6), rng.normal(size=3)
         fd = B.finite_difference(lambda m: float(B.project_mean2d(m, cam.proj, 640, 480) @ g2), mean3, 1e-6)
@@ -100,6 +140,45 @@ def test_input_chain_gradients_match_finite_differences():
                                   mean3, 1e-6)
         anm = B.conic_backward_mean(c3, mean3, cam.view, focal, cam.tan_fovx, cam.tan_fovy, gk)
         assert np.abs(anm - fdm).max() <= 2e-5 * max(1.0, np.abs(fdm).max()), (trial, anm, fdm)
+
+
+@pytest.mark.parametrize("kx", [1.0, 1.7])
+def test_upstream_profile_chain_under_a_rotated_pose(kx):
+    """The upstream profile's camera-dependent functions (inria_conic_backward: covariance and Jacobian; the pixel centre)
+    under the rotated pose, with square pixels and with focal_x = focal_y / 1.7, against central differences; the clamped
+    trials are placed in view space — x alone, y alone, both — and are asserted to be clamped."""
+    from helpers import world_from_view
+    rng = np.random.default_rng(13)
+    w, h = 640, 480
+    cam = _camera("posed", w, h, kx)
+    fx, fy = w / (2.0 * cam.tan_fovx), h / (2.0 * cam.tan_fovy)
+    assert abs(fx / fy - 1.0 / kx) < 1e-3
+    tx_, ty_ = cam.tan_fovx, cam.tan_fovy
+    placed = {5: ((2.0 * tx_, 0.4 * ty_), (True, False)), 6: ((-0.3 * tx_, -1.8 * ty_), (False, True)),
+              7: ((-1.6 * tx_, 2.2 * ty_), (True, True))}
+    for trial in range(8):
+        mean = rng.uniform(-1.5, 1.5, 3)
+        if trial in placed:
+            (rx, ry), state = placed[trial]
+            mean = world_from_view(cam, [[rx * 4.5, ry * 4.5, 4.5]])[0]
+            assert _clamp_state(cam, mean) == state
+        else:
+            assert _clamp_state(cam, mean) == (False, False)
+        scale, quat = np.exp(rng.uniform(-3, -0.5, 3)), rng.normal(size=4)
+        c3 = B.inria_cov3d(scale, quat, 1.3)
+        gk = rng.normal(size=3)
+        g_c3, g_mean_j = B.inria_conic_backward(c3, mean, cam.view, fx, fy, tx_, ty_, gk)
+        fd_c3 = B.finite_difference(lambda c_: float(B.inria_cov2d_conic(c_, mean, cam.view, fx, fy, tx_, ty_) @ gk), c3, 1e-7)
+        fd_mj = B.finite_difference(lambda m_: float(B.inria_cov2d_conic(c3, m_, cam.view, fx, fy, tx_, ty_) @ gk), mean, 1e-6)
+        assert np.abs(g_c3 - fd_c3).max() <= 2e-5 * max(1e-6, np.abs(fd_c3).max()), trial
+        assert np.abs(g_mean_j - fd_mj).max() <= 2e-5 * max(1e-6, np.abs(fd_mj).max()), trial
+        if kx != 1.0:      # the two focal lengths are not interchangeable here
+            swapped = B.inria_conic_backward(c3, mean, cam.view, fy, fx, tx_, ty_, gk)[0]
+            assert np.abs(swapped - g_c3).max() > 1e-2 * np.abs(g_c3).max()
+        g2 = rng.normal(size=2)
+        g_m = B.inria_project_mean2d_backward(mean, cam.proj, w, h, g2)
+        fd_m = B.finite_difference(lambda m_: float(B.inria_project_mean2d(m_, cam.proj, w, h) @ g2), mean, 1e-6)
+        assert np.abs(g_m - fd_m).max() <= 1e-6 * max(1.0, np.abs(fd_m).max())
 
 
 def test_vectorised_tile_backward_matches_the_per_pixel_loops():

@@ -96,21 +96,28 @@ def test_camera_scratch_depends_on_n_only():
 
 
 # ---- the reference against finite differences ---------------------------------------------------------------------------
-def _scenario(sh_degree, seed):
+def _scenario(sh_degree, seed, pose="default"):
     """Ten Gaussians in front of a 64 x 48 camera — two of them with t.x / t.z, t.y / t.z beyond 1.3 tan_fov, one with a
     colour channel clamped at zero — and one behind it (radius 0), with random per-Gaussian gradients. Everything the
-    library reads as float32 is float32-representable."""
+    library reads as float32 is float32-representable. pose: "default" (no rotation: the view matrix's rotation block is
+    diag(1, -1, 1)) or "posed" (rotated and rolled: the block is not symmetric); the three placed Gaussians sit at the same
+    view-space positions under either."""
     from gsrast_amd import camera
+    from helpers import posed_camera, world_from_view
     from oracle import backward_np as B
     rng = np.random.default_rng(seed)
     W, H = 64, 48
-    cam = camera.default_camera(W, H, near=0.05, far=50.0, position=(0.3, -0.2, -4.0))
+    if pose == "default":
+        cam = camera.default_camera(W, H, near=0.05, far=50.0, position=(0.3, -0.2, -4.0))
+    else:
+        cam = posed_camera(W, H, eye=(2.0, -1.2, -4.2), target=0.0, roll=0.4)
     n = 11
     means = np.ones((n, 4))
     means[:, :3] = rng.uniform(-1.0, 1.0, size=(n, 3))
-    means[0, :3] = (6.0, 0.2, 0.3)          # far to the side: t.x / t.z clamped
-    means[1, :3] = (0.1, 4.5, -0.2)         # far up: t.y / t.z clamped
-    means[10, :3] = (0.0, 0.0, -7.0)        # behind the camera
+    # in view space (under the default pose: the world positions (6, 0.2, 0.3), (0.1, 4.5, -0.2) and (0, 0, -7))
+    means[0, :3] = world_from_view(cam, [[5.7, -0.4, 4.3]])[0]     # far to the side: t.x / t.z clamped
+    means[1, :3] = world_from_view(cam, [[-0.2, -4.7, 3.8]])[0]    # far up: t.y / t.z clamped
+    means[10, :3] = world_from_view(cam, [[-0.3, -0.2, -3.0]])[0]  # behind the camera
     means = means.astype(np.float32).astype(np.float64)
     radii = np.ones(n, np.int32)
     radii[10] = 0
@@ -164,9 +171,20 @@ CASES = [("gscuda", None, 0), ("gscuda", True, 0), ("gscuda", "inverse", 0), ("g
 def test_camera_reference_against_central_differences(semantics, depth, sh_degree):
     """Every visible Gaussian's 35 terms against central differences of its share of L, taken w.r.t. each camera float;
     exact zeros where nothing depends on the entry; the float32-decision variant (what the kernel does) within 1e-5."""
+    _reference_against_central_differences(semantics, depth, sh_degree, "default")
+
+
+@pytest.mark.parametrize("semantics,depth,sh_degree", CASES)
+def test_camera_reference_against_central_differences_under_a_rotated_pose(semantics, depth, sh_degree):
+    """The same under a rotated and rolled camera (the test above keeps its ids): there the view matrix's rotation block is
+    not symmetric, so that the reference's own indexing of it is pinned too."""
+    _reference_against_central_differences(semantics, depth, sh_degree, "posed")
+
+
+def _reference_against_central_differences(semantics, depth, sh_degree, pose):
     from oracle import backward_np as B
     inria = semantics == "inria"
-    cam, means, radii, cov3D, shs, grads, clamped = _scenario(sh_degree, seed=len(semantics) + sh_degree + 7)
+    cam, means, radii, cov3D, shs, grads, clamped = _scenario(sh_degree, seed=len(semantics) + sh_degree + 7, pose=pose)
     kw = dict(dL_ddepths=grads["dL_ddepths"] if depth else None, inverse=depth == "inverse", inria=inria,
               shs=shs, sh_degree=sh_degree, dL_dcolors=grads["dL_dcolors"], clamped=clamped)
     args = (means, cam.view, cam.proj, cam.cam_pos, cam.tan_fovx, cam.tan_fovy, cam.width, cam.height, radii, cov3D,
@@ -181,6 +199,8 @@ def test_camera_reference_against_central_differences(semantics, depth, sh_degre
     t = np.array([[v[r] * m[0] + v[4 + r] * m[1] + v[8 + r] * m[2] + v[12 + r] for r in range(3)] for m in means[:10, :3]])
     assert abs(t[0, 0] / t[0, 2]) > 1.3 * cam.tan_fovx and abs(t[1, 1] / t[1, 2]) > 1.3 * cam.tan_fovy
     assert (t[:, 2] > 0.2).all()
+    tb = [v[r] * means[10, 0] + v[4 + r] * means[10, 1] + v[8 + r] * means[10, 2] + v[12 + r] for r in range(3)]
+    assert tb[2] < -1.0                                    # Gaussian 10 is behind the camera under either pose
     for j, i in enumerate(vis):
         g = {k: grads[k][i] for k in grads}
         F = _per_gaussian_loss(inria, sh_degree, depth, cam, means[i, :3], cov3D[i], shs[i].reshape(16, 3), g)
