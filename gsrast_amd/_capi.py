@@ -200,6 +200,8 @@ SIGNATURES = {
     "gsr_footprint_misses_tile": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gsr_ply_activate_layout": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_int, C.c_void_p]),
+    "gsr_activate_params": (C.c_int, [C.c_int] + [C.c_void_p] * 9),
+    "gsr_activate_params_backward": (C.c_int, [C.c_int] + [C.c_void_p] * 13),
 }
 
 _lib = None

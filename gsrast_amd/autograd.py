@@ -1,0 +1,332 @@
+"""torch.autograd over the rasterizer: raw (trainable) parameters -> image, and `loss.backward()` back to them.
+
+  activate   raw parameters -> the arrays gsr_forward takes (gsr_activate_params / _backward, csrc/activations.hip)
+  rasterize  SplatRasterizer.draw / backward / camera_backward as one differentiable function
+  GaussianParams, render   the two joined for a trainer: `render(params, rast, cam)` then `loss.backward()`
+
+Ownership. Every tensor these functions return — images and gradients alike — is allocated by the call that returns it and
+written by no later call of the library (the rasterizer writes into them through its `into=` arguments; nothing is cloned):
+autograd may keep a gradient as `param.grad`, and a loss may be evaluated after the next frame was drawn. A
+SplatRasterizer's chunks, on the other hand, hold ONE forward call: the backward of a frame must run before the same
+rasterizer object draws again, and is refused (RuntimeError, nothing launched) if it did not. Keep one rasterizer object
+per graph that is alive at the same time.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _capi
+from . import ply as _ply
+from .camera import Camera
+from .rasterizer import SplatRasterizer
+
+F32 = torch.float32
+
+
+def _stream(dev) -> int:
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _f32c(t: torch.Tensor, shape, name: str) -> torch.Tensor:
+    if t.dtype != F32 or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected float32 {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    t = t.contiguous()
+    # (the kernels move these arrays in 16-byte vectors: a view that starts in the middle of a row is copied)
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class RadiiSlot:
+    """Carries the radii of the frame from `rasterize` (which draws after `activate` ran) to the backward of `activate`:
+    i32[N], a copy of the forward call's geomState.internal_radii; a Gaussian the frame culled then gets zero gradients
+    without its rows being read."""
+
+    def __init__(self):
+        self.radii: "torch.Tensor | None" = None
+
+
+class _Activate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xyz, opacity_logit, log_scale, rotation, slot):
+        n, dev = int(xyz.shape[0]), xyz.device
+        xyz, log_scale, rotation = _f32c(xyz, (n, 3), "xyz"), _f32c(log_scale, (n, 3), "log_scale"), _f32c(rotation, (n, 4), "rotation")
+        opacity_logit = _f32c(opacity_logit, (n,), "opacity_logit")
+        means3D, scales, rotations = (torch.empty((n, 4), dtype=F32, device=dev) for _ in range(3))
+        opacities = torch.empty((n,), dtype=F32, device=dev)
+        with torch.cuda.device(dev):
+            rc = _capi.lib().gsr_activate_params(n, xyz.data_ptr(), opacity_logit.data_ptr(), log_scale.data_ptr(),
+                                                 rotation.data_ptr(), means3D.data_ptr(), scales.data_ptr(),
+                                                 rotations.data_ptr(), opacities.data_ptr(), _stream(dev))
+        _capi.check(rc, "gsr_activate_params")
+        ctx.save_for_backward(opacity_logit, log_scale, rotation)
+        ctx.slot = slot
+        # each output depends on one input: one whose input requires no gradient requires none either, and the rasterizer's
+        # backward is then not asked for it
+        need_xyz, need_opacity, need_scale, need_rotation = ctx.needs_input_grad[:4]
+        off = [t for t, need in ((means3D, need_xyz), (scales, need_scale), (rotations, need_rotation), (opacities, need_opacity))
+               if not need]
+        if off:
+            ctx.mark_non_differentiable(*off)
+        return means3D, scales, rotations, opacities
+
+    @staticmethod
+    def backward(ctx, g_means, g_scales, g_rotations, g_opacities):
+        opacity_logit, log_scale, rotation = ctx.saved_tensors
+        n, dev = int(rotation.shape[0]), rotation.device
+        want = [need and g is not None for need, g in zip(ctx.needs_input_grad[:4], (g_means, g_opacities, g_scales, g_rotations))]
+        if not any(want):
+            return None, None, None, None, None
+        keep = []                                   # what the kernel reads must live until the launch is enqueued
+
+        def vec4(g, name):
+            g = _f32c(g, (n, 4), name)
+            keep.append(g)
+            return g.data_ptr()
+
+        def opacity_vec4(g):
+            """The opacity's gradient where the kernel reads it, in .w of a vec4 array: `rasterize` returns it as column 3
+            of dL_dconic_opacity, which is then read in place; a plain [N] gradient is padded."""
+            if (g.dtype == F32 and tuple(g.shape) == (n,) and n > 0 and g.stride(0) == 4 and g.storage_offset() >= 3
+                    and (g.data_ptr() - 12) % 16 == 0):
+                keep.append(g)
+                return g.data_ptr() - 12
+            t = torch.zeros((n, 4), dtype=F32, device=dev)
+            t[:, 3] = g
+            keep.append(t)
+            return t.data_ptr()
+
+        new = lambda *shape: torch.empty(shape, dtype=F32, device=dev)
+        d_xyz = new(n, 3) if want[0] else None
+        d_op = new(n) if want[1] else None
+        d_scale = new(n, 3) if want[2] else None
+        d_rot = new(n, 4) if want[3] else None
+        radii = ctx.slot.radii if ctx.slot is not None else None
+        if radii is not None:
+            assert radii.dtype == torch.int32 and tuple(radii.shape) == (n,) and radii.device == dev and radii.is_contiguous()
+        p = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(dev):
+            rc = _capi.lib().gsr_activate_params_backward(
+                n, p(opacity_logit) if want[1] else None, p(log_scale) if want[2] else None, p(rotation) if want[3] else None,
+                p(radii), vec4(g_means, "dL_dmeans3D") if want[0] else None, vec4(g_scales, "dL_dscales") if want[2] else None,
+                vec4(g_rotations, "dL_drotations") if want[3] else None, opacity_vec4(g_opacities) if want[1] else None,
+                p(d_xyz), p(d_op), p(d_scale), p(d_rot), _stream(dev))
+        _capi.check(rc, "gsr_activate_params_backward")
+        return d_xyz, d_op, d_scale, d_rot, None
+
+
+def activate(xyz, opacity_logit, log_scale, rotation, *, radii_slot: "RadiiSlot | None" = None):
+    """Raw parameters -> (means3D [N,4] = (x,y,z,1), scales [N,4] = (exp s, e), rotations [N,4] = r/|r|, opacities [N] =
+    sigmoid) on the device, in the float32 arithmetic of the .ply loader (bit-equal to `load_ply` of the same raw values).
+    Inputs: float32 device tensors xyz [N,3], opacity_logit [N], log_scale [N,3], rotation [N,4] (real part first).
+    Differentiable: the backward is one kernel, computes only the gradients of the inputs that require one, and returns
+    fresh tensors. radii_slot: filled by `rasterize` with the frame's radii; culled Gaussians then get exact zeros. Pass
+    one only when the rasterizer is the sole consumer of the four outputs (as `render` does): a regulariser on `scales`
+    reaches culled Gaussians too."""
+    return _Activate.apply(xyz, opacity_logit, log_scale, rotation, radii_slot)
+
+
+_DRAW_OPTIONS = ("plan", "overlap_emit", "tile_history", "deep_tiles")
+STALE_MESSAGE = ("this rasterizer has drawn another frame, or was given another scene or camera, since the forward pass whose "
+                 "backward is asked for: a SplatRasterizer holds the state of one forward call. Run backward() before the "
+                 "same object renders again, or keep one rasterizer object per graph kept alive")
+
+
+class _Rasterize(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp):
+        n, dev = int(means3D.shape[0]), rast.device
+        means3D, scales, rotations = _f32c(means3D, (n, 4), "means3D"), _f32c(scales, (n, 4), "scales"), _f32c(rotations, (n, 4), "rotations")
+        opacities, shs = _f32c(opacities, (n,), "opacities"), _f32c(shs, (n, 48), "shs")
+        if colors_precomp is not None:
+            colors_precomp = _f32c(colors_precomp, (n, 3), "colors_precomp")
+        rast.bind_scene(means3D, scales, rotations, opacities, shs)
+        rast.set_camera_device(view, proj, cam_pos, *opts["tan_fov"])
+        H, W, depth = rast.height, rast.width, opts["depth"]
+        into = {"out_color": torch.empty((3, H, W), dtype=F32, device=dev)}
+        if depth:
+            into["out_depth"] = torch.empty((H, W), dtype=F32, device=dev)
+        rast.draw(None, sync=False, semantics=opts["semantics"], sh_degree=opts["sh_degree"], scale_modifier=opts["scale_modifier"],
+                  depth=depth, colors_precomp=colors_precomp if colors_precomp is not None else False, sorted_lists=True,
+                  into=into, **opts["draw"])
+        opacity_map = rast.opacity_map()                      # (1 - finalT: a new tensor)
+        if opts["radii_slot"] is not None:
+            opts["radii_slot"].radii = rast.map_geometry_state()["radii"].clone()
+        ctx.rast, ctx.opts = rast, opts
+        ctx.receipt, ctx.epoch = rast.last_receipt.copy(), rast._state_epoch
+        ctx.view_shapes = (view.shape, proj.shape, cam_pos.shape)
+        ctx.has_colors = colors_precomp is not None
+        ctx.save_for_backward(means3D, scales, rotations, opacities, shs)      # (a write to one of them before backward() is reported)
+        ctx.mark_non_differentiable(opacity_map)
+        return into["out_color"], into.get("out_depth"), opacity_map
+
+    @staticmethod
+    def backward(ctx, g_color, g_depth, _g_opacity_map):
+        rast, opts = ctx.rast, ctx.opts
+        if rast._state_epoch != ctx.epoch:
+            raise RuntimeError(STALE_MESSAGE)
+        ctx.saved_tensors                                     # noqa: B018 (raises if one was modified in place)
+        need = dict(zip(("means3D", "scales", "rotations", "opacities", "shs", "view", "proj", "cam_pos", "colors_precomp"),
+                        ctx.needs_input_grad[2:]))
+        n, dev = rast.num_gaussians, rast.device
+        if g_color is None and g_depth is None:
+            return (None,) * 11
+        if g_color is None:
+            g_color = torch.zeros((3, rast.height, rast.width), dtype=F32, device=dev)
+        new = lambda *shape: torch.empty(shape, dtype=F32, device=dev)
+        into = {}
+        if need["means3D"]:
+            into["dL_dmeans3D"] = new(n, 4)
+        if need["scales"] or need["rotations"]:
+            into["dL_dscales"] = new(n, 4)                   # (the chain writes the quaternion's gradient beside the scale's only)
+        if need["rotations"]:
+            into["dL_drotations"] = new(n, 4)
+        if need["opacities"]:
+            into["dL_dconic_opacity"] = new(n, 4)
+        if need["shs"] and not ctx.has_colors:
+            # the reference's colour reads the DC triple only: that chain writes floats 0..15 of a row, upstream's all 48
+            into["dL_dshs"] = new(n, 48) if opts["semantics"] == "inria" else torch.zeros((n, 48), dtype=F32, device=dev)
+        if need["means3D"] and opts["semantics"] == "inria" and not ctx.has_colors and "dL_dshs" not in into:
+            into["dL_dshs"] = new(n, 48)                     # (gsr_backward forms dL_dmeans3D's term through the view direction with it)
+        if need["colors_precomp"] and ctx.has_colors:
+            into["dL_dcolors"] = new(n, 3)
+        camera = need["view"] or need["proj"] or need["cam_pos"]
+        if camera:
+            into["camera"] = new(35)
+        if not into:
+            return (None,) * 11
+        res = rast.backward(g_color, semantics=opts["semantics"], sh_degree=opts["sh_degree"], scale_modifier=opts["scale_modifier"],
+                            receipt=ctx.receipt, wide_sums=True, dL_ddepth=g_depth if opts["depth"] else None,
+                            depth=opts["depth"] or None, camera=camera, into=into, sync=False)
+        g = lambda k, on=True: res[k] if (on and k in res) else None
+        cam_g = lambda k, name, shape: res[k].reshape(shape) if need[name] else None
+        return (None, None, g("dL_dmeans3D"), g("dL_dscales", need["scales"]), g("dL_drotations"),
+                res["dL_dconic_opacity"][:, 3] if need["opacities"] else None, g("dL_dshs", need["shs"]),
+                cam_g("dL_dview_matrix", "view", ctx.view_shapes[0]), cam_g("dL_dproj_matrix", "proj", ctx.view_shapes[1]),
+                cam_g("dL_dcam_pos", "cam_pos", ctx.view_shapes[2]), g("dL_dcolors"))
+
+
+def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, tan_fov, *,
+              semantics: str = "gscuda", sh_degree: int = 3, scale_modifier: float = 1.0, depth: "bool | str" = False,
+              colors_precomp: "torch.Tensor | None" = None, radii_slot: "RadiiSlot | None" = None, **draw_options):
+    """One differentiable frame: SplatRasterizer.draw forward, .backward / .camera_backward backward.
+
+    Tensors in the library's layouts, float32 on rast.device: means3D / scales / rotations [N,4], opacities [N], shs [N,48]
+    (as `semantics` reads them), view / proj (16 elements, column-major as Camera.view / .proj; any shape), cam_pos (3),
+    colors_precomp [N,3] or None. tan_fov = (tan_fovx, tan_fovy), Python floats. The rasterizer is pointed at these tensors
+    (bind_scene: nothing is copied) and the camera is copied on the device. draw_options: plan, overlap_emit, tile_history,
+    deep_tiles, passed to draw(); the sorted lists are always written.
+
+    Returns (color [3,H,W], depth [H,W] or None, opacity_map [H,W]), each a new tensor. opacity_map (1 - finalT) is NOT
+    differentiable: a gradient with respect to the accumulated opacity would be a further sum in render_backward_kernel,
+    which does not exist yet (out of scope here); dividing the depth channel by it treats it as a constant.
+
+    The backward asks gsr_backward (double sums: the gradients do not depend on the order of the tiles' atomics) for exactly
+    the per-Gaussian outputs whose input requires a gradient, written into new tensors; when view, proj or cam_pos requires
+    one, it runs with camera=True and returns the three camera gradients in the inputs' shapes. It raises RuntimeError
+    before launching anything if `rast` drew again, or was rebound, after this call (see the module docstring)."""
+    assert set(draw_options) <= set(_DRAW_OPTIONS), sorted(draw_options)
+    assert depth in (False, True, "inverse"), depth
+    opts = {"tan_fov": (float(tan_fov[0]), float(tan_fov[1])), "semantics": semantics, "sh_degree": int(sh_degree),
+            "scale_modifier": float(scale_modifier), "depth": depth, "radii_slot": radii_slot, "draw": dict(draw_options)}
+    return _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp)
+
+
+def _rest_to_coefficient_major(sh: np.ndarray) -> np.ndarray:
+    """[N,48] in the file's order (f_dc 3, f_rest channel-major [3][15]) -> [N][16][3]."""
+    n = sh.shape[0]
+    out = sh.copy()
+    out[:, 3:] = sh[:, 3:].reshape(n, 3, 15).transpose(0, 2, 1).reshape(n, 45)
+    return out
+
+
+def _rest_to_file_order(sh: np.ndarray) -> np.ndarray:
+    n = sh.shape[0]
+    out = sh.copy()
+    out[:, 3:] = sh[:, 3:].reshape(n, 15, 3).transpose(0, 2, 1).reshape(n, 45)
+    return out
+
+
+class GaussianParams(torch.nn.Module):
+    """The raw, trainable values of a scene: xyz [N,3], opacity_logit [N], log_scale [N,3], rotation [N,4] (unnormalised,
+    real part first), shs [N,48] — what a 3DGS .ply stores and what an optimiser steps. sh_layout: "file" (f_rest
+    channel-major, as stored; all the reference's semantics reads is the DC triple) or "coefficient_major" ([16][3], what
+    semantics="inria" with sh_degree >= 1 reads)."""
+
+    def __init__(self, xyz, opacity_logit, log_scale, rotation, shs, sh_layout: str = "file", device=None):
+        super().__init__()
+        assert sh_layout in ("file", "coefficient_major"), sh_layout
+        self.sh_layout = sh_layout
+
+        def param(a, shape):
+            t = a.detach().clone() if isinstance(a, torch.Tensor) else torch.from_numpy(np.array(a, dtype=np.float32))
+            t = t.to(device=device if device is not None else t.device, dtype=F32).reshape(shape).contiguous()
+            return torch.nn.Parameter(t)
+        n = int(np.shape(xyz)[0]) if not isinstance(xyz, torch.Tensor) else int(xyz.shape[0])
+        self.xyz = param(xyz, (n, 3))
+        self.opacity_logit = param(opacity_logit, (n,))
+        self.log_scale = param(log_scale, (n, 3))
+        self.rotation = param(rotation, (n, 4))
+        self.shs = param(shs, (n, 48))
+
+    @classmethod
+    def from_raw(cls, xyz, opacity_logit, log_scale, rotation, shs, sh_layout: str = "file", device=None) -> "GaussianParams":
+        """From arrays or tensors of raw values (copied); shs already in `sh_layout`."""
+        return cls(xyz, opacity_logit, log_scale, rotation, shs, sh_layout, device)
+
+    @classmethod
+    def from_ply(cls, path: str, sh_layout: str = "file", device="cuda:0") -> "GaussianParams":
+        """The file's raw values, unactivated (`activated()` of the result equals `ply.load_ply` of the file bit for bit)."""
+        n, off = _ply.parse_header(path)
+        raw = np.fromfile(path, dtype="<f4", offset=off, count=n * _ply.RECORD_FLOATS)
+        if raw.size < n * _ply.RECORD_FLOATS:
+            raise ValueError(f"{path}: file ends before {n} records")
+        rec = raw.reshape(n, _ply.RECORD_FLOATS).astype(np.float32)
+        sh = rec[:, 6:54]
+        if sh_layout == "coefficient_major":
+            sh = _rest_to_coefficient_major(sh)
+        return cls(rec[:, 0:3], rec[:, 54], rec[:, 55:58], rec[:, 58:62], sh, sh_layout, device)
+
+    @property
+    def num_gaussians(self) -> int:
+        return int(self.xyz.shape[0])
+
+    def activated(self, radii_slot: "RadiiSlot | None" = None):
+        """(means3D, scales, rotations, opacities): `activate` of the raw values."""
+        return activate(self.xyz, self.opacity_logit, self.log_scale, self.rotation, radii_slot=radii_slot)
+
+    def save_ply(self, path: str) -> None:
+        """Writes the raw values as a 3DGS .ply (ply.write_ply); a coefficient-major shs goes back to the file's order."""
+        host = lambda t: t.detach().cpu().numpy()
+        sh = host(self.shs)
+        if self.sh_layout == "coefficient_major":
+            sh = _rest_to_file_order(sh)
+        _ply.write_ply(path, host(self.xyz), sh, host(self.opacity_logit), host(self.log_scale), host(self.rotation))
+
+
+def _camera_tensors(camera, dev):
+    if isinstance(camera, Camera):
+        cache = camera.__dict__.setdefault("_device_tensors", {})
+        key = str(dev)
+        if key not in cache:
+            cache[key] = tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32).reshape(-1).copy()).to(dev)
+                               for a in (camera.view, camera.proj, camera.cam_pos))
+        return cache[key] + (float(camera.tan_fovx), float(camera.tan_fovy))
+    view, proj, cam_pos, tan_fovx, tan_fovy = camera
+    return view, proj, cam_pos, float(tan_fovx), float(tan_fovy)
+
+
+def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: str = "gscuda", sh_degree: int = 3,
+           scale_modifier: float = 1.0, depth: "bool | str" = False, **draw_options):
+    """`activate` then `rasterize`: (color [3,H,W], depth [H,W] or None, opacity_map [H,W]) of `params` seen from `camera`
+    — a Camera (its matrices are uploaded once per device and kept with it; write to a Camera's arrays and it must be a new
+    object) or a tuple (view, proj, cam_pos, tan_fovx, tan_fovy) whose first three are device tensors, which may require
+    gradients. `loss.backward()` fills params.*.grad (and the camera tensors' .grad). Gaussians the frame culled get zero
+    gradients without their rows being read."""
+    if semantics == "inria" and sh_degree >= 1:
+        assert params.sh_layout == "coefficient_major", 'semantics="inria" reads shs as [N][16][3]: sh_layout="coefficient_major"'
+    slot = RadiiSlot()
+    means3D, scales, rotations, opacities = params.activated(slot)
+    view, proj, cam_pos, tan_fovx, tan_fovy = _camera_tensors(camera, rast.device)
+    return rasterize(rast, means3D, scales, rotations, opacities, params.shs, view, proj, cam_pos, (tan_fovx, tan_fovy),
+                     semantics=semantics, sh_degree=sh_degree, scale_modifier=scale_modifier, depth=depth, radii_slot=slot,
+                     **draw_options)

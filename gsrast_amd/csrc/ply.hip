@@ -14,6 +14,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include "activation_math.hpp"
 #include "gsr_common.hpp"
 
 namespace gsr {
@@ -49,12 +50,9 @@ __global__ __launch_bounds__(256) void ply_activate_kernel(const float* __restri
         const float* r = w + lane * kPlyFloats;
         const long long i = first + lane;
         means3D[i] = make_float4(r[0], r[1], r[2], 1.0f);
-        scales[i] = make_float4(expf(r[55]), expf(r[56]), expf(r[57]), expf(1.0f));
-        const float q0 = r[58], q1 = r[59], q2 = r[60], q3 = r[61];
-        const float d = (q0 * q0 + q1 * q1) + (q2 * q2 + q3 * q3);           // glm::dot(vec4)
-        const float inv = 1.0f / sqrtf(d);                                    // glm::inversesqrt
-        rotations[i] = make_float4(q0 * inv, q1 * inv, q2 * inv, q3 * inv);
-        opacities[i] = 1.0f / (1.0f + expf(-r[54]));                          // sigmoid, SplatData.cpp:8-11
+        scales[i] = activate_scale(r[55], r[56], r[57]);
+        rotations[i] = activate_rotation(r[58], r[59], r[60], r[61]);
+        opacities[i] = activate_opacity(r[54]);
     }
     // SH block of the wave's records: count * 48 contiguous output floats
     float* sh_out = shs + first * 48;

@@ -91,6 +91,9 @@ class SplatRasterizer:
         self._cam_host = torch.zeros(35, dtype=torch.float32).pin_memory()
         self._view, self._proj, self._cam_pos = self._cam_dev[0:16], self._cam_dev[16:32], self._cam_dev[32:35]
         self._last_cam = None
+        # counts what changes the state a backward pass reads (a draw, a camera upload, a new scene binding): what
+        # gsrast_amd.autograd compares to refuse the backward of a frame that is no longer held
+        self._state_epoch = 0
         # this view's tile history (gsr_tile_history: how long the tiles of its last frames took; the blend starts the slow
         # ones first). One per rasterizer object, so two of them on one thread do not feed each other's frames.
         self._history = C.c_void_p()
@@ -120,6 +123,31 @@ class SplatRasterizer:
         self._colors_dc, self._colors_key = None, None   # colours precomputed from the DC triples, on first use, per SH tensor state
         self.rects = (torch.zeros((self.num_gaussians, 2), dtype=torch.int32, device=self.device)
                       if use_rects else None)
+        self._state_epoch += 1
+
+    def bind_scene(self, means3D: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor, opacities: torch.Tensor,
+                   shs: torch.Tensor, use_rects: "bool | None" = None) -> None:
+        """Points the rasterizer at the caller's device tensors (means3D / scales / rotations [N,4], opacities [N], shs
+        [N,48]; float32, contiguous, on this device) without copying them: what a trainer whose activated parameters are new
+        tensors every step calls per frame (gsrast_amd.autograd.rasterize does). `rects` is kept while N and use_rects
+        (default: as it is) are unchanged; the precomputed-colour cache is dropped as configure_from_scene drops it."""
+        n = int(means3D.shape[0])
+        for name, t, shape in (("means3D", means3D, (n, 4)), ("scales", scales, (n, 4)), ("rotations", rotations, (n, 4)),
+                               ("opacities", opacities, (n,)), ("shs", shs, (n, 48))):
+            assert isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.device, name
+            assert tuple(t.shape) == shape and t.is_contiguous(), (name, tuple(t.shape), shape)
+        self.means3D, self.scales, self.rotations, self.opacities, self.shs = means3D, scales, rotations, opacities, shs
+        if use_rects is None:
+            use_rects = self.use_rects
+        have = getattr(self, "rects", None)
+        if not use_rects:
+            self.rects = None
+        elif have is None or have.shape[0] != n:
+            self.rects = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
+        self.use_rects = use_rects
+        self.num_gaussians = n
+        self._colors_dc, self._colors_key = None, None
+        self._state_epoch += 1
 
     def set_camera(self, cam: Camera) -> None:
         """Uploads the 35 camera floats (the reference's caller copies view / proj per frame,
@@ -134,6 +162,19 @@ class SplatRasterizer:
         self._cam_dev.copy_(self._cam_host, non_blocking=True)     # stream-ordered before the next forward call
         self._tan = (float(cam.tan_fovx), float(cam.tan_fovy))
         self._last_cam = cam
+        self._state_epoch += 1
+
+    def set_camera_device(self, view: torch.Tensor, proj: torch.Tensor, cam_pos: torch.Tensor, tan_fovx: float,
+                          tan_fovy: float) -> None:
+        """The 35 camera floats from device tensors (16 / 16 / 3 elements in the layouts of Camera.view / .proj / .cam_pos),
+        copied on the device in stream order: no host round trip. A later set_camera uploads again, whichever Camera."""
+        with torch.no_grad():
+            for dst, src, k in ((self._view, view, 16), (self._proj, proj, 16), (self._cam_pos, cam_pos, 3)):
+                assert isinstance(src, torch.Tensor) and src.device == self.device and src.numel() == k, (src.shape, k)
+                dst.copy_(src.detach().reshape(k))
+        self._tan = (float(tan_fovx), float(tan_fovy))
+        self._last_cam = None
+        self._state_epoch += 1
 
     # -- one frame --------------------------------------------------------------------
     def draw(self, cam: Camera | None = None, *, profile: bool = False, count_staged: bool = False,
@@ -141,7 +182,7 @@ class SplatRasterizer:
              sync: bool = True, semantics: str = "gscuda", sh_degree: int = 3, plan: str = "auto",
              overlap_emit: "bool | None" = None, sorted_lists: bool = True, colors_precomp: "bool | torch.Tensor" = False,
              tile_history: "bool | str" = True, deep_tiles: "bool | str | None" = None,
-             depth: "bool | str" = False) -> torch.Tensor:
+             depth: "bool | str" = False, into: "dict | None" = None) -> torch.Tensor:
         """One `forward` call on the current torch stream. Returns the planar (3,H,W) image
         tensor owned by this object. `sync` adds the device synchronise the reference's caller
         performs after every call (CudaBuffer.hpp:8-12). semantics="inria" selects the upstream
@@ -164,9 +205,23 @@ class SplatRasterizer:
         either semantics); backward() then reads the same tensor.
         depth: True = also the depth channel (gsr_forward_args.out_depth: sum of z_i alpha_i T_i per pixel, view-space z, no
         background, not normalised — see opacity_map()), "inverse" = of 1 / z_i (GSR_FLAG_DEPTH_INVERSE); written to
-        self.out_depth, an (H, W) tensor owned by this object."""
+        self.out_depth, an (H, W) tensor owned by this object.
+        into: {"out_color": (3,H,W) tensor, "out_depth": (H,W) tensor} (either or both; float32, contiguous, on this device):
+        the call writes the image / the depth channel there instead of into this object's own tensors, which it then leaves
+        alone, and returns into["out_color"] if given — memory no later call of this object writes."""
         if cam is not None:
             self.set_camera(cam)
+        self._state_epoch += 1
+        out_color, out_depth = self.out_color, None
+        if into is not None:
+            assert set(into) <= {"out_color", "out_depth"}, sorted(into)
+            for k, shape in (("out_color", (3, self.height, self.width)), ("out_depth", (self.height, self.width))):
+                t = into.get(k)
+                if t is not None:
+                    assert t.dtype == torch.float32 and t.device == self.device and t.is_contiguous(), k
+                    assert tuple(t.shape) == shape, (k, tuple(t.shape))
+            out_color = into.get("out_color", out_color)
+            out_depth = into.get("out_depth")
         a = _capi.ForwardArgs()
         a.struct_size = C.sizeof(_capi.ForwardArgs)
         inria = semantics == "inria"
@@ -201,16 +256,18 @@ class SplatRasterizer:
         a.view_matrix, a.proj_matrix, a.cam_pos = self._view.data_ptr(), self._proj.data_ptr(), self._cam_pos.data_ptr()
         a.tan_fovx, a.tan_fovy = self._tan
         a.prefiltered = 0
-        a.out_color = self.out_color.data_ptr()
+        a.out_color = out_color.data_ptr()
         a.radii = None
         a.rects = self.rects.data_ptr() if (self.rects is not None and not inria) else None
         a.box_min = a.box_max = None
         a.stream = torch.cuda.current_stream(self.device).cuda_stream
         a.tile_history = self._history if tile_history is True else None
         if depth:
-            if self.out_depth is None:
-                self.out_depth = torch.zeros((self.height, self.width), dtype=torch.float32, device=self.device)
-            a.out_depth = self.out_depth.data_ptr()
+            if out_depth is None:
+                if self.out_depth is None:
+                    self.out_depth = torch.zeros((self.height, self.width), dtype=torch.float32, device=self.device)
+                out_depth = self.out_depth
+            a.out_depth = out_depth.data_ptr()
         if tile_rows is not None:
             a.tile_row_begin, a.tile_row_end = int(tile_rows[0]), int(tile_rows[1])
         with torch.cuda.device(self.device):
@@ -236,7 +293,7 @@ class SplatRasterizer:
         if sync:
             torch.cuda.current_stream(self.device).synchronize()
             self.poll_async_error()
-        return self.out_color
+        return out_color
 
     def opacity_map(self) -> torch.Tensor:
         """(H, W) accumulated opacity of the last draw(), 1 - finalT: divide out_depth by it for expected depth."""
@@ -282,6 +339,7 @@ class SplatRasterizer:
         then holds pc::ImageState (depth, temporary image); see map_points_image_state."""
         if cam is not None:
             self.set_camera(cam)
+        self._state_epoch += 1
         if getattr(self, "_means3", None) is None or self._means3.shape[0] != self.num_gaussians:
             self._means3 = self.means3D[:, :3].contiguous()        # this path reads a stride of three floats
         a = _capi.ForwardArgs()
@@ -315,7 +373,8 @@ class SplatRasterizer:
                  tile_rows: tuple[int, int] | None = None, scale_modifier: float = 1.0, semantics: str = "gscuda",
                  sh_degree: int = 3, receipt: "_capi.ForwardReceipt | None | bool" = None, wide_sums: bool = True,
                  outputs: "tuple[str, ...] | None" = None, dL_ddepth: "torch.Tensor | None" = None,
-                 depth: "bool | str | None" = None, camera: bool = False) -> dict:
+                 depth: "bool | str | None" = None, camera: bool = False, into: "dict | None" = None,
+                 sync: bool = True) -> dict:
         """Gradients of sum(dL_dout * out_color) of the LAST draw() through gsr_backward; `semantics` / `sh_degree`
         must be those of that draw(). receipt: the gsr_forward_receipt of the draw() this is the backward of (default:
         this object's last draw(); any host thread may call); False = none, the reference's contract only (sorted lists
@@ -335,7 +394,14 @@ class SplatRasterizer:
         camera: the result also holds the gradients w.r.t. the camera, dL_dview_matrix (16,), dL_dproj_matrix (16,) and
         dL_dcam_pos (3,) in the layouts of Camera.view / .proj / .cam_pos (camera_backward(), right behind gsr_backward on the
         same stream). gsr_backward then also writes what that pass reads — dL_dmean2D, dL_dcov2D, and under inria with SH
-        colours dL_dcolors — whatever `outputs` and `with_cov3D` say; arrays not asked for stay out of the result."""
+        colours dL_dcolors — whatever `outputs` and `with_cov3D` say; arrays not asked for stay out of the result.
+        into (needs wide_sums): {name: tensor} of the per-Gaussian outputs to compute, written into the caller's tensors
+        (float32, contiguous, on this device, in the shapes above; with camera=True also "camera": (35,), view | proj |
+        cam_pos) instead of this object's; it replaces `outputs`, and the result holds exactly these tensors (the camera's
+        three as views of into["camera"]): memory no later call of this object writes. None of this object's output buffers
+        is allocated for such a call; what the call needs beside them (dL_ddepths, the camera pass's inputs) is scratch
+        of this object. dL_dshs under semantics="gscuda" must come zero-filled: that chain writes floats 0..15 of each row.
+        sync=False: returns without waiting for the stream."""
         assert semantics in ("gscuda", "inria")
         n, dev = self.num_gaussians, self.device
         g = dL_dout.to(device=dev, dtype=torch.float32).contiguous()
@@ -351,7 +417,21 @@ class SplatRasterizer:
         # kept per semantics so that a gscuda call never returns what an inria call left in floats 16..47.
         caches = self.__dict__.setdefault("_bw_out_by_semantics", {})
         cache = caches.get(semantics)
-        if cache is None or cache["dL_dmean2D"].shape[0] != n or ("dL_dcov3D" in cache) != with_cov3D:
+        shapes = {"dL_dmean2D": (n, 2), "dL_dconic_opacity": (n, 4), "dL_dcolors": (n, 3), "dL_dcov2D": (n, 4),
+                  "dL_dcov3D": (n, 6), "dL_dshs": (n, 48), "dL_dmeans3D": (n, 4), "dL_dscales": (n, 4), "dL_drotations": (n, 4)}
+        camera_into = None
+        if into is not None:
+            assert wide_sums and outputs is None, "into= needs wide_sums and replaces outputs="
+            into = dict(into)
+            camera_into = into.pop("camera", None)
+            assert set(into) <= set(shapes) and (with_cov3D or set(into) <= {"dL_dmean2D", "dL_dconic_opacity", "dL_dcolors"}), sorted(into)
+            for k, t in into.items():
+                assert t.dtype == torch.float32 and t.device == dev and t.is_contiguous() and tuple(t.shape) == shapes[k], k
+            # this object's scratch of such calls: never handed out
+            cache = self.__dict__.setdefault("_bw_into_scratch", {})
+            if cache and next(iter(cache.values())).shape[0] != n:
+                cache.clear()
+        elif cache is None or cache["dL_dmean2D"].shape[0] != n or ("dL_dcov3D" in cache) != with_cov3D:
             cache = {"dL_dmean2D": torch.empty((n, 2), dtype=torch.float32, device=dev),
                      "dL_dconic_opacity": torch.empty((n, 4), dtype=torch.float32, device=dev),
                      "dL_dcolors": torch.empty((n, 3), dtype=torch.float32, device=dev)}
@@ -396,7 +476,9 @@ class SplatRasterizer:
                 if getattr(self, "_depth_sums_f64", None) is None or self._depth_sums_f64.shape[0] != n:
                     self._depth_sums_f64 = torch.zeros((n,), dtype=torch.float64, device=dev)     # (the library leaves it zero)
                 a.depth_sums_f64 = self._depth_sums_f64.data_ptr()
-        if outputs is not None:
+        if into is not None:
+            out = into
+        elif outputs is not None:
             assert wide_sums and set(outputs) <= set(cache), (outputs, sorted(cache))
             out = {k: cache[k] for k in outputs}
             if dL_ddepth is not None:
@@ -407,6 +489,8 @@ class SplatRasterizer:
             sh_colour = semantics == "inria" and col is None        # (colours from SH move with the camera position)
             for k in ("dL_dmean2D", "dL_dcov2D") + (("dL_dcolors",) if sh_colour else ()):
                 if k not in out:
+                    if into is not None and cache.get(k) is None:
+                        cache[k] = torch.empty(shapes[k], dtype=torch.float32, device=dev)
                     need[k] = cache.get(k)
             if "dL_dcov2D" in need and need["dL_dcov2D"] is None:          # (with_cov3D=False: a buffer of its own)
                 if getattr(self, "_camera_cov2D", None) is None or self._camera_cov2D.shape[0] != n:
@@ -446,19 +530,21 @@ class SplatRasterizer:
             inverse = bool(a.flags & _capi.GSR_FLAG_DEPTH_INVERSE)
             cam_out = self.camera_backward(grads, semantics=semantics, sh_degree=sh_degree, shs_colour=sh_colour,
                                            depth=("inverse" if inverse else True) if dL_ddepth is not None else None,
-                                           profile=profile, sync=False)
-            torch.cuda.current_stream(dev).synchronize()
+                                           profile=profile, sync=False, into=camera_into)
+            if sync:
+                torch.cuda.current_stream(dev).synchronize()
             res = {k: v for k, v in out.items() if dL_ddepth is not None or k != "dL_ddepths"}
             res.update(cam_out)
             return res
-        torch.cuda.current_stream(dev).synchronize()
+        if sync:
+            torch.cuda.current_stream(dev).synchronize()
         if dL_ddepth is None and "dL_ddepths" in out:
             return {k: v for k, v in out.items() if k != "dL_ddepths"}
         return out
 
     def camera_backward(self, grads: dict, *, semantics: str = "gscuda", sh_degree: int = 3, depth: "bool | str | None" = None,
                         shs_colour: "bool | None" = None, receipt: "_capi.ForwardReceipt | None" = None,
-                        profile: bool = False, sync: bool = True) -> dict:
+                        profile: bool = False, sync: bool = True, into: "torch.Tensor | None" = None) -> dict:
         """gsr_camera_backward alone, on the current stream: the gradients w.r.t. the camera of the last draw(), from the
         per-Gaussian gradients its gsr_backward returned — grads["dL_dmean2D"] [N,2], grads["dL_dcov2D"] [N,4], with a depth
         gradient grads["dL_ddepths"] [N] (depth: the channel's mode, True or "inverse"), and grads["dL_dcolors"] [N,3] when
@@ -466,7 +552,9 @@ class SplatRasterizer:
         object's last draw() without one — as backward() decides it: colours from SH unless that draw took colors_precomp).
         Returns float32 device tensors dL_dview_matrix (16,), dL_dproj_matrix (16,), dL_dcam_pos (3,) in the layouts of
         Camera.view / .proj / .cam_pos, owned by this object and overwritten by the next call. The scratch
-        (gsr_camera_backward_scratch_bytes) is kept by this object. backward(camera=True) calls this."""
+        (gsr_camera_backward_scratch_bytes) is kept by this object. backward(camera=True) calls this.
+        into: a (35,) float32 tensor on this device, view | proj | cam_pos — the result is written there and returned as
+        views of it, and this object's own gradient buffer is left alone."""
         assert semantics in ("gscuda", "inria") and depth in (None, False, True, "inverse"), (semantics, depth)
         n, dev = self.num_gaussians, self.device
         inria = semantics == "inria"
@@ -504,6 +592,9 @@ class SplatRasterizer:
         if depth:
             a.dL_ddepths = ptr("dL_ddepths")
         g = self._camera_grad
+        if into is not None:
+            assert into.dtype == torch.float32 and into.device == dev and into.is_contiguous() and tuple(into.shape) == (35,)
+            g = into
         a.dL_dview_matrix, a.dL_dproj_matrix, a.dL_dcam_pos = g[0:16].data_ptr(), g[16:32].data_ptr(), g[32:35].data_ptr()
         a.scratch = self._camera_scratch.data_ptr()
         a.stream = torch.cuda.current_stream(dev).cuda_stream

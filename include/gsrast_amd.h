@@ -615,6 +615,33 @@ enum { GSR_SH_LAYOUT_FILE = 0, GSR_SH_LAYOUT_COEFFICIENT_MAJOR = 1 };
 int gsr_ply_activate_layout(const float* raw_device, int n, float* means3D, float* scales, float* rotations,
                             float* opacities, float* shs, int sh_layout, void* stream);
 
+/* ---- a trainer's raw parameters (csrc/activations.hip) ---- */
+/* The same activations from separate arrays instead of the file record: what a trainer optimises (positions f32[3 n],
+ * opacity logits f32[n], log-scales f32[3 n], unnormalised quaternions f32[4 n], real part first) -> the arrays
+ * gsr_forward takes: means3D (x, y, z, 1), scales (exp s, exp s, exp s, e), rotations r / |r| (all vec4[n]) and
+ * opacities 1 / (1 + exp(-x)) (f32[n]). Float32 arithmetic in the operation order of gsr_ply_activate: bit-equal results
+ * for equal raw values. SH coefficients need no activation. Device pointers, every one required; the arrays of three and
+ * four floats per Gaussian 16-byte aligned (GSR_ERR_INVALID_ARG otherwise, before any HIP call); n <= 0 is GSR_OK and
+ * touches nothing. Asynchronous on stream. */
+int gsr_activate_params(int n, const float* raw_means, const float* raw_opacity, const float* raw_scales,
+                        const float* raw_rotations, float* means3D, float* scales, float* rotations, float* opacities,
+                        void* stream);
+/* The gradients gsr_backward returns (dL_dmeans3D, dL_dscales, dL_drotations vec4[n]; the opacity's is
+ * dL_dconic_opacity[i].w) through those activations, to the raw arrays:
+ *   dL_draw_means[3 i + k]  = dL_dmeans3D[i][k]                                   k < 3
+ *   dL_draw_scales[3 i + k] = dL_dscales[i][k] * exp(s[k])                        k < 3
+ *   dL_draw_opacity[i]      = dL_dconic_opacity[i].w * sigmoid(x) * sigmoid(-x)
+ *   dL_draw_rotations[i]    = (g - q (q . g)) / |r|,  q = r / |r|,  g = dL_drotations[i]
+ * each formed in double from the float32 inputs and rounded to float once. Every output is optional: a NULL output is not
+ * computed or written, and the inputs only it reads may then be NULL too; an output that is given without its inputs, or a
+ * vector array that is not 16-byte aligned, is GSR_ERR_INVALID_ARG before any HIP call. radii (i32[n], the forward call's
+ * geomState.internal_radii, or NULL): a Gaussian with radii[i] <= 0 gets exact zeros in every output and nothing else of
+ * it is loaded. A zero quaternion has no gradient (NaN). n <= 0 is GSR_OK. Asynchronous on stream. */
+int gsr_activate_params_backward(int n, const float* raw_opacity, const float* raw_scales, const float* raw_rotations,
+                                 const int32_t* radii, const float* dL_dmeans3D, const float* dL_dscales,
+                                 const float* dL_drotations, const float* dL_dconic_opacity, float* dL_draw_means,
+                                 float* dL_draw_opacity, float* dL_draw_scales, float* dL_draw_rotations, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
