@@ -14,7 +14,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, backward_plan
+from .backward_plan import DEPTHS, INTO, ROW_FLOATS, SET
 from .camera import Camera
 
 
@@ -61,6 +62,55 @@ def _dev(a, device, dtype=torch.float32) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dtype).contiguous()
 
 
+class BackwardBuffers:
+    """The device memory one rasterizer's backward passes keep between calls, each piece created on first use.
+      sets      per semantics, the arrays a call without into= hands out ({name: [N, k]}, backward_plan.output_set), rebuilt
+                when with_cov3D changes. dL_dshs is 48 floats per Gaussian; the gscuda chain writes floats 0..15 of every
+                row, the inria chain all 48: it is zero-filled once, and the sets are kept per semantics so that a gscuda
+                call never returns what an inria call left in floats 16..47.
+      scratch   by name, everything else: the arrays the camera pass reads where neither the caller nor a set has them,
+                dL_ddepths (the only one a result names, and only without into=), sums_f64 [N,12] and depth_sums_f64 [N]
+                (created zero, left zero by the library, never cleared here), camera_scratch, camera_grad (view | proj | cam_pos)."""
+
+    def __init__(self, device: torch.device):
+        self.device, self.n = device, 0
+        self.sets: dict[str, dict[str, torch.Tensor]] = {}
+        self.scratch: dict[str, torch.Tensor] = {}
+
+    def fit(self, n: int) -> None:
+        """The one rule for "N changed": all of this is sized by N, so all of it goes."""
+        if n != self.n:
+            self.n = n
+            self.sets.clear()
+            self.scratch.clear()
+
+    def get(self, name: str, *shape, dtype=torch.float32, zero=False) -> torch.Tensor:
+        """scratch[name], created with `shape` on first use."""
+        if name not in self.scratch:
+            self.scratch[name] = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=self.device)
+        return self.scratch[name]
+
+    def take(self, plan: backward_plan.BackwardPlan, semantics: str, with_cov3D: bool, into: "dict | None") -> dict:
+        """{name: tensor} of every array `plan` gives a pointer, each from the source the plan names."""
+        own = None
+        if plan.takes_output_set:
+            own = self.sets.get(semantics)
+            if own is None or ("dL_dcov3D" in own) != with_cov3D:
+                own = self.sets[semantics] = {k: (torch.zeros if k == "dL_dshs" else torch.empty)(
+                    (self.n, ROW_FLOATS[k]), dtype=torch.float32, device=self.device) for k in backward_plan.output_set(with_cov3D)}
+        return {k: into[k] if source == INTO else own[k] if source == SET else
+                self.get(k, *((self.n,) if k == DEPTHS else (self.n, ROW_FLOATS[k]))) for k, source in plan.sources.items()}
+
+
+# gsr_forward_args.plan_used beside the plan's name: the attribute of the rasterizer that draw() sets from each bit
+_PLAN_USED_FLAGS = (("last_blend_from_lists", _capi.GSR_PLAN_BLEND_FROM_LISTS),    # (block plan only: the blend read the sorted lists — sparse frames — instead of the block lists)
+                    ("last_tiles_reordered", _capi.GSR_PLAN_TILES_REORDERED),
+                    ("last_tile_order_dropped", _capi.GSR_PLAN_TILE_ORDER_DROPPED),
+                    ("last_emit_overlapped", _capi.GSR_PLAN_EMIT_OVERLAPPED),
+                    ("last_colors_beside", _capi.GSR_PLAN_COLORS_BESIDE),
+                    ("last_deep_tiles", _capi.GSR_PLAN_DEEP_TILES))
+
+
 class SplatRasterizer:
     """Uploads a scene once and renders it per camera through gsr_forward."""
 
@@ -82,10 +132,18 @@ class SplatRasterizer:
         self.last_num_rendered = 0
         self.last_records_staged = 0
         self.last_plan = "none"
-        self.last_blend_from_lists = False
+        for name, _ in _PLAN_USED_FLAGS:            # last_blend_from_lists, last_tiles_reordered, ...: of the last draw()
+            setattr(self, name, False)
         self.last_lists_written = True
         self.last_receipt: _capi.ForwardReceipt | None = None      # of the last draw(): what backward() / poll take
         self.last_stage_ms: dict[str, float] = {}
+        self.last_backward_ms: tuple = ()              # (render, chain) of the last backward(profile=True)
+        self.last_camera_ms: "float | None" = None     # of the last camera_backward(profile=True)
+        self.rects: torch.Tensor | None = None
+        self._bw = BackwardBuffers(self.device)
+        # which colours a draw() composited (backward() reads the same ones): (that call's receipt serial, tensor or None)
+        self._colors_of_call: "tuple[int | None, torch.Tensor | None]" = (None, None)
+        self._means3: torch.Tensor | None = None       # draw_points' copy of the centres, three floats each
         # view (16) | proj (16) | cam_pos (3): one device buffer, uploaded with one async copy from pinned memory
         self._cam_dev = torch.zeros(35, dtype=torch.float32, device=self.device)
         self._cam_host = torch.zeros(35, dtype=torch.float32).pin_memory()
@@ -100,8 +158,10 @@ class SplatRasterizer:
         with torch.cuda.device(self.device):
             _capi.check(self.lib.gsr_tile_history_create(C.byref(self._history)), "gsr_tile_history_create")
 
+    _history = None             # (until __init__ has created it: __del__ also runs after an __init__ that raised)
+
     def __del__(self):
-        h, self._history = getattr(self, "_history", None), None
+        h, self._history = self._history, None
         if h is not None and h.value:
             try:
                 torch.cuda.synchronize(self.device)          # (the streams it was used on must be idle)
@@ -139,10 +199,9 @@ class SplatRasterizer:
         self.means3D, self.scales, self.rotations, self.opacities, self.shs = means3D, scales, rotations, opacities, shs
         if use_rects is None:
             use_rects = self.use_rects
-        have = getattr(self, "rects", None)
         if not use_rects:
             self.rects = None
-        elif have is None or have.shape[0] != n:
+        elif self.rects is None or self.rects.shape[0] != n:
             self.rects = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
         self.use_rects = use_rects
         self.num_gaussians = n
@@ -177,6 +236,21 @@ class SplatRasterizer:
         self._state_epoch += 1
 
     # -- one frame --------------------------------------------------------------------
+    def _forward_args(self, means3D: torch.Tensor, out_color: torch.Tensor) -> _capi.ForwardArgs:
+        """gsr_forward_args as draw() and draw_points() both fill it; every other field is zero."""
+        a = _capi.ForwardArgs()
+        a.struct_size = C.sizeof(_capi.ForwardArgs)
+        a.geometry_alloc, a.binning_alloc, a.image_alloc = self.geom.callback, self.binning.callback, self.image.callback
+        a.num_gaussians, a.sh_dims, a.M = self.num_gaussians, 3, 16
+        a.background = self.background.data_ptr()
+        a.width, a.height = self.width, self.height
+        a.means3D, a.shs = means3D.data_ptr(), self.shs.data_ptr()
+        a.view_matrix, a.proj_matrix, a.cam_pos = self._view.data_ptr(), self._proj.data_ptr(), self._cam_pos.data_ptr()
+        a.tan_fovx, a.tan_fovy = self._tan
+        a.out_color = out_color.data_ptr()
+        a.stream = torch.cuda.current_stream(self.device).cuda_stream
+        return a
+
     def draw(self, cam: Camera | None = None, *, profile: bool = False, count_staged: bool = False,
              tile_rows: tuple[int, int] | None = None, scale_modifier: float = 1.0,
              sync: bool = True, semantics: str = "gscuda", sh_degree: int = 3, plan: str = "auto",
@@ -222,8 +296,7 @@ class SplatRasterizer:
                     assert tuple(t.shape) == shape, (k, tuple(t.shape))
             out_color = into.get("out_color", out_color)
             out_depth = into.get("out_depth")
-        a = _capi.ForwardArgs()
-        a.struct_size = C.sizeof(_capi.ForwardArgs)
+        a = self._forward_args(self.means3D, out_color)
         inria = semantics == "inria"
         assert semantics in ("gscuda", "inria")
         a.flags = ((_capi.GSR_FLAG_PROFILE if profile else 0) | (_capi.GSR_FLAG_COUNT_STAGED if count_staged else 0)
@@ -236,11 +309,8 @@ class SplatRasterizer:
                       False: _capi.GSR_FLAG_NO_DEEP_TILES, None: 0}[deep_tiles]
                    | (_capi.GSR_FLAG_DEPTH_INVERSE if depth == "inverse" else 0))
         assert depth in (False, True, "inverse"), depth
-        a.geometry_alloc, a.binning_alloc, a.image_alloc = self.geom.callback, self.binning.callback, self.image.callback
-        a.num_gaussians, a.sh_dims, a.M = self.num_gaussians, (sh_degree if inria else 3), 16
-        a.background = self.background.data_ptr()
-        a.width, a.height = self.width, self.height
-        a.means3D, a.shs = self.means3D.data_ptr(), self.shs.data_ptr()
+        if inria:
+            a.sh_dims = sh_degree
         if isinstance(colors_precomp, torch.Tensor):
             assert colors_precomp.shape == (self.num_gaussians, 3) and colors_precomp.dtype == torch.float32
             assert colors_precomp.device == self.device and colors_precomp.is_contiguous()
@@ -252,15 +322,7 @@ class SplatRasterizer:
         a.opacities, a.scales = self.opacities.data_ptr(), self.scales.data_ptr()
         a.scale_modifier = scale_modifier
         a.rotations = self.rotations.data_ptr()
-        a.cov3D_precomp = None
-        a.view_matrix, a.proj_matrix, a.cam_pos = self._view.data_ptr(), self._proj.data_ptr(), self._cam_pos.data_ptr()
-        a.tan_fovx, a.tan_fovy = self._tan
-        a.prefiltered = 0
-        a.out_color = out_color.data_ptr()
-        a.radii = None
         a.rects = self.rects.data_ptr() if (self.rects is not None and not inria) else None
-        a.box_min = a.box_max = None
-        a.stream = torch.cuda.current_stream(self.device).cuda_stream
         a.tile_history = self._history if tile_history is True else None
         if depth:
             if out_depth is None:
@@ -282,13 +344,8 @@ class SplatRasterizer:
         self.last_records_staged = int(a.records_staged)
         self.last_plan = _capi.PLAN_NAMES[int(a.plan_used) & 0xFF]
         self.last_lists_written = not (int(a.plan_used) & _capi.GSR_PLAN_LISTS_SKIPPED)
-        # block plan only: did the blend read the sorted lists (sparse frames) instead of the block lists
-        self.last_blend_from_lists = bool(int(a.plan_used) & _capi.GSR_PLAN_BLEND_FROM_LISTS)
-        self.last_tiles_reordered = bool(int(a.plan_used) & _capi.GSR_PLAN_TILES_REORDERED)
-        self.last_tile_order_dropped = bool(int(a.plan_used) & _capi.GSR_PLAN_TILE_ORDER_DROPPED)
-        self.last_emit_overlapped = bool(int(a.plan_used) & _capi.GSR_PLAN_EMIT_OVERLAPPED)
-        self.last_colors_beside = bool(int(a.plan_used) & _capi.GSR_PLAN_COLORS_BESIDE)
-        self.last_deep_tiles = bool(int(a.plan_used) & _capi.GSR_PLAN_DEEP_TILES)
+        for name, bit in _PLAN_USED_FLAGS:
+            setattr(self, name, bool(int(a.plan_used) & bit))
         self.last_stage_ms = {n: float(a.stage_ms[i]) for i, n in enumerate(_capi.STAGE_NAMES)} if profile else {}
         if sync:
             torch.cuda.current_stream(self.device).synchronize()
@@ -309,7 +366,6 @@ class SplatRasterizer:
     def tile_history_times(self):
         """(times, deep flags, deep count) of this object's history after its last call: numpy u32[tiles] in units of 10 ns,
         bool[tiles] (composited by four waves), and the number of deep tiles of the last sorted order (gsr_tile_history_times)."""
-        import numpy as np
         tiles = ((self.width + 15) // 16) * ((self.height + 15) // 16)
         out, deep = (C.c_uint32 * tiles)(), C.c_uint32(0)
         _capi.check(self.lib.gsr_tile_history_times(self._history, out, tiles, C.byref(deep)), "gsr_tile_history_times")
@@ -340,19 +396,9 @@ class SplatRasterizer:
         if cam is not None:
             self.set_camera(cam)
         self._state_epoch += 1
-        if getattr(self, "_means3", None) is None or self._means3.shape[0] != self.num_gaussians:
+        if self._means3 is None or self._means3.shape[0] != self.num_gaussians:
             self._means3 = self.means3D[:, :3].contiguous()        # this path reads a stride of three floats
-        a = _capi.ForwardArgs()
-        a.struct_size = C.sizeof(_capi.ForwardArgs)
-        a.geometry_alloc, a.binning_alloc, a.image_alloc = self.geom.callback, self.binning.callback, self.image.callback
-        a.num_gaussians, a.sh_dims, a.M = self.num_gaussians, 3, 16
-        a.background = self.background.data_ptr()
-        a.width, a.height = self.width, self.height
-        a.means3D, a.shs = self._means3.data_ptr(), self.shs.data_ptr()
-        a.view_matrix, a.proj_matrix, a.cam_pos = self._view.data_ptr(), self._proj.data_ptr(), self._cam_pos.data_ptr()
-        a.tan_fovx, a.tan_fovy = self._tan
-        a.out_color = self.out_color.data_ptr()
-        a.stream = torch.cuda.current_stream(self.device).cuda_stream
+        a = self._forward_args(self._means3, self.out_color)
         with torch.cuda.device(self.device):
             rc = self.lib.gsr_forward_points(C.byref(a))
         _capi.check(rc, "gsr_forward_points")
@@ -369,6 +415,35 @@ class SplatRasterizer:
                 "outColor": v(st.out_color, 3 * P, torch.float32).view(3, self.height, self.width)}
 
     # -- backward pass (BASELINE config 5; no counterpart in the reference) ------------------
+    def _backward_args(self, rcpt: "_capi.ForwardReceipt | None", col: "torch.Tensor | None", semantics: str,
+                       sh_degree: int) -> _capi.BackwardArgs:
+        """gsr_backward_args with what does not depend on the gradients asked for: the scene, the camera and what the forward
+        call of `rcpt` left in the three chunks (col: its precomputed colours, else its geomState.rgb)."""
+        n = self.num_gaussians
+        gst, ist, bst = _capi.GeometryState(), _capi.ImageState(), _capi.BinningState()
+        self.lib.gsr_geometry_from_chunk(self.geom.base(), n, C.byref(gst))
+        self.lib.gsr_image_from_chunk(self.image.base(), self.width * self.height, C.byref(ist))
+        num_rendered = int(rcpt.num_rendered) if rcpt is not None else self.last_num_rendered
+        self.lib.gsr_binning_from_chunk(self.binning.base(), num_rendered, C.byref(bst))
+        a = _capi.BackwardArgs()
+        a.struct_size = C.sizeof(_capi.BackwardArgs)
+        if semantics == "inria":
+            a.flags = _capi.GSR_FLAG_SEMANTICS_INRIA
+            a.cam_pos, a.shs, a.clamped, a.sh_dims = self._cam_pos.data_ptr(), self.shs.data_ptr(), gst.clamped, int(sh_degree)
+        a.num_gaussians, a.width, a.height = n, self.width, self.height
+        a.background = self.background.data_ptr()
+        a.means2D, a.conic_opacity, a.cov3D = gst.means2D, gst.conic_opacity, gst.cov3D
+        a.colors = col.data_ptr() if col is not None else gst.rgb
+        a.radii = gst.internal_radii
+        a.ranges, a.n_contrib, a.final_t = ist.ranges, ist.n_contrib, ist.accum_alpha
+        a.point_list = bst.values
+        a.means3D, a.view_matrix = self.means3D.data_ptr(), self._view.data_ptr()
+        a.tan_fovx, a.tan_fovy = self._tan
+        a.stream = torch.cuda.current_stream(self.device).cuda_stream
+        if rcpt is not None:
+            a.receipt = rcpt
+        return a
+
     def backward(self, dL_dout: torch.Tensor, *, profile: bool = False, with_cov3D: bool = True,
                  tile_rows: tuple[int, int] | None = None, scale_modifier: float = 1.0, semantics: str = "gscuda",
                  sh_degree: int = 3, receipt: "_capi.ForwardReceipt | None | bool" = None, wide_sums: bool = True,
@@ -388,7 +463,8 @@ class SplatRasterizer:
         "dL_dcov3D", "dL_dshs"); the others are neither computed nor written (the chain is bound by its writes) and
         absent from the result. The tensors are owned by this object and overwritten by the next call.
         dL_ddepth: (H, W) gradient w.r.t. the depth channel (gsr_backward_args.dL_dout_depth); the result then also holds
-        dL_ddepths [N] (w.r.t. each Gaussian's d_i) and dL_dmeans3D includes the term through z. depth: the channel's mode,
+        dL_ddepths [N] (w.r.t. each Gaussian's d_i; one buffer for both semantics, which any later call with a depth gradient, into= or
+        not, writes) and dL_dmeans3D includes the term through z. depth: the channel's mode,
         True or "inverse" (default: that of the last draw(depth=...), else True) — the backward recomputes d_i, so any
         draw() serves, whether or not it wrote out_depth.
         camera: the result also holds the gradients w.r.t. the camera, dL_dview_matrix (16,), dL_dproj_matrix (16,) and
@@ -402,145 +478,60 @@ class SplatRasterizer:
         is allocated for such a call; what the call needs beside them (dL_ddepths, the camera pass's inputs) is scratch
         of this object. dL_dshs under semantics="gscuda" must come zero-filled: that chain writes floats 0..15 of each row.
         sync=False: returns without waiting for the stream."""
-        assert semantics in ("gscuda", "inria")
         n, dev = self.num_gaussians, self.device
+        rcpt = self.last_receipt if receipt is None else (None if receipt is False else receipt)
+        col = self._colors_of(rcpt)
+        plan = backward_plan.plan_backward(semantics, with_cov3D, wide_sums, None if outputs is None else tuple(outputs),
+                                           None if into is None else tuple(into), dL_ddepth is not None, camera, col is not None)
         g = dL_dout.to(device=dev, dtype=torch.float32).contiguous()
         assert g.shape == (3, self.height, self.width)
-        gst, ist, bst = _capi.GeometryState(), _capi.ImageState(), _capi.BinningState()
-        self.lib.gsr_geometry_from_chunk(self.geom.base(), n, C.byref(gst))
-        self.lib.gsr_image_from_chunk(self.image.base(), self.width * self.height, C.byref(ist))
-        rcpt = self.last_receipt if receipt is None else (None if receipt is False else receipt)
-        num_rendered = int(rcpt.num_rendered) if rcpt is not None else self.last_num_rendered
-        self.lib.gsr_binning_from_chunk(self.binning.base(), num_rendered, C.byref(bst))
-        # output buffers are allocated once per scene and semantics and reused. dL_dshs is 48 floats per Gaussian; the
-        # gscuda chain writes floats 0..15 of every Gaussian, the inria chain all 48: the buffer is zero-filled once, and
-        # kept per semantics so that a gscuda call never returns what an inria call left in floats 16..47.
-        caches = self.__dict__.setdefault("_bw_out_by_semantics", {})
-        cache = caches.get(semantics)
-        shapes = {"dL_dmean2D": (n, 2), "dL_dconic_opacity": (n, 4), "dL_dcolors": (n, 3), "dL_dcov2D": (n, 4),
-                  "dL_dcov3D": (n, 6), "dL_dshs": (n, 48), "dL_dmeans3D": (n, 4), "dL_dscales": (n, 4), "dL_drotations": (n, 4)}
-        camera_into = None
-        if into is not None:
-            assert wide_sums and outputs is None, "into= needs wide_sums and replaces outputs="
-            into = dict(into)
-            camera_into = into.pop("camera", None)
-            assert set(into) <= set(shapes) and (with_cov3D or set(into) <= {"dL_dmean2D", "dL_dconic_opacity", "dL_dcolors"}), sorted(into)
-            for k, t in into.items():
-                assert t.dtype == torch.float32 and t.device == dev and t.is_contiguous() and tuple(t.shape) == shapes[k], k
-            # this object's scratch of such calls: never handed out
-            cache = self.__dict__.setdefault("_bw_into_scratch", {})
-            if cache and next(iter(cache.values())).shape[0] != n:
-                cache.clear()
-        elif cache is None or cache["dL_dmean2D"].shape[0] != n or ("dL_dcov3D" in cache) != with_cov3D:
-            cache = {"dL_dmean2D": torch.empty((n, 2), dtype=torch.float32, device=dev),
-                     "dL_dconic_opacity": torch.empty((n, 4), dtype=torch.float32, device=dev),
-                     "dL_dcolors": torch.empty((n, 3), dtype=torch.float32, device=dev)}
-            if with_cov3D:
-                cache["dL_dcov2D"] = torch.empty((n, 4), dtype=torch.float32, device=dev)     # (m00, m01, m11, 0): what the chain starts from
-                cache["dL_dcov3D"] = torch.empty((n, 6), dtype=torch.float32, device=dev)
-                cache["dL_dshs"] = torch.zeros((n, 48), dtype=torch.float32, device=dev)
-                for k in ("dL_dmeans3D", "dL_dscales", "dL_drotations"):
-                    cache[k] = torch.empty((n, 4), dtype=torch.float32, device=dev)
-            caches[semantics] = cache
-        out = cache
-        a = _capi.BackwardArgs()
-        a.struct_size = C.sizeof(_capi.BackwardArgs)
-        a.flags = (_capi.GSR_FLAG_PROFILE if profile else 0) | (_capi.GSR_FLAG_SEMANTICS_INRIA if semantics == "inria" else 0)
-        if semantics == "inria":
-            a.cam_pos, a.shs, a.clamped, a.sh_dims = self._cam_pos.data_ptr(), self.shs.data_ptr(), gst.clamped, int(sh_degree)
-        a.num_gaussians, a.width, a.height = n, self.width, self.height
-        a.background = self.background.data_ptr()
-        a.means2D, a.conic_opacity, a.cov3D = gst.means2D, gst.conic_opacity, gst.cov3D
-        serial, col = getattr(self, "_colors_of_call", (None, None))
-        if rcpt is not None and int(rcpt.serial) != serial:
-            col = None                               # a receipt of another call: that call's colours are its geomState.rgb
-        a.colors = col.data_ptr() if col is not None else gst.rgb
-        a.radii = gst.internal_radii
-        a.ranges, a.n_contrib, a.final_t = ist.ranges, ist.n_contrib, ist.accum_alpha
-        a.point_list = bst.values
-        a.means3D, a.view_matrix = self.means3D.data_ptr(), self._view.data_ptr()
-        a.tan_fovx, a.tan_fovy = self._tan
-        a.dL_dout_color = g.data_ptr()
+        for k, t in (into or {}).items():
+            if k != "camera":
+                assert t.dtype == torch.float32 and t.device == dev and t.is_contiguous(), k
+                assert tuple(t.shape) == (n, ROW_FLOATS[k]), k
+        mode = None
         if dL_ddepth is not None:
             gd = dL_ddepth.to(device=dev, dtype=torch.float32).contiguous()
             assert gd.shape == (self.height, self.width)
-            mode = depth if depth is not None else (self.last_depth or True)
-            assert mode in (True, "inverse"), mode
-            if mode == "inverse":
-                a.flags |= _capi.GSR_FLAG_DEPTH_INVERSE
+            mode = backward_plan.depth_mode(depth, self.last_depth)
+        self._bw.fit(n)
+        arrays = self._bw.take(plan, semantics, with_cov3D, into)
+        a = self._backward_args(rcpt, col, semantics, sh_degree)
+        a.flags |= (_capi.GSR_FLAG_PROFILE if profile else 0) | (_capi.GSR_FLAG_DEPTH_INVERSE if mode == "inverse" else 0)
+        a.dL_dout_color = g.data_ptr()
+        if dL_ddepth is not None:
             a.dL_dout_depth = gd.data_ptr()
-            if cache.get("dL_ddepths") is None or cache["dL_ddepths"].shape[0] != n:
-                cache["dL_ddepths"] = torch.empty((n,), dtype=torch.float32, device=dev)
-            a.dL_ddepths = cache["dL_ddepths"].data_ptr()
-            if wide_sums:
-                if getattr(self, "_depth_sums_f64", None) is None or self._depth_sums_f64.shape[0] != n:
-                    self._depth_sums_f64 = torch.zeros((n,), dtype=torch.float64, device=dev)     # (the library leaves it zero)
-                a.depth_sums_f64 = self._depth_sums_f64.data_ptr()
-        if into is not None:
-            out = into
-        elif outputs is not None:
-            assert wide_sums and set(outputs) <= set(cache), (outputs, sorted(cache))
-            out = {k: cache[k] for k in outputs}
-            if dL_ddepth is not None:
-                out["dL_ddepths"] = cache["dL_ddepths"]
-        # camera=True: the per-Gaussian arrays the camera pass reads are written whether or not the result names them
-        need = {}
-        if camera:
-            sh_colour = semantics == "inria" and col is None        # (colours from SH move with the camera position)
-            for k in ("dL_dmean2D", "dL_dcov2D") + (("dL_dcolors",) if sh_colour else ()):
-                if k not in out:
-                    if into is not None and cache.get(k) is None:
-                        cache[k] = torch.empty(shapes[k], dtype=torch.float32, device=dev)
-                    need[k] = cache.get(k)
-            if "dL_dcov2D" in need and need["dL_dcov2D"] is None:          # (with_cov3D=False: a buffer of its own)
-                if getattr(self, "_camera_cov2D", None) is None or self._camera_cov2D.shape[0] != n:
-                    self._camera_cov2D = torch.empty((n, 4), dtype=torch.float32, device=dev)
-                need["dL_dcov2D"] = self._camera_cov2D
-        ptr = lambda k: out[k].data_ptr() if k in out else (need[k].data_ptr() if k in need else None)
-        a.dL_dmean2D, a.dL_dconic_opacity = ptr("dL_dmean2D"), ptr("dL_dconic_opacity")
-        a.dL_dcolors = ptr("dL_dcolors")
-        a.dL_dcov3D = ptr("dL_dcov3D")
-        a.dL_dcov2D = ptr("dL_dcov2D")
+        for k, t in arrays.items():             # (the fields of gsr_backward_args carry the arrays' names)
+            setattr(a, k, t.data_ptr())
         if wide_sums:
-            if getattr(self, "_sums_f64", None) is None or self._sums_f64.shape[0] != n:
-                self._sums_f64 = torch.zeros((n, 12), dtype=torch.float64, device=dev)      # (the library leaves it zero)
-            a.sums_f64 = self._sums_f64.data_ptr()
-        a.dL_dshs = ptr("dL_dshs")
-        if with_cov3D:
+            a.sums_f64 = self._bw.get("sums_f64", n, 12, dtype=torch.float64, zero=True).data_ptr()
+            if dL_ddepth is not None:
+                a.depth_sums_f64 = self._bw.get("depth_sums_f64", n, dtype=torch.float64, zero=True).data_ptr()
+        if plan.chain_inputs:
             a.proj_matrix, a.scales, a.rotations = self._proj.data_ptr(), self.scales.data_ptr(), self.rotations.data_ptr()
             a.scale_modifier = scale_modifier
-            a.dL_dmeans3D, a.dL_dscales = ptr("dL_dmeans3D"), ptr("dL_dscales")
-            a.dL_drotations = ptr("dL_drotations")
-        a.stream = torch.cuda.current_stream(dev).cuda_stream
         if tile_rows is not None:
             a.tile_row_begin, a.tile_row_end = int(tile_rows[0]), int(tile_rows[1])
-        if rcpt is not None:
-            a.receipt = rcpt
         with torch.cuda.device(dev):
             rc = self.lib.gsr_backward(C.byref(a))
-        if rc != _capi.GSR_OK and wide_sums:
-            self._depth_sums_f64 = None
-            self._sums_f64 = None           # (a call that failed half way may have left sums behind: the next call starts from a zeroed scratch again)
+        if rc != _capi.GSR_OK and wide_sums:     # (a call that failed half way may have left sums behind: the next starts from zeroed ones)
+            self._bw.scratch.pop("sums_f64", None)
+            self._bw.scratch.pop("depth_sums_f64", None)
         _capi.check(rc, "gsr_backward")
         self.last_backward_ms = (float(a.stage_ms[0]), float(a.stage_ms[1])) if profile else ()
         if camera:
-            grads = {k: out[k] if k in out else need[k] for k in ("dL_dmean2D", "dL_dcov2D") + (("dL_dcolors",) if sh_colour else ())}
-            if dL_ddepth is not None:
-                grads["dL_ddepths"] = cache["dL_ddepths"]
-            inverse = bool(a.flags & _capi.GSR_FLAG_DEPTH_INVERSE)
-            cam_out = self.camera_backward(grads, semantics=semantics, sh_degree=sh_degree, shs_colour=sh_colour,
-                                           depth=("inverse" if inverse else True) if dL_ddepth is not None else None,
-                                           profile=profile, sync=False, into=camera_into)
-            if sync:
-                torch.cuda.current_stream(dev).synchronize()
-            res = {k: v for k, v in out.items() if dL_ddepth is not None or k != "dL_ddepths"}
-            res.update(cam_out)
-            return res
+            arrays.update(self.camera_backward({k: arrays[k] for k in plan.camera_inputs}, semantics=semantics,
+                                               sh_degree=sh_degree, shs_colour="dL_dcolors" in plan.camera_inputs, depth=mode,
+                                               profile=profile, sync=False, into=into["camera"] if plan.camera_into else None))
         if sync:
             torch.cuda.current_stream(dev).synchronize()
-        if dL_ddepth is None and "dL_ddepths" in out:
-            return {k: v for k, v in out.items() if k != "dL_ddepths"}
-        return out
+        return {k: arrays[k] for k in plan.result}
+
+    def _colors_of(self, rcpt: "_capi.ForwardReceipt | None") -> "torch.Tensor | None":
+        """The precomputed colours the draw() of `rcpt` composited, None where it took its geomState.rgb: they are recorded
+        with the call's serial, so a receipt of another call gets None (that call's colours are its geomState.rgb)."""
+        serial, col = self._colors_of_call
+        return col if rcpt is None or int(rcpt.serial) == serial else None
 
     def camera_backward(self, grads: dict, *, semantics: str = "gscuda", sh_degree: int = 3, depth: "bool | str | None" = None,
                         shs_colour: "bool | None" = None, receipt: "_capi.ForwardReceipt | None" = None,
@@ -559,18 +550,12 @@ class SplatRasterizer:
         n, dev = self.num_gaussians, self.device
         inria = semantics == "inria"
         if shs_colour is None:
-            serial, col = getattr(self, "_colors_of_call", (None, None))
-            rcpt = self.last_receipt if receipt is None else receipt
-            if rcpt is not None and int(rcpt.serial) != serial:
-                col = None                           # a receipt of another call: that call's colours are its geomState.rgb
-            shs_colour = inria and col is None
+            shs_colour = inria and self._colors_of(self.last_receipt if receipt is None else receipt) is None
         gst = _capi.GeometryState()
         self.lib.gsr_geometry_from_chunk(self.geom.base(), n, C.byref(gst))
-        nbytes = int(self.lib.gsr_camera_backward_scratch_bytes(n))
-        if getattr(self, "_camera_scratch", None) is None or self._camera_scratch.numel() != nbytes:
-            self._camera_scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        if getattr(self, "_camera_grad", None) is None:
-            self._camera_grad = torch.empty((35,), dtype=torch.float32, device=dev)    # view 16 | proj 16 | cam_pos 3
+        self._bw.fit(n)
+        scratch = self._bw.get("camera_scratch", int(self.lib.gsr_camera_backward_scratch_bytes(n)), dtype=torch.uint8)
+        g = self._bw.get("camera_grad", 35)
 
         def ptr(k):
             t = grads[k]
@@ -591,12 +576,11 @@ class SplatRasterizer:
         a.dL_dmean2D, a.dL_dcov2D = ptr("dL_dmean2D"), ptr("dL_dcov2D")
         if depth:
             a.dL_ddepths = ptr("dL_ddepths")
-        g = self._camera_grad
         if into is not None:
             assert into.dtype == torch.float32 and into.device == dev and into.is_contiguous() and tuple(into.shape) == (35,)
             g = into
         a.dL_dview_matrix, a.dL_dproj_matrix, a.dL_dcam_pos = g[0:16].data_ptr(), g[16:32].data_ptr(), g[32:35].data_ptr()
-        a.scratch = self._camera_scratch.data_ptr()
+        a.scratch = scratch.data_ptr()
         a.stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
             rc = self.lib.gsr_camera_backward(C.byref(a))

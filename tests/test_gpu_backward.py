@@ -365,12 +365,12 @@ def test_double_sums_are_reproducible_and_agree_with_the_float_sums():
     r.draw(camera.default_camera(w, h, near=0.05, far=50.0))
     dL = torch.randn((3, h, w), generator=torch.Generator().manual_seed(5)).cuda()
     a = {k: v.clone() for k, v in r.backward(dL, wide_sums=True).items()}
-    assert float(r._sums_f64.abs().max()) == 0.0                 # left zero for the next call
+    assert float(r._bw.scratch["sums_f64"].abs().max()) == 0.0                 # left zero for the next call
     b = {k: v.clone() for k, v in r.backward(dL, wide_sums=True).items()}
     for k in a:
         assert torch.equal(a[k], b[k]), k
     base = {k: v.clone() for k, v in r.backward(dL, wide_sums=True, with_cov3D=False).items()}
-    assert float(r._sums_f64.abs().max()) == 0.0
+    assert float(r._bw.scratch["sums_f64"].abs().max()) == 0.0
     for k in ("dL_dmean2D", "dL_dconic_opacity", "dL_dcolors"):
         assert torch.equal(base[k], a[k]), k                     # the same sums whether or not the chain runs behind them
     f = r.backward(dL, wide_sums=False)
@@ -400,7 +400,7 @@ def test_optional_outputs_give_the_same_numbers_and_leave_the_others_alone():
     dL = torch.randn((3, h, w), generator=torch.Generator().manual_seed(6)).cuda()
     full = {k: v.clone() for k, v in r.backward(dL).items()}
     assert all(float(v.abs().max()) > 0 for v in full.values())
-    cache = r._bw_out_by_semantics["gscuda"]
+    cache = r._bw.sets["gscuda"]
     for subset in (("dL_dmean2D", "dL_dcov3D", "dL_dshs"),
                    ("dL_dmean2D", "dL_dconic_opacity", "dL_dshs", "dL_dmeans3D", "dL_dscales", "dL_drotations"),
                    ("dL_dmeans3D",), ("dL_dcolors",), ("dL_dshs",)):
@@ -414,7 +414,7 @@ def test_optional_outputs_give_the_same_numbers_and_leave_the_others_alone():
         for k, v in cache.items():
             if k not in subset and k != "dL_dshs":
                 assert bool((v == 7.0).all()), (subset, k)     # not asked for: not written
-        assert float(r._sums_f64.abs().max()) == 0.0
+        assert float(r._bw.scratch["sums_f64"].abs().max()) == 0.0
     with pytest.raises(AssertionError):
         r.backward(dL, outputs=("dL_dcov3D",), wide_sums=False)
     # the C ABI itself: without sums_f64 the three arrays of the sums are required
@@ -448,3 +448,110 @@ def test_backward_of_a_frame_without_instances_is_all_zero():
     out = r.backward(dl)
     for k, v in out.items():
         assert float(v.abs().sum()) == 0.0, k
+
+
+# ---- SplatRasterizer.backward()'s host side: who owns which buffer, and for how long (128 x 96, forty Gaussians) ---------
+_W, _H = 128, 96
+_CAM_KEYS = ("dL_dview_matrix", "dL_dproj_matrix", "dL_dcam_pos")
+
+
+def _small(n, **draw):
+    """(rasterizer with n Gaussians drawn once, dL [3,H,W], depth gradient [H,W])"""
+    import torch
+    from gsrast_amd import camera
+    from gsrast_amd.rasterizer import SplatRasterizer
+    from helpers import single_gaussian_scene
+    r = SplatRasterizer(_W, _H)
+    r.configure_from_scene(single_gaussian_scene(n=n, scale=0.3))
+    r.draw(camera.default_camera(_W, _H), **draw)
+    gen = torch.Generator().manual_seed(11)
+    return r, torch.randn((3, _H, _W), generator=gen).cuda(), torch.randn((_H, _W), generator=gen).cuda()
+
+
+def _redraw(r, n, **draw):
+    from gsrast_amd import camera
+    from helpers import single_gaussian_scene
+    r.configure_from_scene(single_gaussian_scene(n=n, scale=0.3))
+    r.draw(camera.default_camera(_W, _H), **draw)
+
+
+@pytest.fixture(scope="module")
+def fresh_24():
+    """backward(depth gradient, camera) of an object that has seen the 24-Gaussian scene only: computed once, not written again.
+    (sorted lists: every sum in double, so the bits do not depend on the order of arrival)"""
+    r, dL, gd = _small(24, plan="sort", tile_history=False)
+    res = {k: v.clone() for k, v in r.backward(dL, dL_ddepth=gd, camera=True).items()}
+    assert float(res["dL_dmeans3D"].abs().max()) > 0 and float(res["dL_dview_matrix"].abs().max()) > 0
+    return res
+
+
+def test_results_are_this_objects_buffers_call_after_call():
+    """"Owned by this object and overwritten by the next call": two calls return the same memory under each name."""
+    r, dL, gd = _small(40)
+    for kw in (dict(), dict(outputs=("dL_dmean2D", "dL_dcov3D", "dL_dshs")), dict(dL_ddepth=gd, camera=True),
+               dict(with_cov3D=False)):
+        first = {k: v.data_ptr() for k, v in r.backward(dL, **kw).items()}
+        again = {k: v.data_ptr() for k, v in r.backward(dL, **kw).items()}
+        assert list(first) == list(again) and first == again, kw
+        if "outputs" in kw:
+            assert list(first) == list(kw["outputs"])
+
+
+def test_into_calls_allocate_none_of_the_output_sets():
+    """A rasterizer that only ever makes into= calls (the trainer's five, camera and depth gradient) keeps no output set for
+    either semantics; its results are the caller's tensors and the camera's three views of into["camera"]."""
+    import torch
+    from gsrast_amd import camera
+    r, dL, gd = _small(40)
+    n = r.num_gaussians
+    five = {"dL_dmeans3D": 4, "dL_dscales": 4, "dL_drotations": 4, "dL_dconic_opacity": 4, "dL_dshs": 48}
+    for semantics in ("gscuda", "inria", "gscuda"):
+        r.draw(camera.default_camera(_W, _H), semantics=semantics)
+        into = {k: torch.zeros((n, c), device="cuda") for k, c in five.items()}
+        into["camera"] = torch.zeros(35, device="cuda")
+        res = r.backward(dL, semantics=semantics, dL_ddepth=gd, camera=True, into=into)
+        assert list(res) == list(five) + list(_CAM_KEYS) and "dL_ddepths" not in res
+        for k in five:
+            assert res[k].data_ptr() == into[k].data_ptr(), k
+        base = into["camera"].data_ptr()
+        assert [res[k].data_ptr() - base for k in _CAM_KEYS] == [0, 64, 128]
+        assert [tuple(res[k].shape) for k in _CAM_KEYS] == [(16,), (16,), (3,)]
+        assert float(res["dL_dmeans3D"].abs().max()) > 0 and float(into["camera"].abs().max()) > 0
+    assert r._bw.sets == {}
+
+
+def test_a_change_of_N_gives_the_bits_of_a_fresh_object(fresh_24):
+    """One rule for "N changed": after forty Gaussians, twenty-four give what an object that never saw the forty gives."""
+    import torch
+    r, dL, gd = _small(40, plan="sort", tile_history=False)
+    big = r.backward(dL, dL_ddepth=gd, camera=True)
+    assert big["dL_dmeans3D"].shape == (40, 4) and big["dL_ddepths"].shape == (40,)
+    _redraw(r, 24, plan="sort", tile_history=False)
+    got = r.backward(dL, dL_ddepth=gd, camera=True)
+    fresh = fresh_24
+    assert list(got) == list(fresh)
+    for k, v in got.items():
+        assert v.shape == fresh[k].shape and (k in _CAM_KEYS or v.shape[0] == 24), k
+        assert torch.equal(v, fresh[k]), k
+    assert r._bw.scratch["sums_f64"].shape == (24, 12) and r._bw.scratch["depth_sums_f64"].shape == (24,)
+    assert bool((r._bw.scratch["sums_f64"] == 0).all()) and bool((r._bw.scratch["depth_sums_f64"] == 0).all())
+
+
+def test_a_refused_call_drops_both_double_sums(fresh_24):
+    """gsr_backward refuses the receipt of a frame of another N (an error return, before anything is launched): both scratches
+    of the double sums are dropped, and the next call gives the bits of a fresh object."""
+    import torch
+    from gsrast_amd import _capi
+    r, dL, gd = _small(40, plan="sort", tile_history=False)
+    stale = r.last_receipt.copy()
+    _redraw(r, 24, plan="sort", tile_history=False)
+    r.backward(dL, dL_ddepth=gd, camera=True)
+    assert "sums_f64" in r._bw.scratch and "depth_sums_f64" in r._bw.scratch
+    with pytest.raises(_capi.GsrError) as e:
+        r.backward(dL, dL_ddepth=gd, camera=True, receipt=stale)
+    assert e.value.code == _capi.GSR_ERR_INVALID_ARG
+    assert "sums_f64" not in r._bw.scratch and "depth_sums_f64" not in r._bw.scratch
+    got = r.backward(dL, dL_ddepth=gd, camera=True)
+    for k, v in fresh_24.items():
+        assert torch.equal(got[k], v), k
+    assert bool((r._bw.scratch["sums_f64"] == 0).all()) and bool((r._bw.scratch["depth_sums_f64"] == 0).all())

@@ -132,4 +132,4 @@ def test_depth_sums_are_reproducible_and_left_zero():
                     assert np.array_equal(run[k], runs[0][k]), (kw, k)
                 else:
                     _close(run[k], runs[0][k].astype(np.float64), f"{kw} {k}", rtol=1e-5)
-        assert bool((r._depth_sums_f64 == 0).all()) and bool((r._sums_f64 == 0).all())
+        assert bool((r._bw.scratch["depth_sums_f64"] == 0).all()) and bool((r._bw.scratch["sums_f64"] == 0).all())
