@@ -151,6 +151,20 @@ class CameraBackwardArgs(C.Structure):
     ]
 
 
+GSR_ADAM_MAX_TENSORS = 8
+
+
+class AdamTensor(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("row_floats", C.c_int32), ("step_size", C.c_float), ("rs", C.c_float), ("b1c", C.c_float),
+                ("b2", C.c_float), ("b2c", C.c_float), ("eps", C.c_float)]
+
+
+class AdamArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("num_tensors", C.c_int32), ("num_rows", C.c_int64),
+                ("visible", C.c_void_p), ("stream", C.c_void_p), ("tensors", AdamTensor * GSR_ADAM_MAX_TENSORS)]
+
+
 # name -> (restype, argtypes); this is also the list the symbol test checks against the header.
 SIGNATURES = {
     "gsr_geometry_from_chunk": (C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(GeometryState)]),
@@ -202,6 +216,7 @@ SIGNATURES = {
                                           C.c_int, C.c_void_p]),
     "gsr_activate_params": (C.c_int, [C.c_int] + [C.c_void_p] * 9),
     "gsr_activate_params_backward": (C.c_int, [C.c_int] + [C.c_void_p] * 13),
+    "gsr_adam_step": (C.c_int, [C.POINTER(AdamArgs)]),
 }
 
 _lib = None

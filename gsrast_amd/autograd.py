@@ -316,15 +316,16 @@ def _camera_tensors(camera, dev):
 
 
 def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: str = "gscuda", sh_degree: int = 3,
-           scale_modifier: float = 1.0, depth: "bool | str" = False, **draw_options):
+           scale_modifier: float = 1.0, depth: "bool | str" = False, radii_slot: "RadiiSlot | None" = None, **draw_options):
     """`activate` then `rasterize`: (color [3,H,W], depth [H,W] or None, opacity_map [H,W]) of `params` seen from `camera`
     — a Camera (its matrices are uploaded once per device and kept with it; write to a Camera's arrays and it must be a new
     object) or a tuple (view, proj, cam_pos, tan_fovx, tan_fovy) whose first three are device tensors, which may require
     gradients. `loss.backward()` fills params.*.grad (and the camera tensors' .grad). Gaussians the frame culled get zero
-    gradients without their rows being read."""
+    gradients without their rows being read. radii_slot: a RadiiSlot of the caller's, used instead of the call's own; after
+    the call its `.radii` is the frame's radii (i32[N], a new tensor per frame) — what optim.GaussianAdam.step() takes."""
     if semantics == "inria" and sh_degree >= 1:
         assert params.sh_layout == "coefficient_major", 'semantics="inria" reads shs as [N][16][3]: sh_layout="coefficient_major"'
-    slot = RadiiSlot()
+    slot = radii_slot if radii_slot is not None else RadiiSlot()
     means3D, scales, rotations, opacities = params.activated(slot)
     view, proj, cam_pos, tan_fovx, tan_fovy = _camera_tensors(camera, rast.device)
     return rasterize(rast, means3D, scales, rotations, opacities, params.shs, view, proj, cam_pos, (tan_fovx, tan_fovy),

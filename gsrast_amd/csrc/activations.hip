@@ -13,35 +13,10 @@
 // LDS region, where every lane finds its own three floats at a stride of three words (no bank conflict: 3 is odd).
 #include "activation_math.hpp"
 #include "gsr_common.hpp"
+#include "wave_triples.hpp"      // (stage_triples / flush_triples)
 
 namespace gsr {
 namespace {
-
-constexpr int kTriple = 3 * kWave;        // floats of one wave's records in an array of three floats per Gaussian
-
-// The wave's `count` records of three floats, global -> LDS. `src` is 16-byte aligned (the array is, and a wave starts at a
-// multiple of 768 bytes). `wanted`: bit r set = record r is read afterwards; a vector none of whose floats is wanted is
-// not loaded.
-__device__ __forceinline__ void stage_triples(const float* __restrict__ src, int count, float* w, int lane, unsigned long long wanted) {
-    const int nfloats = 3 * count, bulk = nfloats & ~3;
-    const int f = 4 * lane;
-    if (f < bulk) {
-        const int r0 = f / 3, r1 = (f + 3) / 3;                              // (f + 3 <= 191: record 63 at most)
-        if (((wanted >> r0) | (wanted >> r1)) & 1ull)
-            *reinterpret_cast<float4*>(w + f) = *reinterpret_cast<const float4*>(src + f);
-    }
-    const int t = bulk + lane;                                               // a partial wave's last one to three floats
-    if (t < nfloats && ((wanted >> (t / 3)) & 1ull)) w[t] = src[t];
-}
-
-// ... and LDS -> global: every float of the wave's records is written.
-__device__ __forceinline__ void flush_triples(float* __restrict__ dst, int count, const float* w, int lane) {
-    const int nfloats = 3 * count, bulk = nfloats & ~3;
-    const int f = 4 * lane;
-    if (f < bulk) *reinterpret_cast<float4*>(dst + f) = *reinterpret_cast<const float4*>(w + f);
-    const int t = bulk + lane;
-    if (t < nfloats) dst[t] = w[t];
-}
 
 __global__ __launch_bounds__(256) void activate_params_kernel(int n, const float* __restrict__ raw_means,
                                                               const float* __restrict__ raw_opacity,

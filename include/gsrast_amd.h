@@ -642,6 +642,46 @@ int gsr_activate_params_backward(int n, const float* raw_opacity, const float* r
                                  const float* dL_drotations, const float* dL_dconic_opacity, float* dL_draw_means,
                                  float* dL_draw_opacity, float* dL_draw_scales, float* dL_draw_rotations, void* stream);
 
+/* ---- the optimiser step over those raw parameters (csrc/adam.hip) ----
+ * One in-place Adam update of up to GSR_ADAM_MAX_TENSORS arrays that share a row count: array k has row_floats floats per
+ * row, a row being one Gaussian (3 / 1 / 3 / 4 / 48 for the five raw arrays). Per element, in float32 without contraction
+ * and in exactly this order, which is the definition of the result:
+ *   m' = m + b1c * (g - m)
+ *   v' = b2 * v + b2c * (g * g)
+ *   den = sqrtf(v') / rs + eps
+ *   p' = p - step_size * (m' / den)
+ * sqrtf and / are correctly rounded, so p', m', v' are a function of the inputs alone (not of the launch shape, the
+ * other arrays of the call, or `visible`); float32 denormals are not pinned. The six scalars are the caller's, per array,
+ * so that parameter groups with different rates, betas and eps share a call. For Adam at step t >= 1 (computed in double,
+ * each rounded to float once):
+ *   step_size = lr / (1 - beta1^t)   rs = sqrt(1 - beta2^t)   b1c = 1 - beta1   b2 = beta2   b2c = 1 - beta2   eps
+ * visible (i32[num_rows], device, or NULL): row i is updated iff visible[i] > 0 — a frame's radii can be passed as they
+ * are. A row that is not keeps the bits of param, exp_avg and exp_avg_sq, and its grad is never used (it may be NaN): of
+ * such a row the kernel reads the visibility word only, except where a 16-byte vector of a three-float array also holds
+ * floats of a visible neighbour; that vector is read and written back whole, the row's floats unchanged. NULL: every row.
+ * Refused with GSR_ERR_INVALID_ARG before any HIP call: a wrong struct_size, num_rows < 0, num_tensors outside
+ * 1..GSR_ADAM_MAX_TENSORS, and for any array a NULL among its four pointers, one that is not 16-byte aligned, or
+ * row_floats <= 0. More rows than one launch covers: GSR_ERR_TOO_LARGE. num_rows == 0 is GSR_OK and touches nothing.
+ * One launch, asynchronous on stream; the arrays must not overlap. */
+#define GSR_ADAM_MAX_TENSORS 8
+typedef struct gsr_adam_tensor {
+    float* param;                  /* f32[num_rows * row_floats], updated in place */
+    const float* grad;             /* f32[num_rows * row_floats] */
+    float* exp_avg;                /* m, updated in place */
+    float* exp_avg_sq;             /* v, updated in place */
+    int32_t row_floats;
+    float step_size, rs, b1c, b2, b2c, eps;
+} gsr_adam_tensor;
+typedef struct gsr_adam_args {
+    uint32_t struct_size;          /* = sizeof(gsr_adam_args) */
+    int32_t num_tensors;
+    int64_t num_rows;
+    const int32_t* visible;
+    void* stream;
+    gsr_adam_tensor tensors[GSR_ADAM_MAX_TENSORS];
+} gsr_adam_args;
+int gsr_adam_step(const gsr_adam_args* args);
+
 #ifdef __cplusplus
 }
 #endif
