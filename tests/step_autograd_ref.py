@@ -1,0 +1,309 @@
+"""The training step's forward, restated once in plain differentiable torch (float64 by default, CPU, no custom Function):
+raw parameters + camera tensors -> color [3,H,W] and depth [H,W]. torch.autograd differentiates the whole composition, so
+the gradient it gives owes nothing to oracle/backward_np.py, tests/camera_grad_ref.py, tests/activation_ref.py or to the
+way the tests stitch those together: a coupling missing from both the kernels and that stitching shows here.
+
+The semantics are those of oracle/oracle_np.py (profile "gscuda"), oracle/inria_np.py (profile "inria") and
+include/gsrast_amd.h (activations: csrc/activation_math.hpp; the depth channel). tests/test_step_autograd_cpu.py pins this
+forward to the oracles' images, and measures what float32 arithmetic alone does to its gradients (the table BOUNDS below).
+The frames it is used on — scene, camera, cases, loss weights — are tests/step_frames.py's.
+
+Differentiated: the activations; quaternion -> rotation -> cov3D with the modifier; t = V (x, y, z, 1); the clamp of
+t.x / t.z, t.y / t.z; J; cov2D = J W Sigma W^T J^T with each profile's focal lengths, the 0.3 dilation and the conic; each
+profile's pixel centre; each profile's colour; the blend front to back with the background through the final T; the depth
+channel.
+
+Structure (no gradient, passed in as plain arrays so that the CPU oracle's state and the GPU's own state serve alike):
+  vis       bool[N]    radii > 0
+  ranges    int[T,2], values int[R]   each tile's list in order
+  nContrib  int[H,W]   each pixel's last contributor
+  clamped   bool[N,3]  the SH colour's clamp flags (upstream profile)
+  clx, cly  bool[N], sx, sy float[N]   the float32 clamp decisions on t.x / t.z, t.y / t.z and the side (clamp_decisions_f32)
+The decisions inside a pixel (alpha < 1/255, power > 0, the 0.99 clamp, the cut-off) are taken by the restatement itself
+in its own arithmetic, without gradient. A pixel on which one of them lies within a relative 1e-5 of its threshold, or
+whose last contributor differs from nContrib, is left out of the loss (pixels_to_drop).
+
+forward(..., cut=NAME) detaches exactly one coupling (CUTS): the blindness guards of the tests."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+F64, F32 = torch.float64, torch.float32
+RAW = ("xyz", "opacity_logit", "log_scale", "rotation", "shs")
+CUTS = ("background", "jacobian_mean", "view_direction", "depth_mean", "clamp_to_tz", "modifier", "quat_norm", "cov2D_view")
+
+SH_C0 = 0.28209479177387814
+SH_C1 = 0.4886025119029199
+SH_C2 = (1.0925484305920792, -1.0925484305920792, 0.31539156525252005, -1.0925484305920792, 0.5462742152960396)
+SH_C3 = (-0.5900435899266435, 2.890611442640554, -0.4570457994644658, 0.3731763325901154, -0.4570457994644658,
+         1.445305721320277, -0.5900435899266435)
+
+_f = lambda x: float(np.float32(x))
+ALPHA_MIN = float(np.float32(1.0) / np.float32(255.0))
+ALPHA_MAX = _f(0.99)
+MARGIN = 1e-5
+
+# The GPU bound of gradient array k of a case of tests/step_frames.py, as a share of the reference array's largest entry:
+# max(2e-4, 2 e32[k]), e32 = what float32 arithmetic alone does to the array on that frame (this restatement in float32
+# against itself in float64, same structure, same dropped pixels). 2e-4 is the RTOL of tests/test_gpu_backward*.py.
+# tests/test_step_autograd_cpu.py measures e32 and checks this table against it. Entries: (case, array) -> bound, for the
+# arrays whose 2 e32 exceeds the floor — none does (e32 is at most 3.5e-6): every array of every case is at the floor.
+FLOOR = 2e-4
+BOUNDS = {}
+
+
+def bound(case, array):
+    return BOUNDS.get((case, array), FLOOR)
+
+
+# ---- structure -----------------------------------------------------------------------------------------------------------------
+def clamp_decisions_f32(means3D, view, tan_fovx, tan_fovy):
+    """(clx, cly, sx, sy): is t.x / t.z (t.y / t.z) beyond +-1.3f tan_fov, and on which side — in float32, in the kernels'
+    operation order (as tests/camera_grad_ref.py forms them)."""
+    f = np.float32
+    v, m, one = np.asarray(view, f).reshape(16), np.asarray(means3D, f), f(1.0)
+    with np.errstate(all="ignore"):
+        tx = (v[0] * m[:, 0] + v[4] * m[:, 1]) + (v[8] * m[:, 2] + v[12] * one)
+        ty = (v[1] * m[:, 0] + v[5] * m[:, 1]) + (v[9] * m[:, 2] + v[13] * one)
+        tz = (v[2] * m[:, 0] + v[6] * m[:, 1]) + (v[10] * m[:, 2] + v[14] * one)
+        rx, ry = tx / tz, ty / tz
+        limx, limy = f(1.3) * f(tan_fovx), f(1.3) * f(tan_fovy)
+        cx, cy = np.minimum(limx, np.maximum(-limx, rx)), np.minimum(limy, np.maximum(-limy, ry))
+    return rx != cx, ry != cy, np.sign(rx).astype(np.float64), np.sign(ry).astype(np.float64)
+
+
+def structure_of(means3D, view, tan_fovx, tan_fovy, width, height, radii, ranges, values, n_contrib, clamped=None):
+    """The structure dict of forward() from a forward state's arrays (the CPU oracle's, or the GPU's read back)."""
+    n = np.asarray(radii).shape[0]
+    clx, cly, sx, sy = clamp_decisions_f32(np.asarray(means3D)[:, :3], view, tan_fovx, tan_fovy)
+
+    def u32(a):                                               # (the state's words are unsigned, whatever type carries them)
+        a = np.ascontiguousarray(a)
+        return (a.view(np.uint32) if a.dtype.itemsize == 4 else a).astype(np.int64)
+    return {"vis": np.asarray(radii) > 0,
+            "ranges": u32(ranges).reshape(-1, 2),
+            "values": u32(values).reshape(-1),
+            "nContrib": u32(n_contrib).reshape(height, width),
+            "clamped": np.zeros((n, 3), bool) if clamped is None else np.asarray(clamped, bool),
+            "clx": clx, "cly": cly, "sx": sx, "sy": sy}
+
+
+# ---- the differentiable forward ----------------------------------------------------------------------------------------------
+def leaves(raw, cam, dtype=F64, colors=False):
+    """The leaf tensors forward() is differentiated by: the raw parameters (and `colors` for the colors_precomp case) and the
+    three camera tensors, from their float32 values."""
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dtype).requires_grad_(True)
+    out = {k: t(raw[k]) for k in RAW}
+    if colors:
+        out["colors"] = t(raw["colors"])
+    out.update(view=t(cam.view), proj=t(cam.proj), cam_pos=t(cam.cam_pos))
+    return out
+
+
+def _sh_colour(deg, d, sh):
+    """0.5 + sum_k B_k(d) sh[k]: d [n,3] unit directions, sh [n,16,3]."""
+    x, y, z = d[:, 0:1], d[:, 1:2], d[:, 2:3]
+    res = SH_C0 * sh[:, 0]
+    if deg > 0:
+        res = res - SH_C1 * y * sh[:, 1] + SH_C1 * z * sh[:, 2] - SH_C1 * x * sh[:, 3]
+    if deg > 1:
+        xx, yy, zz, xy, yz, xz = x * x, y * y, z * z, x * y, y * z, x * z
+        res = (res + SH_C2[0] * xy * sh[:, 4] + SH_C2[1] * yz * sh[:, 5] + SH_C2[2] * (2.0 * zz - xx - yy) * sh[:, 6]
+               + SH_C2[3] * xz * sh[:, 7] + SH_C2[4] * (xx - yy) * sh[:, 8])
+    if deg > 2:
+        res = (res + SH_C3[0] * y * (3.0 * xx - yy) * sh[:, 9] + SH_C3[1] * xy * z * sh[:, 10]
+               + SH_C3[2] * y * (4.0 * zz - xx - yy) * sh[:, 11] + SH_C3[3] * z * (2.0 * zz - 3.0 * xx - 3.0 * yy) * sh[:, 12]
+               + SH_C3[4] * x * (4.0 * zz - xx - yy) * sh[:, 13] + SH_C3[5] * z * (xx - yy) * sh[:, 14]
+               + SH_C3[6] * x * (xx - 3.0 * yy) * sh[:, 15])
+    return res + 0.5
+
+
+def _rotation(q, profile):
+    """[n,3,3] (math rows / columns). gscuda: of (x, y, z, w) = q, which its preprocess has normalised; upstream: of the raw
+    (r, x, y, z) = q."""
+    if profile == "gscuda":
+        x, y, z, w = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+        rows = [[2.0 * (x * x + y * y) - 1.0, 2.0 * (y * z - x * w), 2.0 * (y * w + x * z)],
+                [2.0 * (y * z + x * w), 2.0 * (x * x + z * z) - 1.0, 2.0 * (z * w - x * y)],
+                [2.0 * (y * w - x * z), 2.0 * (z * w + x * y), 2.0 * (x * x + w * w) - 1.0]]
+    else:
+        r, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+        rows = [[1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - r * z), 2.0 * (x * z + r * y)],
+                [2.0 * (x * y + r * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - r * x)],
+                [2.0 * (x * z - r * y), 2.0 * (y * z + r * x), 1.0 - 2.0 * (x * x + y * y)]]
+    return torch.stack([torch.stack(row, 1) for row in rows], 1)
+
+
+def forward(leaf, structure, tan_fovx, tan_fovy, width, height, *, background, profile="gscuda", sh_degree=0,
+            scale_modifier=1.0, depth=False, cut=None):
+    """(color [3,H,W], depth [H,W] or None, aux). leaf: dict of tensors xyz [N,3], opacity_logit [N], log_scale [N,3],
+    rotation [N,4], shs [N,48], view [16], proj [16], cam_pos [3] and optionally colors [N,3] (composited as given, no SH).
+    aux: the activated tensors means3D [N,3], scales [N,3], rotations [N,4], opacities [N] (graph nodes: differentiate by them
+    for the gradients gsr_backward returns), finalT [H,W], last [H,W] (this forward's last contributor) and near [H,W]
+    (a decision of the pixel within MARGIN of its threshold), visible (the indices of the visible Gaussians), per_gaussian
+    (graph nodes over the visible Gaussians: mean2D [n,2], cov2D [n,3] = (a, b, c) dilated, colors [n,3], depths [n] or None —
+    what the blend reads, for the per-Gaussian sums of the render backward) and cov3D [n,6]."""
+    assert cut is None or cut in CUTS, cut
+    assert profile in ("gscuda", "inria") and depth in (False, True, "inverse")
+    inria = profile == "inria"
+    dt = leaf["xyz"].dtype
+    cst = lambda a: torch.as_tensor(np.asarray(a, np.float64)).to(dt)
+    # -- the activations
+    means3D = leaf["xyz"] * 1.0
+    scales = torch.exp(leaf["log_scale"])
+    norm = torch.sqrt((leaf["rotation"] * leaf["rotation"]).sum(1, keepdim=True))
+    rotations = leaf["rotation"] / (norm.detach() if cut == "quat_norm" else norm)
+    opacities = 1.0 / (1.0 + torch.exp(-leaf["opacity_logit"]))
+    aux = {"means3D": means3D, "scales": scales, "rotations": rotations, "opacities": opacities}
+    idx = torch.from_numpy(np.nonzero(structure["vis"])[0])
+    n = idx.numel()
+    m, s, q, o = means3D[idx], scales[idx], rotations[idx], opacities[idx]
+    # -- cov3D = R diag(mod s)^2 R^T
+    if not inria:
+        qn = torch.sqrt((q * q).sum(1, keepdim=True))
+        q = q / (qn.detach() if cut == "quat_norm" else qn)
+    R = _rotation(q, profile)
+    ms = s + (s * (scale_modifier - 1.0)).detach() if cut == "modifier" else scale_modifier * s
+    M = R * ms[:, None, :]
+    Sigma = M @ M.transpose(1, 2)
+    # -- t = V (x, y, z, 1)
+    V = leaf["view"].reshape(4, 4).T                         # V[r, c] = view[4 c + r]
+    t = m @ V[:3, :3].T + V[:3, 3]
+    tj = t.detach() if cut == "jacobian_mean" else t
+    tz = tj[:, 2]
+    limx, limy = float(np.float32(1.3) * np.float32(tan_fovx)), float(np.float32(1.3) * np.float32(tan_fovy))
+    clx, cly = (torch.from_numpy(structure[k])[idx] for k in ("clx", "cly"))
+    sx, sy = (cst(structure[k])[idx] for k in ("sx", "sy"))
+    tz_c = tz.detach() if cut == "clamp_to_tz" else tz
+    tx = torch.where(clx, sx * limx * tz_c, tj[:, 0])
+    ty = torch.where(cly, sy * limy * tz_c, tj[:, 1])
+    fy = float(np.float32(height) / (np.float32(2.0) * np.float32(tan_fovy)))
+    fx = float(np.float32(width) / (np.float32(2.0) * np.float32(tan_fovx))) if inria else fy
+    zero = torch.zeros_like(tz)
+    J = torch.stack([torch.stack([fx / tz, zero, -(fx * tx) / (tz * tz)], 1),
+                     torch.stack([zero, fy / tz, -(fy * ty) / (tz * tz)], 1)], 1)
+    Wm = V[:3, :3].detach() if cut == "cov2D_view" else V[:3, :3]
+    P = J @ Wm
+    cov = P @ Sigma @ P.transpose(1, 2)
+    cov2D = torch.stack([cov[:, 0, 0] + _f(0.3), cov[:, 0, 1], cov[:, 1, 1] + _f(0.3)], 1)
+    ca, cb, cc = cov2D[:, 0], cov2D[:, 1], cov2D[:, 2]
+    det = ca * cc - cb * cb
+    A, B, C = cc / det, -cb / det, ca / det
+    # -- the pixel centre
+    Pm = leaf["proj"].reshape(4, 4).T
+    h = m @ Pm[:, :3].T + Pm[:, 3]                            # (the activated mean's w is 1 under either profile)
+    if inria:
+        pw = 1.0 / (h[:, 3] + _f(0.0000001))
+        mx, my = ((h[:, 0] * pw + 1.0) * width - 1.0) * 0.5, ((h[:, 1] * pw + 1.0) * height - 1.0) * 0.5
+    else:
+        pw = 1.0 / (_f(0.001) + h[:, 3])
+        mx, my = (h[:, 0] * pw * 0.5 + 0.5) * width, (h[:, 1] * pw * 0.5 + 0.5) * height
+    mean2D = torch.stack([mx, my], 1)
+    mx, my = mean2D[:, 0], mean2D[:, 1]
+    # -- the colour
+    if "colors" in leaf:
+        rgb = leaf["colors"][idx]
+    elif inria:
+        dv = m - leaf["cam_pos"][None, :]
+        if cut == "view_direction":
+            dv = dv.detach()
+        d = dv / torch.sqrt((dv * dv).sum(1, keepdim=True))
+        raw_rgb = _sh_colour(min(3, max(0, int(sh_degree))), d, leaf["shs"][idx].reshape(n, 16, 3))
+        rgb = torch.where(torch.from_numpy(structure["clamped"])[idx], torch.zeros_like(raw_rgb), raw_rgb)
+    else:
+        rgb = 0.5 + 0.4 * leaf["shs"][idx][:, :3]
+    rgb = rgb * 1.0
+    # -- the depth values
+    dval = None
+    if depth:
+        dval = 1.0 / t[:, 2] if depth == "inverse" else t[:, 2]
+        if cut == "depth_mean":
+            dval = dval.detach()
+        dval = dval * 1.0
+    # -- the blend, tile by tile: [records, pixels]
+    local = np.full(structure["vis"].shape[0], -1, np.int64)
+    local[idx.numpy()] = np.arange(n)
+    gx, gy = (width + 15) // 16, (height + 15) // 16
+    cutoff = _f(1e-4) if inria else _f(0.001)
+    bg = cst(background)
+    color = torch.zeros((3, height, width), dtype=dt)
+    dmap = torch.zeros((height, width), dtype=dt) if depth else None
+    finalT = torch.ones((height, width), dtype=dt)
+    last = torch.zeros((height, width), dtype=torch.int64)
+    near = torch.zeros((height, width), dtype=torch.bool)
+    for tyi in range(gy):
+        for txi in range(gx):
+            r0, r1 = (int(v) for v in structure["ranges"][tyi * gx + txi])
+            ya, yb, xa, xb = tyi * 16, min(height, tyi * 16 + 16), txi * 16, min(width, txi * 16 + 16)
+            ids = torch.from_numpy(local[structure["values"][r0:r1]]) if r1 > r0 else torch.zeros(0, dtype=torch.int64)
+            assert (ids >= 0).all()
+            py, px = torch.meshgrid(torch.arange(ya, yb), torch.arange(xa, xb), indexing="ij")
+            px, py = px.reshape(-1).to(dt), py.reshape(-1).to(dt)
+            L, npx = ids.numel(), px.numel()
+            dx, dy = mx[ids][:, None] - px[None, :], my[ids][:, None] - py[None, :]
+            power = -0.5 * (A[ids][:, None] * dx * dx + C[ids][:, None] * dy * dy) - B[ids][:, None] * dx * dy
+            a_raw = o[ids][:, None] * torch.exp(power)
+            alpha = torch.clamp(a_raw, max=ALPHA_MAX)
+            with torch.no_grad():
+                skip = (power > 0) | (alpha < ALPHA_MIN)
+                a0 = torch.where(skip, torch.zeros_like(alpha), alpha)
+                T0 = torch.cat([torch.ones((1, npx), dtype=dt), torch.cumprod(1.0 - a0, 0)[:-1]], 0) if L else a0
+                test = T0 * (1.0 - a0)
+                stop = ~skip & (test < cutoff)
+                order = torch.arange(L)[:, None].expand(L, npx)
+                none = torch.zeros(npx, dtype=torch.int64)
+                first = torch.where(stop, order, torch.full_like(order, L)).min(0).values if L else none
+                dead = order >= first[None, :]
+                on = ~skip & ~dead                                        # the records the pixel composites
+                seen = order <= first[None, :]                            # the records whose decisions the pixel takes
+                close = lambda v, thr: (v - thr).abs() <= MARGIN * thr
+                nr = seen & ((power.abs() <= MARGIN) | close(a_raw, ALPHA_MIN)
+                             | (~skip & (close(a_raw, ALPHA_MAX) | close(test, cutoff))))
+                lst = torch.where(on, order + 1, torch.zeros_like(order)).max(0).values if L else none
+            a = torch.where(on, alpha, torch.zeros_like(alpha))
+            Tx = torch.cat([torch.ones((1, npx), dtype=dt), torch.cumprod(1.0 - a, 0)[:-1]], 0) if L else a
+            wgt = a * Tx
+            Tf = torch.prod(1.0 - a, 0) if L else torch.ones(npx, dtype=dt)
+            Tb = Tf.detach() if cut == "background" else Tf
+            shape = (yb - ya, xb - xa)
+            color[:, ya:yb, xa:xb] = ((wgt.T @ rgb[ids]).T + bg[:, None] * Tb[None, :]).reshape(3, *shape)
+            if depth:
+                dmap[ya:yb, xa:xb] = (wgt * dval[ids][:, None]).sum(0).reshape(shape)
+            finalT[ya:yb, xa:xb] = Tf.detach().reshape(shape)
+            last[ya:yb, xa:xb] = lst.reshape(shape)
+            near[ya:yb, xa:xb] = (nr.any(0) if L else torch.zeros(npx, dtype=torch.bool)).reshape(shape)
+    aux.update(finalT=finalT.numpy(), last=last.numpy(), near=near.numpy(), visible=idx.numpy(),
+               per_gaussian={"mean2D": mean2D, "cov2D": cov2D, "colors": rgb, "depths": dval},
+               cov3D=torch.stack([Sigma[:, 0, 0], Sigma[:, 0, 1], Sigma[:, 0, 2], Sigma[:, 1, 1], Sigma[:, 1, 2],
+                                  Sigma[:, 2, 2]], 1).detach())
+    return color, dmap, aux
+
+
+def pixels_to_drop(aux, structure):
+    """bool[H,W]: the pixels left out of the loss — a float64 decision within a relative 1e-5 of its threshold, or a last
+    contributor that differs from the forward state's nContrib. aux: of the uncut float64 forward()."""
+    return aux["near"] | (aux["last"] != structure["nContrib"])
+
+
+def gradients(leaf, structure, cam, w, wd, drop, dtype=F64, **forward_options):
+    """One step of the reference: forward(leaf, structure, <cam's tangents and size>, **forward_options), loss =
+    (w . color).sum() + (wd . depth).sum() with the dropped pixels' weights zero, and autograd. Returns (grads, color, depth,
+    aux) — grads: float64 numpy, keyed by the leaves' names, by "means3D", "scales", "rotations", "opacities" (the gradients
+    w.r.t. the activated arrays) and by "per_gaussian.mean2D" etc. (w.r.t. aux["per_gaussian"], rows in the order of
+    aux["visible"]); zeros where the loss does not depend on the tensor."""
+    depth = forward_options.get("depth", False)
+    color, dmap, aux = forward(leaf, structure, cam.tan_fovx, cam.tan_fovy, cam.width, cam.height, **forward_options)
+    keep = torch.from_numpy(~drop)
+    wt, wdt = torch.from_numpy(w).to(dtype) * keep, torch.from_numpy(wd).to(dtype) * keep
+    loss = (wt * color).sum() + ((wdt * dmap).sum() if depth else 0.0)
+    names = list(leaf) + ["means3D", "scales", "rotations", "opacities"]
+    tensors = [leaf[k] for k in leaf] + [aux[k] for k in names[len(leaf):]]
+    for k, t in aux["per_gaussian"].items():
+        if t is not None and t.requires_grad:
+            names.append("per_gaussian." + k)
+            tensors.append(t)
+    got = torch.autograd.grad(loss, tensors, allow_unused=True)
+    grads = {k: (g.detach().to(F64).numpy() if g is not None else np.zeros(tuple(t.shape)))
+             for k, g, t in zip(names, got, tensors)}
+    return grads, color.detach().to(F64).numpy(), (dmap.detach().to(F64).numpy() if depth else None), aux

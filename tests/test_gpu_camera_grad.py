@@ -1,7 +1,8 @@
 """GPU: gradients w.r.t. the camera (backward(camera=True), gsr_camera_backward). Checked against the float64 reference
 (tests/camera_grad_ref.py) applied to the library's own per-Gaussian gradients, end to end against the float64 blend
 backward (oracle/backward_np.py), for bit reproducibility, for tile-row bands adding up to the frame, at the edges (nothing
-visible, Gaussians behind the camera) and on the 5.8 M-splat bench scene."""
+visible, Gaussians behind the camera), on the 5.8 M-splat bench scene, and alone on synthetic per-Gaussian arrays at the sizes
+where the pass's loops take further turns."""
 import ctypes as C
 
 import numpy as np
@@ -275,3 +276,98 @@ def test_camera_grad_full_size():
     assert np.array_equal(_bits(first), _bits(second))
     exp, M = _reference(r, cam, out, "gscuda", True, 0, device=r.device)
     _assert_close(first, exp, M, "full size")
+
+
+# ---- the camera pass at its loop edges: gsr_camera_backward alone on synthetic per-Gaussian arrays -----------------------
+# camera_pass_kernel: a fixed grid of at most 768 x 256 threads, two Gaussians deep in flight (cur, nxt, r_after);
+# camera_sum_kernel: rows t, t + 256, ... Up to N = 65 536 the sum loop runs once, up to 196 608 the pass loop runs once, and
+# only beyond 393 216 does a thread reach a third iteration, where the radius loaded two iterations ahead is consumed.
+LOOP_EDGE_SIZES = [65_537, 196_609, 393_217 + 255]
+
+
+def _loop_edge_inputs(n, seed):
+    """Per-Gaussian arrays of n Gaussians in front of pose P1 (some beyond the +-1.3 tan(fov) clamp), PSD cov3D, random
+    gradients, shs and clamp flags; about half of the rows visible, whole waves culled in every iteration of the pass loop,
+    the last row visible. Every array of a culled row holds NaN (clamp flags: 255): a culled Gaussian loads nothing but its
+    radius."""
+    from helpers import posed_camera, world_from_view
+    cam = posed_camera(96, 64, eye=(2.0, -1.2, -4.2), target=(0.0, 0.0, 0.0), roll=0.4)
+    rng = np.random.default_rng(seed)
+    z = rng.uniform(1.0, 6.0, n)
+    t = np.stack([rng.uniform(-1.5, 1.5, n) * cam.tan_fovx * z, rng.uniform(-1.5, 1.5, n) * cam.tan_fovy * z, z], 1)
+    means = np.ones((n, 4), np.float32)
+    means[:, :3] = world_from_view(cam, t)
+    A = rng.normal(size=(n, 3, 3)) * 0.1
+    S = A @ A.transpose(0, 2, 1)
+    a = {"means3D": means,
+         "cov3D": np.stack([S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2]], 1).astype(np.float32),
+         "dL_dmean2D": rng.normal(size=(n, 2)).astype(np.float32),
+         "dL_dcov2D": np.concatenate([rng.normal(size=(n, 3)), np.zeros((n, 1))], 1).astype(np.float32),
+         "dL_ddepths": rng.normal(size=n).astype(np.float32),
+         "dL_dcolors": rng.normal(size=(n, 3)).astype(np.float32),
+         "shs": rng.normal(0, 0.35, (n, 48)).astype(np.float32)}
+    clamped = rng.uniform(size=(n, 3)) < 0.2
+    radii = np.where(rng.uniform(size=n) < 0.5, rng.integers(1, 9, n), 0).astype(np.int32)
+    stride = 768 * 256
+    for first in (128, 4096, stride + 64, stride + 32768, 2 * stride + 192):          # whole waves, in each iteration
+        if first + 64 <= n:
+            radii[first:first + 64] = 0
+    radii[-1] = 3
+    off = radii <= 0
+    for v in a.values():
+        v[off] = np.nan
+    flags = clamped.astype(np.uint8)
+    flags[off] = 255
+    return cam, a, radii, clamped, flags
+
+
+@pytest.mark.parametrize("semantics", ["gscuda", "inria"])
+@pytest.mark.parametrize("n", LOOP_EDGE_SIZES)
+def test_camera_pass_at_its_loop_edges(n, semantics):
+    """gsr_camera_backward on synthetic arrays at the sizes where the sum loop takes a second turn, the pass loop a second
+    and a third — in both instantiations (upstream: SH colour of degree 3, with an inverse-depth gradient). Finite although
+    the culled rows hold NaN; within 1e-6 M_k of the float64 reference computed on the device; the same bits twice."""
+    import torch
+    from gsrast_amd import _capi
+    inria = semantics == "inria"
+    cam, a, radii, clamped, flags = _loop_edge_inputs(n, seed=n % 1000)
+    off = radii <= 0
+    assert 0.4 * n < (~off).sum() < 0.6 * n and radii[-1] > 0
+    assert all(np.isnan(v[off]).all() for v in a.values())
+    dev = torch.device("cuda:0")
+    d = {k: torch.from_numpy(v).to(dev) for k, v in a.items()}
+    rad, flg = torch.from_numpy(radii).to(dev), torch.from_numpy(flags).to(dev)
+    view, proj, pos = (torch.from_numpy(np.asarray(v, np.float32).copy()).to(dev) for v in (cam.view, cam.proj, cam.cam_pos))
+    L = _capi.lib()
+    scratch = torch.empty(int(L.gsr_camera_backward_scratch_bytes(n)), dtype=torch.uint8, device=dev)
+    outs = []
+    for _ in range(2):
+        out = torch.full((35,), float("nan"), dtype=torch.float32, device=dev)
+        scratch.fill_(255)
+        args = _capi.CameraBackwardArgs()
+        args.struct_size = C.sizeof(_capi.CameraBackwardArgs)
+        args.flags = (_capi.GSR_FLAG_SEMANTICS_INRIA | _capi.GSR_FLAG_DEPTH_INVERSE) if inria else 0
+        args.num_gaussians, args.width, args.height = n, cam.width, cam.height
+        args.means3D, args.view_matrix, args.proj_matrix, args.cam_pos = (t.data_ptr() for t in (d["means3D"], view, proj, pos))
+        args.tan_fovx, args.tan_fovy = cam.tan_fovx, cam.tan_fovy
+        args.cov3D, args.radii = d["cov3D"].data_ptr(), rad.data_ptr()
+        if inria:
+            args.shs, args.clamped, args.sh_dims = d["shs"].data_ptr(), flg.data_ptr(), 3
+            args.dL_dcolors = d["dL_dcolors"].data_ptr()
+        args.dL_dmean2D, args.dL_dcov2D, args.dL_ddepths = (d[k].data_ptr() for k in ("dL_dmean2D", "dL_dcov2D", "dL_ddepths"))
+        args.dL_dview_matrix, args.dL_dproj_matrix, args.dL_dcam_pos = out[0:16].data_ptr(), out[16:32].data_ptr(), out[32:35].data_ptr()
+        args.scratch = scratch.data_ptr()
+        args.stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            _capi.check(L.gsr_camera_backward(C.byref(args)), "gsr_camera_backward")
+        torch.cuda.synchronize()
+        outs.append(out.cpu().numpy())
+    got = outs[0]
+    assert np.array_equal(_bits(outs[0]), _bits(outs[1]))
+    exp, M = camera_grad(d["means3D"], cam.view, cam.proj, cam.cam_pos, cam.tan_fovx, cam.tan_fovy, cam.width, cam.height, rad,
+                         d["cov3D"], d["dL_dmean2D"], d["dL_dcov2D"], dL_ddepths=d["dL_ddepths"], inverse=inria, inria=inria,
+                         shs=d["shs"] if inria else None, sh_degree=3, dL_dcolors=d["dL_dcolors"] if inria else None,
+                         clamped=torch.from_numpy(clamped).to(dev) if inria else None, device=dev)
+    _assert_close(got, exp, M, f"{semantics}, n = {n}")
+    assert M[:16].max() > 0 and M[16:32].max() > 0
+    assert (M[32:] > 0).all() if inria else (got[32:] == 0).all()
