@@ -165,6 +165,13 @@ class AdamArgs(C.Structure):
                 ("visible", C.c_void_p), ("stream", C.c_void_p), ("tensors", AdamTensor * GSR_ADAM_MAX_TENSORS)]
 
 
+class PhotoLossArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("channels", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("lambda_dssim", C.c_double), ("image", C.c_void_p), ("target", C.c_void_p), ("scratch", C.c_void_p),
+                ("out", C.c_void_p), ("dL_dloss", C.c_void_p), ("dL_dimage", C.c_void_p), ("want_backward", C.c_int32),
+                ("stream", C.c_void_p)]
+
+
 # name -> (restype, argtypes); this is also the list the symbol test checks against the header.
 SIGNATURES = {
     "gsr_geometry_from_chunk": (C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(GeometryState)]),
@@ -217,6 +224,9 @@ SIGNATURES = {
     "gsr_activate_params": (C.c_int, [C.c_int] + [C.c_void_p] * 9),
     "gsr_activate_params_backward": (C.c_int, [C.c_int] + [C.c_void_p] * 13),
     "gsr_adam_step": (C.c_int, [C.POINTER(AdamArgs)]),
+    "gsr_photo_loss_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "gsr_photo_loss_forward": (C.c_int, [C.POINTER(PhotoLossArgs)]),
+    "gsr_photo_loss_backward": (C.c_int, [C.POINTER(PhotoLossArgs)]),
 }
 
 _lib = None

@@ -682,6 +682,60 @@ typedef struct gsr_adam_args {
 } gsr_adam_args;
 int gsr_adam_step(const gsr_adam_args* args);
 
+/* ---- the photometric training loss and its gradient (csrc/photo_loss.hip) ----
+ * loss = (1 - lambda) * L1 + lambda * (1 - SSIM) of image against target, both f32[channels][height][width], and dloss /
+ * dimage. SSIM is the mean of the per-pixel map m below over an 11 x 11 Gaussian window, sigma 1.5, zero padded. All
+ * per-pixel arithmetic is float32 without contraction, / correctly rounded, in exactly this order, which is the definition
+ * of the result (it does not depend on the tile shape or the launch):
+ *   window   g[k] = exp(-(k - 5)^2 / 4.5) / sum, k = 0..10: computed and normalised in double, rounded to float once
+ *            (GSR_PHOTO_LOSS_WINDOW below spells the eleven floats out).
+ *   conv(a)  separable: h(r,c) = sum_k g[k] * a(r, c + k - 5), then conv(a)(r,c) = sum_k g[k] * h(r + k - 5, c); each sum is
+ *            acc = acc + g[k] * v from acc = 0.0f with k ascending; a tap outside the image contributes g[k] * 0.
+ *   per pixel and channel, x = image, y = target, C1 = 0.01^2, C2 = 0.03^2 (each rounded to float once):
+ *     mu1 = conv(x)   mu2 = conv(y)
+ *     s11 = conv(x*x) - mu1*mu1   s22 = conv(y*y) - mu2*mu2   s12 = conv(x*y) - mu1*mu2
+ *     a1 = 2*(mu1*mu2) + C1   a2 = 2*s12 + C2   b1 = (mu1*mu1 + mu2*mu2) + C1   b2 = (s11 + s22) + C2
+ *     m     = (a1*a2) / (b1*b2)
+ *     d_s12 = (2*a1) / (b1*b2)
+ *     d_s11 = -(m / b2)
+ *     d_mu1 = (2*mu2*a2) / (b1*b2) - (2*mu1*m) / b1
+ *     t_mu  = (d_mu1 - 2*mu1*d_s11) - mu2*d_s12
+ *   loss terms: the float values |x - y| and m are summed in DOUBLE, per workgroup and then over the workgroups' partial
+ *     sums in a fixed order (no floating-point atomic takes part: two runs give the same bits). In double, with n = channels *
+ *     height * width:  l1 = l1_sum / n,  ssim = ssim_sum / n,  loss = (1 - lambda) * l1 + lambda * (1 - ssim);  each of
+ *     the three is rounded to float once: out[3] = (loss, l1, ssim), on the device.
+ *   gradient: cs = -lambda / n and cl = (1 - lambda) / n (in double on the host, each rounded to float once), up =
+ *     *dL_dloss, read on the device:
+ *     S   = (conv(t_mu) + 2*x*conv(d_s11)) + y*conv(d_s12)
+ *     sgn = (x - y > 0) - (x - y < 0)
+ *     dL_dimage = up * (cs*S + cl*sgn)
+ * gsr_photo_loss_forward writes out and, with want_backward != 0, the three maps t_mu, d_s11, d_s12 into scratch;
+ * gsr_photo_loss_backward convolves them and writes dL_dimage. The caller owns scratch
+ * (gsr_photo_loss_scratch_bytes(channels, width, height) bytes: the workgroups' partial sums and the three maps) and keeps
+ * it, image and target unchanged between the two calls; the library keeps nothing. Both calls enqueue on stream and do not
+ * synchronise. Refused with GSR_ERR_INVALID_ARG before anything is launched: a wrong struct_size; channels, width or height
+ * below 1; lambda_dssim outside [0, 1] (or NaN); a NULL among image, target, scratch and (forward) out or (backward) dL_dloss,
+ * dL_dimage; image, target, scratch or dL_dimage not 16-byte aligned, out or dL_dloss not 4-byte aligned. More than 2^31 - 1
+ * floats per image, 65535 channels or 65535 * 16 rows: GSR_ERR_TOO_LARGE. Inputs are taken as finite. */
+#define GSR_PHOTO_LOSS_WINDOW { 0.00102838012f, 0.00759875821f, 0.0360007733f, 0.109360687f, 0.213005543f, 0.266011715f, \
+                                0.213005543f, 0.109360687f, 0.0360007733f, 0.00759875821f, 0.00102838012f }
+typedef struct gsr_photo_loss_args {
+    uint32_t struct_size;          /* = sizeof(gsr_photo_loss_args) */
+    int32_t channels, width, height;
+    double lambda_dssim;           /* a double, so that cs and cl are those of the caller's lambda and not of its float */
+    const float* image;            /* f32[channels][height][width] */
+    const float* target;
+    void* scratch;                 /* gsr_photo_loss_scratch_bytes(channels, width, height) bytes */
+    float* out;                    /* forward: f32[3] = (loss, l1, ssim) */
+    const float* dL_dloss;         /* backward: one float, the upstream gradient */
+    float* dL_dimage;              /* backward: f32[channels][height][width] */
+    int32_t want_backward;         /* forward: also write what the backward reads into scratch */
+    void* stream;
+} gsr_photo_loss_args;
+size_t gsr_photo_loss_scratch_bytes(int channels, int width, int height);     /* 0 for sizes the calls refuse */
+int gsr_photo_loss_forward(const gsr_photo_loss_args* args);
+int gsr_photo_loss_backward(const gsr_photo_loss_args* args);
+
 #ifdef __cplusplus
 }
 #endif
