@@ -172,6 +172,18 @@ class PhotoLossArgs(C.Structure):
                 ("stream", C.c_void_p)]
 
 
+class DensifyArray(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("src_exp_avg", C.c_void_p), ("src_exp_avg_sq", C.c_void_p),
+                ("dst", C.c_void_p), ("dst_exp_avg", C.c_void_p), ("dst_exp_avg_sq", C.c_void_p)]
+
+
+class DensifyApplyArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("log_shrink", C.c_float), ("n_src", C.c_int64), ("counts", C.c_int32 * 4),
+                ("src_of", C.c_void_p), ("noise", C.c_void_p), ("stream", C.c_void_p),
+                ("xyz", DensifyArray), ("opacity_logit", DensifyArray), ("log_scale", DensifyArray),
+                ("rotation", DensifyArray), ("shs", DensifyArray)]
+
+
 # name -> (restype, argtypes); this is also the list the symbol test checks against the header.
 SIGNATURES = {
     "gsr_geometry_from_chunk": (C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(GeometryState)]),
@@ -227,6 +239,11 @@ SIGNATURES = {
     "gsr_photo_loss_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "gsr_photo_loss_forward": (C.c_int, [C.POINTER(PhotoLossArgs)]),
     "gsr_photo_loss_backward": (C.c_int, [C.POINTER(PhotoLossArgs)]),
+    "gsr_densify_accumulate": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "gsr_densify_plan_temp_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_densify_plan": (C.c_int, [C.c_int64] + [C.c_void_p] * 5 + [C.c_float] * 5 + [C.c_int32] + [C.c_void_p] * 4),
+    "gsr_densify_apply": (C.c_int, [C.POINTER(DensifyApplyArgs)]),
 }
 
 _lib = None

@@ -45,6 +45,16 @@ class RadiiSlot:
         self.radii: "torch.Tensor | None" = None
 
 
+class FrameSlot(RadiiSlot):
+    """A RadiiSlot that also receives, in the frame's backward, dL_dmean2D [N,2]: the gradient w.r.t. each Gaussian's
+    pixel-space centre (no NDC factor; a new tensor per frame) — the statistic densify.DensityStats.update() accumulates.
+    The backward asks gsr_backward for one more array; the other gradients are the same bits as with a RadiiSlot."""
+
+    def __init__(self):
+        super().__init__()
+        self.dL_dmean2D: "torch.Tensor | None" = None
+
+
 class _Activate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, opacity_logit, log_scale, rotation, slot):
@@ -194,9 +204,14 @@ class _Rasterize(torch.autograd.Function):
             into["camera"] = new(35)
         if not into:
             return (None,) * 11
+        frame_slot = opts["radii_slot"] if isinstance(opts["radii_slot"], FrameSlot) else None
+        if frame_slot is not None:
+            into["dL_dmean2D"] = new(n, 2)
         res = rast.backward(g_color, semantics=opts["semantics"], sh_degree=opts["sh_degree"], scale_modifier=opts["scale_modifier"],
                             receipt=ctx.receipt, wide_sums=True, dL_ddepth=g_depth if opts["depth"] else None,
                             depth=opts["depth"] or None, camera=camera, into=into, sync=False)
+        if frame_slot is not None:
+            frame_slot.dL_dmean2D = res["dL_dmean2D"]
         g = lambda k, on=True: res[k] if (on and k in res) else None
         cam_g = lambda k, name, shape: res[k].reshape(shape) if need[name] else None
         return (None, None, g("dL_dmeans3D"), g("dL_dscales", need["scales"]), g("dL_drotations"),
@@ -222,7 +237,8 @@ def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs,
 
     The backward asks gsr_backward (double sums: the gradients do not depend on the order of the tiles' atomics) for exactly
     the per-Gaussian outputs whose input requires a gradient, written into new tensors; when view, proj or cam_pos requires
-    one, it runs with camera=True and returns the three camera gradients in the inputs' shapes. It raises RuntimeError
+    one, it runs with camera=True and returns the three camera gradients in the inputs' shapes. With a FrameSlot as radii_slot
+    it also asks for dL_dmean2D, into a new [N,2] tensor left in the slot. It raises RuntimeError
     before launching anything if `rast` drew again, or was rebound, after this call (see the module docstring)."""
     assert set(draw_options) <= set(_DRAW_OPTIONS), sorted(draw_options)
     assert depth in (False, True, "inverse"), depth
@@ -322,7 +338,8 @@ def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: 
     object) or a tuple (view, proj, cam_pos, tan_fovx, tan_fovy) whose first three are device tensors, which may require
     gradients. `loss.backward()` fills params.*.grad (and the camera tensors' .grad). Gaussians the frame culled get zero
     gradients without their rows being read. radii_slot: a RadiiSlot of the caller's, used instead of the call's own; after
-    the call its `.radii` is the frame's radii (i32[N], a new tensor per frame) — what optim.GaussianAdam.step() takes."""
+    the call its `.radii` is the frame's radii (i32[N], a new tensor per frame) — what optim.GaussianAdam.step() takes. A
+    FrameSlot also receives, in the backward, the frame's dL_dmean2D [N,2] — what densify.DensityStats.update() takes."""
     if semantics == "inria" and sh_degree >= 1:
         assert params.sh_layout == "coefficient_major", 'semantics="inria" reads shs as [N][16][3]: sh_layout="coefficient_major"'
     slot = radii_slot if radii_slot is not None else RadiiSlot()

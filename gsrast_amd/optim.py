@@ -44,7 +44,8 @@ def _refuse(t: torch.Tensor, name: str) -> None:
 class GaussianAdam(torch.optim.Optimizer):
     """Adam over float32 GPU parameters whose first dimension is the Gaussian: torch.optim.Adam's arguments and defaults
     (no weight decay, amsgrad or maximize), its param_groups (a learning rate per group, read at every step) and its state
-    keys "step", "exp_avg", "exp_avg_sq" — code that prunes or densifies by editing an Adam's state applies unchanged."""
+    keys "step", "exp_avg", "exp_avg_sq" — code that prunes or densifies by editing an Adam's state applies unchanged
+    (gsrast_amd.densify.densify_and_prune does it in one HIP launch)."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8):
         if not lr >= 0.0:

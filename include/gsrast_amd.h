@@ -736,6 +736,88 @@ size_t gsr_photo_loss_scratch_bytes(int channels, int width, int height);     /*
 int gsr_photo_loss_forward(const gsr_photo_loss_args* args);
 int gsr_photo_loss_backward(const gsr_photo_loss_args* args);
 
+/* ---- adaptive density control over the raw parameters (csrc/densify.hip) ----
+ * Three calls: the statistics of a frame, the decision which Gaussians are cloned, split and pruned, and the move of the
+ * five raw arrays and their Adam moments into arrays of the new row count. Each enqueues on stream and does not
+ * synchronise; the caller reads `counts` back between the second and the third (it allocates the new arrays).
+ *
+ * gsr_densify_accumulate: one launch, no atomics. For a row with radii[i] > 0, in float32 without contraction, in this order:
+ *   gx = dL_dmean2D[i].x * half_width     gy = dL_dmean2D[i].y * half_height      (upstream's NDC convention: 0.5 W, 0.5 H;
+ *                                                                                  gsr_backward's dL_dmean2D carries no NDC factor)
+ *   grad_accum[i] = grad_accum[i] + sqrtf(gx*gx + gy*gy)
+ *   denom[i]      = denom[i] + 1
+ *   max_radii[i]  = max(max_radii[i], radii[i])
+ * Of a row with radii[i] <= 0 the kernel reads the radii word only: its gradient may be NaN, its three statistics keep
+ * their bits. Refused with GSR_ERR_INVALID_ARG before any HIP call: n < 0, a NULL pointer, dL_dmean2D not 8-byte aligned or
+ * another array not 4-byte aligned. More rows than one launch covers: GSR_ERR_TOO_LARGE. n == 0 is GSR_OK. */
+int gsr_densify_accumulate(int64_t n, const float* dL_dmean2D, const int32_t* radii, float half_width, float half_height,
+                           float* grad_accum, int32_t* denom, int32_t* max_radii, void* stream);
+/* gsr_densify_plan: the decision, taken in the raw domain (no exponential enters it; the caller forms the thresholds in
+ * double and rounds each to float once: log_dense = log(percent_dense * extent), logit_min_opacity = logit(min_opacity),
+ * log_world = log(0.1 * extent), log_shrink = log(0.8 * 2)). Per source row i, in float32, which is the definition of the
+ * result:
+ *   g      = denom[i] > 0 ? grad_accum[i] / (float)denom[i] : 0     (/ correctly rounded; a NaN g counts as 0)
+ *   m      = the largest of log_scale[i][0..2]                      (m = s0; if (s1 > m) m = s1; if (s2 > m) m = s2)
+ *   hot    = g >= max_grad            big = m > log_dense
+ *   clone  = hot && !big              split = hot && big
+ *   doomed(M) = opacity_logit[i] < logit_min_opacity || (max_screen > 0 && (max_radii[i] > max_screen || M > log_world))
+ *   doomed = doomed(m)                child_doomed = doomed(m - log_shrink)      (the subtraction in float32)
+ * Row i yields one KEPT row if !split && !doomed, one CLONE row if clone && !doomed, two CHILD rows if split &&
+ * !child_doomed. A clone and a child are tested with their PARENT's max_radii: they inherit it for this test (early
+ * upstream versions zeroed max_radii2D when they densified, and their screen-size pruning never fired because of it).
+ * max_screen <= 0 switches the two size tests off. Output rows in upstream's concatenation order: the kept rows in source
+ * order, then the clones in source order, then child 0 of every surviving split parent in source order, then child 1 of
+ * each. src_of[r] (i32, capacity 3 n) = the source row of output row r, r < K + C + 2 S; counts (i32[4], device) =
+ * (K, C, S, K + C + 2 S) with K kept rows, C clones and S surviving split parents. temp: gsr_densify_plan_temp_bytes(n)
+ * bytes of device memory, 16-byte aligned (three flag arrays, scanned in place, and the scan's own scratch).
+ * Refused with GSR_ERR_INVALID_ARG before any HIP call: n < 0, a NULL pointer, temp not 16-byte aligned or another array
+ * not 4-byte aligned. 3 n > 2^31 - 1 (the scan's sums and the counts are 32-bit): GSR_ERR_TOO_LARGE, and
+ * gsr_densify_plan_temp_bytes is then 0. n == 0 writes counts = 0. */
+size_t gsr_densify_plan_temp_bytes(int64_t n);
+int gsr_densify_plan(int64_t n, const float* opacity_logit, const float* log_scale, const float* grad_accum,
+                     const int32_t* denom, const int32_t* max_radii, float max_grad, float log_dense,
+                     float logit_min_opacity, float log_world, float log_shrink, int32_t max_screen, void* temp,
+                     int32_t* src_of, int32_t* counts, void* stream);
+/* gsr_densify_apply: one launch over the K + C + 2 S output rows of all five arrays; output row r gathers from source row
+ * src_of[r], and a source row that no output row names is never read. Rows [0, K) are kept rows, [K, K + C) clones,
+ * [K + C, K + C + S) child 0 and [K + C + S, K + C + 2 S) child 1 of the split parent with rank j = r - (K + C) resp.
+ * r - (K + C + S).
+ *   kept   the parameter and both moments are copied bit for bit
+ *   clone  the parameter is copied bit for bit; both moments are +0
+ *   child  both moments are +0; opacity_logit, rotation and shs are copied bit for bit;
+ *          log_scale'[c] = log_scale[c] - log_shrink, and, in float32 without contraction, with the parent's values:
+ *            (s0, s1, s2) = exp(log_scale)  and  (r, x, y, z) = rotation / |rotation|  exactly as gsr_activate_params forms
+ *            them (the Gaussian the noise is scaled by is the one that is rendered)
+ *            d[c] = s[c] * noise[j][k][c]                                          k = 0, 1: the child
+ *            R00 = 1 - 2*(y*y + z*z)   R01 = 2*(x*y - r*z)       R02 = 2*(x*z + r*y)
+ *            R10 = 2*(x*y + r*z)       R11 = 1 - 2*(x*x + z*z)   R12 = 2*(y*z - r*x)
+ *            R20 = 2*(x*z - r*y)       R21 = 2*(y*z + r*x)       R22 = 1 - 2*(x*x + y*y)        (upstream's build_rotation)
+ *            xyz'[a] = xyz[a] + ((Ra0*d[0] + Ra1*d[1]) + Ra2*d[2])
+ * The four moment pointers of an array are all NULL (no optimiser state yet: none is read or written) or all set. Source
+ * and destination arrays must not overlap. Refused with GSR_ERR_INVALID_ARG before any HIP call: a wrong struct_size; n_src
+ * or a count below 0; counts[3] != K + C + 2 S; K + S or C + S above n_src; a NULL src_of, src or dst; a NULL noise with
+ * S > 0; moment pointers of an array partly set; a parameter or moment array not 16-byte aligned, src_of or noise not
+ * 4-byte aligned. More rows than one launch covers: GSR_ERR_TOO_LARGE. counts[3] == 0 is GSR_OK and touches nothing. */
+typedef struct gsr_densify_array {
+    const float* src;              /* f32[n_src * w], w = 3 / 1 / 3 / 4 / 48 for xyz / opacity_logit / log_scale / rotation / shs */
+    const float* src_exp_avg;
+    const float* src_exp_avg_sq;
+    float* dst;                    /* f32[counts[3] * w] */
+    float* dst_exp_avg;
+    float* dst_exp_avg_sq;
+} gsr_densify_array;
+typedef struct gsr_densify_apply_args {
+    uint32_t struct_size;          /* = sizeof(gsr_densify_apply_args) */
+    float log_shrink;
+    int64_t n_src;
+    int32_t counts[4];             /* (K, C, S, K + C + 2 S), as gsr_densify_plan wrote them */
+    const int32_t* src_of;         /* i32[counts[3]] */
+    const float* noise;            /* f32[S][2][3], standard normal, the caller's */
+    void* stream;
+    gsr_densify_array xyz, opacity_logit, log_scale, rotation, shs;
+} gsr_densify_apply_args;
+int gsr_densify_apply(const gsr_densify_apply_args* args);
+
 #ifdef __cplusplus
 }
 #endif
