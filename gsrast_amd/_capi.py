@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GSR_LIB_TAG selects a tuning build made with `python -m gsrast_amd.build --tag NAME` (experiments only).
 _TAG = os.environ.get("GSR_LIB_TAG", "")
@@ -268,8 +270,7 @@ def lib() -> C.CDLL:
                 "gsrast_amd has no CPU or PyTorch fallback.")
         # PyTorch bundles its own libamdhip64.so.7; it must be the one already mapped when our
         # library resolves that soname, otherwise two HIP runtimes end up in the process and
-        # torch's device pointers mean nothing to ours ("no HIP device").
-        import torch  # noqa: F401
+        # torch's device pointers mean nothing to ours ("no HIP device"): this module imports torch first.
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(L, name, None)
@@ -286,3 +287,25 @@ def lib() -> C.CDLL:
 def check(code: int, where: str) -> None:
     if code != GSR_OK:
         raise GsrError(code, where)
+
+
+def call(name: str, *args, device=None, where: "str | None" = None) -> None:
+    """The entry point `name` (one that returns a GSR_* code), called with `device` current if one is given: GsrError unless GSR_OK."""
+    fn = getattr(lib(), name)
+    if device is None:
+        code = fn(*args)
+    else:
+        with torch.cuda.device(device):
+            code = fn(*args)
+    check(code, where or name)
+
+
+def stream(device) -> int:
+    """torch's current stream on `device`, as the `stream` arguments of the C ABI take it."""
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def aligned16(t: torch.Tensor) -> torch.Tensor:
+    """(the kernels move rows in 16-byte vectors: a strided view, or one that starts in the middle of a vector, is copied)"""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()

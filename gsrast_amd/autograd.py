@@ -24,16 +24,10 @@ from .rasterizer import SplatRasterizer
 F32 = torch.float32
 
 
-def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _f32c(t: torch.Tensor, shape, name: str) -> torch.Tensor:
     if t.dtype != F32 or tuple(t.shape) != tuple(shape):
         raise ValueError(f"{name}: expected float32 {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
-    t = t.contiguous()
-    # (the kernels move these arrays in 16-byte vectors: a view that starts in the middle of a row is copied)
-    return t if t.data_ptr() % 16 == 0 else t.clone()
+    return _capi.aligned16(t)
 
 
 class RadiiSlot:
@@ -63,11 +57,8 @@ class _Activate(torch.autograd.Function):
         opacity_logit = _f32c(opacity_logit, (n,), "opacity_logit")
         means3D, scales, rotations = (torch.empty((n, 4), dtype=F32, device=dev) for _ in range(3))
         opacities = torch.empty((n,), dtype=F32, device=dev)
-        with torch.cuda.device(dev):
-            rc = _capi.lib().gsr_activate_params(n, xyz.data_ptr(), opacity_logit.data_ptr(), log_scale.data_ptr(),
-                                                 rotation.data_ptr(), means3D.data_ptr(), scales.data_ptr(),
-                                                 rotations.data_ptr(), opacities.data_ptr(), _stream(dev))
-        _capi.check(rc, "gsr_activate_params")
+        _capi.call("gsr_activate_params", n, xyz.data_ptr(), opacity_logit.data_ptr(), log_scale.data_ptr(), rotation.data_ptr(),
+                   means3D.data_ptr(), scales.data_ptr(), rotations.data_ptr(), opacities.data_ptr(), _capi.stream(dev), device=dev)
         ctx.save_for_backward(opacity_logit, log_scale, rotation)
         ctx.slot = slot
         # each output depends on one input: one whose input requires no gradient requires none either, and the rasterizer's
@@ -114,13 +105,12 @@ class _Activate(torch.autograd.Function):
         if radii is not None:
             assert radii.dtype == torch.int32 and tuple(radii.shape) == (n,) and radii.device == dev and radii.is_contiguous()
         p = lambda t: t.data_ptr() if t is not None else None
-        with torch.cuda.device(dev):
-            rc = _capi.lib().gsr_activate_params_backward(
-                n, p(opacity_logit) if want[1] else None, p(log_scale) if want[2] else None, p(rotation) if want[3] else None,
-                p(radii), vec4(g_means, "dL_dmeans3D") if want[0] else None, vec4(g_scales, "dL_dscales") if want[2] else None,
-                vec4(g_rotations, "dL_drotations") if want[3] else None, opacity_vec4(g_opacities) if want[1] else None,
-                p(d_xyz), p(d_op), p(d_scale), p(d_rot), _stream(dev))
-        _capi.check(rc, "gsr_activate_params_backward")
+        _capi.call(
+            "gsr_activate_params_backward",
+            n, p(opacity_logit) if want[1] else None, p(log_scale) if want[2] else None, p(rotation) if want[3] else None,
+            p(radii), vec4(g_means, "dL_dmeans3D") if want[0] else None, vec4(g_scales, "dL_dscales") if want[2] else None,
+            vec4(g_rotations, "dL_drotations") if want[3] else None, opacity_vec4(g_opacities) if want[1] else None,
+            p(d_xyz), p(d_op), p(d_scale), p(d_rot), _capi.stream(dev), device=dev)
         return d_xyz, d_op, d_scale, d_rot, None
 
 

@@ -128,8 +128,6 @@ __global__ __launch_bounds__(256) void activate_params_backward_kernel(const Act
     }
 }
 
-inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
-
 }  // namespace
 }  // namespace gsr
 
@@ -137,15 +135,14 @@ using namespace gsr;
 
 extern "C" {
 
-int gsr_activate_params(int n, const float* raw_means, const float* raw_opacity, const float* raw_scales,
-                        const float* raw_rotations, float* means3D, float* scales, float* rotations, float* opacities,
-                        void* stream) {
+static int activate_params_impl(int n, const float* raw_means, const float* raw_opacity, const float* raw_scales, const float* raw_rotations,
+                                float* means3D, float* scales, float* rotations, float* opacities, void* stream) {
     if (n <= 0) return GSR_OK;
     if (!raw_means || !raw_opacity || !raw_scales || !raw_rotations || !means3D || !scales || !rotations || !opacities)
         return GSR_ERR_INVALID_ARG;
     // (every array but the two of one float per Gaussian is moved in 16-byte vectors)
-    if (misaligned16(raw_means) || misaligned16(raw_scales) || misaligned16(raw_rotations) || misaligned16(means3D) ||
-        misaligned16(scales) || misaligned16(rotations))
+    if (misaligned(raw_means, 16) || misaligned(raw_scales, 16) || misaligned(raw_rotations, 16) || misaligned(means3D, 16) ||
+        misaligned(scales, 16) || misaligned(rotations, 16))
         return GSR_ERR_INVALID_ARG;
     const unsigned blocks = (unsigned)(((long long)n + 255) / 256);
     hipLaunchKernelGGL(activate_params_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n, raw_means, raw_opacity,
@@ -154,11 +151,14 @@ int gsr_activate_params(int n, const float* raw_means, const float* raw_opacity,
     GSR_LAUNCH_CHECK("activate_params_kernel");
     return GSR_OK;
 }
+int gsr_activate_params(int n, const float* raw_means, const float* raw_opacity, const float* raw_scales, const float* raw_rotations,
+                        float* means3D, float* scales, float* rotations, float* opacities, void* stream) {
+    return entry_point(activate_params_impl, n, raw_means, raw_opacity, raw_scales, raw_rotations, means3D, scales, rotations, opacities, stream);
+}
 
-int gsr_activate_params_backward(int n, const float* raw_opacity, const float* raw_scales, const float* raw_rotations,
-                                 const int32_t* radii, const float* dL_dmeans3D, const float* dL_dscales,
-                                 const float* dL_drotations, const float* dL_dconic_opacity, float* dL_draw_means,
-                                 float* dL_draw_opacity, float* dL_draw_scales, float* dL_draw_rotations, void* stream) {
+static int activate_params_backward_impl(int n, const float* raw_opacity, const float* raw_scales, const float* raw_rotations, const int32_t* radii,
+                                         const float* dL_dmeans3D, const float* dL_dscales, const float* dL_drotations, const float* dL_dconic_opacity,
+                                         float* dL_draw_means, float* dL_draw_opacity, float* dL_draw_scales, float* dL_draw_rotations, void* stream) {
     if (n <= 0) return GSR_OK;
     // an output that is asked for needs what it is computed from; one that is not, nothing
     if (dL_draw_means && !dL_dmeans3D) return GSR_ERR_INVALID_ARG;
@@ -166,10 +166,10 @@ int gsr_activate_params_backward(int n, const float* raw_opacity, const float* r
     if (dL_draw_scales && (!raw_scales || !dL_dscales)) return GSR_ERR_INVALID_ARG;
     if (dL_draw_rotations && (!raw_rotations || !dL_drotations)) return GSR_ERR_INVALID_ARG;
     if (!dL_draw_means && !dL_draw_opacity && !dL_draw_scales && !dL_draw_rotations) return GSR_OK;
-    if ((dL_draw_means && (misaligned16(dL_draw_means) || misaligned16(dL_dmeans3D))) ||
-        (dL_draw_opacity && misaligned16(dL_dconic_opacity)) ||
-        (dL_draw_scales && (misaligned16(dL_draw_scales) || misaligned16(raw_scales) || misaligned16(dL_dscales))) ||
-        (dL_draw_rotations && (misaligned16(dL_draw_rotations) || misaligned16(raw_rotations) || misaligned16(dL_drotations))))
+    if ((dL_draw_means && (misaligned(dL_draw_means, 16) || misaligned(dL_dmeans3D, 16))) ||
+        (dL_draw_opacity && misaligned(dL_dconic_opacity, 16)) ||
+        (dL_draw_scales && (misaligned(dL_draw_scales, 16) || misaligned(raw_scales, 16) || misaligned(dL_dscales, 16))) ||
+        (dL_draw_rotations && (misaligned(dL_draw_rotations, 16) || misaligned(raw_rotations, 16) || misaligned(dL_drotations, 16))))
         return GSR_ERR_INVALID_ARG;
     ActivateBackwardParams p;
     p.n = n;
@@ -189,6 +189,12 @@ int gsr_activate_params_backward(int n, const float* raw_opacity, const float* r
     hipLaunchKernelGGL(activate_params_backward_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
     GSR_LAUNCH_CHECK("activate_params_backward_kernel");
     return GSR_OK;
+}
+int gsr_activate_params_backward(int n, const float* raw_opacity, const float* raw_scales, const float* raw_rotations, const int32_t* radii,
+                                 const float* dL_dmeans3D, const float* dL_dscales, const float* dL_drotations, const float* dL_dconic_opacity,
+                                 float* dL_draw_means, float* dL_draw_opacity, float* dL_draw_scales, float* dL_draw_rotations, void* stream) {
+    return entry_point(activate_params_backward_impl, n, raw_opacity, raw_scales, raw_rotations, radii, dL_dmeans3D, dL_dscales, dL_drotations,
+                       dL_dconic_opacity, dL_draw_means, dL_draw_opacity, dL_draw_scales, dL_draw_rotations, stream);
 }
 
 }  // extern "C"

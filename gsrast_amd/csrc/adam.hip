@@ -140,21 +140,19 @@ __global__ __launch_bounds__(256) void adam_step_kernel(const AdamParams q) {
     else update_run<float>(a, first * rf, count, rf, lane, wanted);
 }
 
-inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
-
 }  // namespace
 }  // namespace gsr
 
 using namespace gsr;
 
-extern "C" int gsr_adam_step(const gsr_adam_args* args) {
-    if (!args || args->struct_size != sizeof(gsr_adam_args)) return record_error(GSR_ERR_INVALID_ARG);
-    if (args->num_rows < 0 || args->num_tensors < 1 || args->num_tensors > GSR_ADAM_MAX_TENSORS) return record_error(GSR_ERR_INVALID_ARG);
+static int adam_step_impl(const gsr_adam_args* args) {
+    if (!args || args->struct_size != sizeof(gsr_adam_args)) return GSR_ERR_INVALID_ARG;
+    if (args->num_rows < 0 || args->num_tensors < 1 || args->num_tensors > GSR_ADAM_MAX_TENSORS) return GSR_ERR_INVALID_ARG;
     for (int k = 0; k < args->num_tensors; ++k) {
         const gsr_adam_tensor& t = args->tensors[k];
-        if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq || t.row_floats <= 0) return record_error(GSR_ERR_INVALID_ARG);
-        if (misaligned16(t.param) || misaligned16(t.grad) || misaligned16(t.exp_avg) || misaligned16(t.exp_avg_sq))
-            return record_error(GSR_ERR_INVALID_ARG);
+        if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq || t.row_floats <= 0) return GSR_ERR_INVALID_ARG;
+        if (misaligned(t.param, 16) || misaligned(t.grad, 16) || misaligned(t.exp_avg, 16) || misaligned(t.exp_avg_sq, 16))
+            return GSR_ERR_INVALID_ARG;
     }
     if (args->num_rows == 0) return GSR_OK;
     AdamParams q;
@@ -177,8 +175,9 @@ extern "C" int gsr_adam_step(const gsr_adam_args* args) {
         a.unit_end = units;
     }
     const long long blocks = (units + 3) / 4;
-    if (blocks > 0x7FFFFFFFll) return record_error(GSR_ERR_TOO_LARGE);
+    if (exceeds_grid(blocks)) return GSR_ERR_TOO_LARGE;
     hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)args->stream, q);
     GSR_LAUNCH_CHECK("adam_step_kernel");
     return GSR_OK;
 }
+extern "C" int gsr_adam_step(const gsr_adam_args* args) { return entry_point(adam_step_impl, args); }

@@ -702,61 +702,54 @@ const char* gsr_error_string(int code) {
 }
 
 size_t gsr_scan_temp_bytes(size_t n) { return scan_temp_bytes(n); }
+static int inclusive_scan_impl(const uint32_t* in, uint32_t* out, size_t n, char* temp, void* stream) {
+    if (n && (!in || !out || !temp)) return GSR_ERR_INVALID_ARG;
+    return launch_inclusive_scan(in, out, n, temp, (hipStream_t)stream);
+}
 int gsr_inclusive_scan_u32(const uint32_t* in, uint32_t* out, size_t n, char* temp, void* stream) {
-    clear_hip_error();
-    if (n && (!in || !out || !temp)) return record_error(GSR_ERR_INVALID_ARG);
-    return record_error(launch_inclusive_scan(in, out, n, temp, (hipStream_t)stream));
+    return entry_point(inclusive_scan_impl, in, out, n, temp, stream);
 }
 size_t gsr_sort_temp_bytes(size_t n) { return sort_temp_bytes(n); }
+static int sort_pairs_impl(const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* values_in, uint32_t* values_out, size_t n,
+                           int begin_bit, int end_bit, char* temp, void* stream) {
+    if (n && (!keys_in || !keys_out || !values_in || !values_out || !temp)) return GSR_ERR_INVALID_ARG;
+    return launch_sort_pairs(keys_in, keys_out, values_in, values_out, n, begin_bit, end_bit, temp, (hipStream_t)stream);
+}
 int gsr_sort_pairs_u64_u32(const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* values_in,
                            uint32_t* values_out, size_t n, int begin_bit, int end_bit, char* temp, void* stream) {
-    clear_hip_error();
-    if (n && (!keys_in || !keys_out || !values_in || !values_out || !temp)) return record_error(GSR_ERR_INVALID_ARG);
-    return record_error(launch_sort_pairs(keys_in, keys_out, values_in, values_out, n, begin_bit, end_bit, temp, (hipStream_t)stream));
+    return entry_point(sort_pairs_impl, keys_in, keys_out, values_in, values_out, n, begin_bit, end_bit, temp, stream);
 }
 
-int gsr_colors_from_dc(int n, const float* shs, float* colors, void* stream) {
-    clear_hip_error();
-    if (n <= 0) return record_error(GSR_OK);
-    if (!shs || !colors) return record_error(GSR_ERR_INVALID_ARG);
-    return record_error(launch_colors_from_dc(n, shs, colors, (hipStream_t)stream));
-}
-
-int gsr_blend_expf(int n, const float* in, float* out, void* stream) {
-    clear_hip_error();
-    if (n > 0 && (!in || !out)) return record_error(GSR_ERR_INVALID_ARG);
-    return record_error(launch_exp_test(n, in, out, (hipStream_t)stream));
-}
-
+// (three calls whose launchers, in preprocess.hip and blend.hip, refuse what the call refuses)
+int gsr_colors_from_dc(int n, const float* shs, float* colors, void* stream) { return entry_point(launch_colors_from_dc, n, shs, colors, (hipStream_t)stream); }
+int gsr_blend_expf(int n, const float* in, float* out, void* stream) { return entry_point(launch_exp_test, n, in, out, (hipStream_t)stream); }
 int gsr_footprint_misses_tile(int n, const float* means2D, const float* conic_opacity, const int32_t* tile_xy, int width,
                               int height, uint8_t* misses, void* stream) {
-    clear_hip_error();
-    if (n > 0 && (!means2D || !conic_opacity || !tile_xy || !misses || width <= 0 || height <= 0)) return record_error(GSR_ERR_INVALID_ARG);
-    return record_error(launch_footprint_test(n, means2D, conic_opacity, tile_xy, width, height, misses, (hipStream_t)stream));
+    return entry_point(launch_footprint_test, n, means2D, conic_opacity, tile_xy, width, height, misses, (hipStream_t)stream);
 }
 
-int gsr_poll_async_error(const gsr_forward_receipt* r) {
-    if (!r || r->magic != GSR_RECEIPT_MAGIC || !r->async_words) return record_error(GSR_ERR_INVALID_ARG);
+static int poll_async_error_impl(const gsr_forward_receipt* r) {
+    if (!r || r->magic != GSR_RECEIPT_MAGIC || !r->async_words) return GSR_ERR_INVALID_ARG;
     const volatile uint32_t* w = r->async_words;
     // (the kernels write the owning call's serial, not 1: a late writer of an older call cannot raise the new owner's flag)
-    if (w[kAsyncErrN] == r->serial || w[kAsyncErrR] == r->serial) return record_error(GSR_ERR_INTERNAL);
-    if (w[kAsyncSerial] != r->serial) return record_error(GSR_ERR_STALE_RECEIPT);   // the slot has a new owner: nothing is known about that call any more
+    if (w[kAsyncErrN] == r->serial || w[kAsyncErrR] == r->serial) return GSR_ERR_INTERNAL;
+    if (w[kAsyncSerial] != r->serial) return GSR_ERR_STALE_RECEIPT;   // the slot has a new owner: nothing is known about that call any more
     return GSR_OK;
 }
+int gsr_poll_async_error(const gsr_forward_receipt* r) { return entry_point(poll_async_error_impl, r); }
 
-int gsr_forward(gsr_forward_args* a) {
-    clear_hip_error();
-    if (!a || a->struct_size != sizeof(gsr_forward_args)) return record_error(GSR_ERR_INVALID_ARG);
+static int forward_impl(gsr_forward_args* a) {
+    if (!a || a->struct_size != sizeof(gsr_forward_args)) return GSR_ERR_INVALID_ARG;
     a->num_rendered = 0;
     a->records_staged = 0;
     a->plan_used = 0;
     memset(a->stage_ms, 0, sizeof(a->stage_ms));
     memset(&a->receipt, 0, sizeof(a->receipt));
     Readback* rb = nullptr;
-    const int rc = check_arguments(a, &rb);
-    if (rc != GSR_OK) return record_error(rc);
+    GSR_TRY(check_arguments(a, &rb));
     ForwardCall call(a, *rb);                  // (its SideJoin: the caller's stream waits for the second one however the stages end)
-    return record_error(forward_stages(call));
+    return forward_stages(call);
 }
+int gsr_forward(gsr_forward_args* a) { return entry_point(forward_impl, a); }
 
 }  // extern "C"

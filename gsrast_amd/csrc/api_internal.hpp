@@ -34,9 +34,6 @@ struct gsr_tile_history {
 
 namespace gsr {
 
-// Forgets the failing HIP call gsr_last_hip_error() reports (every entry point starts with it).
-void clear_hip_error();
-
 // ---- chunk layout (chunks.hip) ----
 // Layout of GeometryState::scanningSpace (the reference keeps CUB's scan temp there,
 // AuxBuffer.cu:49-51; this library keeps all of its per-Gaussian scratch there).

@@ -1081,4 +1081,4 @@ static int backward_impl(gsr_backward_args* a) {
     return GSR_OK;
 }
 
-extern "C" int gsr_backward(gsr_backward_args* a) { return record_error(backward_impl(a)); }
+extern "C" int gsr_backward(gsr_backward_args* a) { return entry_point(backward_impl, a); }

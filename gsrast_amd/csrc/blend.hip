@@ -455,6 +455,7 @@ __global__ __launch_bounds__(64) void exp_test_kernel(int n, const float* __rest
 
 int launch_exp_test(int n, const float* in, float* out, hipStream_t stream) {
     if (n <= 0) return GSR_OK;
+    if (!in || !out) return GSR_ERR_INVALID_ARG;
     hipLaunchKernelGGL(exp_test_kernel, dim3((unsigned)std::min(65536, (n + 63) / 64)), dim3(64), 0, stream, n, in, out);
     GSR_LAUNCH_CHECK("exp_test_kernel");
     return GSR_OK;
@@ -463,6 +464,7 @@ int launch_exp_test(int n, const float* in, float* out, hipStream_t stream) {
 int launch_footprint_test(int n, const float* xy, const float* conic_opacity, const int32_t* tile_xy, int width, int height,
                           uint8_t* misses, hipStream_t stream) {
     if (n <= 0) return GSR_OK;
+    if (!xy || !conic_opacity || !tile_xy || !misses || width <= 0 || height <= 0) return GSR_ERR_INVALID_ARG;
     hipLaunchKernelGGL(footprint_test_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n,
                        reinterpret_cast<const float2*>(xy), reinterpret_cast<const float4*>(conic_opacity),
                        reinterpret_cast<const int2*>(tile_xy), width, height, misses);

@@ -370,4 +370,4 @@ extern "C" size_t gsr_camera_backward_scratch_bytes(int32_t num_gaussians) {
     return num_gaussians > 0 ? (size_t)camera_blocks(num_gaussians) * kCamRow * sizeof(double) : 0;
 }
 
-extern "C" int gsr_camera_backward(gsr_camera_backward_args* a) { return record_error(camera_backward_impl(a)); }
+extern "C" int gsr_camera_backward(gsr_camera_backward_args* a) { return entry_point(camera_backward_impl, a); }

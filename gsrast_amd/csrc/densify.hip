@@ -265,8 +265,6 @@ __global__ __launch_bounds__(256) void densify_apply_kernel(const ApplyParams q)
     }
 }
 
-inline bool misaligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
-
 constexpr long long kPlanMaxRows = 0x7FFFFFFFll / 3;                        // 3 n flags, their sums and the counts in 32 bits
 
 inline size_t plan_flag_bytes(long long n) { return ((size_t)n * 3 * sizeof(uint32_t) + 127) / 128 * 128; }
@@ -276,19 +274,23 @@ inline size_t plan_flag_bytes(long long n) { return ((size_t)n * 3 * sizeof(uint
 
 using namespace gsr;
 
-extern "C" int gsr_densify_accumulate(int64_t n, const float* dL_dmean2D, const int32_t* radii, float half_width, float half_height,
-                                      float* grad_accum, int32_t* denom, int32_t* max_radii, void* stream) {
-    if (n < 0 || !dL_dmean2D || !radii || !grad_accum || !denom || !max_radii) return record_error(GSR_ERR_INVALID_ARG);
+static int densify_accumulate_impl(int64_t n, const float* dL_dmean2D, const int32_t* radii, float half_width, float half_height,
+                                   float* grad_accum, int32_t* denom, int32_t* max_radii, void* stream) {
+    if (n < 0 || !dL_dmean2D || !radii || !grad_accum || !denom || !max_radii) return GSR_ERR_INVALID_ARG;
     if (misaligned(dL_dmean2D, 8) || misaligned(radii, 4) || misaligned(grad_accum, 4) || misaligned(denom, 4) || misaligned(max_radii, 4))
-        return record_error(GSR_ERR_INVALID_ARG);
+        return GSR_ERR_INVALID_ARG;
     if (n == 0) return GSR_OK;
     const long long per_block = 4ll * kAccRows * kWave;
     const long long blocks = (n + per_block - 1) / per_block;
-    if (blocks > 0x7FFFFFFFll) return record_error(GSR_ERR_TOO_LARGE);
+    if (exceeds_grid(blocks)) return GSR_ERR_TOO_LARGE;
     hipLaunchKernelGGL(densify_accumulate_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (long long)n,
                        reinterpret_cast<const float2*>(dL_dmean2D), radii, half_width, half_height, grad_accum, denom, max_radii);
     GSR_LAUNCH_CHECK("densify_accumulate_kernel");
     return GSR_OK;
+}
+extern "C" int gsr_densify_accumulate(int64_t n, const float* dL_dmean2D, const int32_t* radii, float half_width, float half_height,
+                                      float* grad_accum, int32_t* denom, int32_t* max_radii, void* stream) {
+    return entry_point(densify_accumulate_impl, n, dL_dmean2D, radii, half_width, half_height, grad_accum, denom, max_radii, stream);
 }
 
 extern "C" size_t gsr_densify_plan_temp_bytes(int64_t n) {
@@ -296,16 +298,15 @@ extern "C" size_t gsr_densify_plan_temp_bytes(int64_t n) {
     return plan_flag_bytes(n) + scan_temp_bytes((size_t)n * 3);
 }
 
-extern "C" int gsr_densify_plan(int64_t n, const float* opacity_logit, const float* log_scale, const float* grad_accum,
-                                const int32_t* denom, const int32_t* max_radii, float max_grad, float log_dense,
-                                float logit_min_opacity, float log_world, float log_shrink, int32_t max_screen, void* temp,
-                                int32_t* src_of, int32_t* counts, void* stream) {
+static int densify_plan_impl(int64_t n, const float* opacity_logit, const float* log_scale, const float* grad_accum, const int32_t* denom,
+                             const int32_t* max_radii, float max_grad, float log_dense, float logit_min_opacity, float log_world,
+                             float log_shrink, int32_t max_screen, void* temp, int32_t* src_of, int32_t* counts, void* stream) {
     if (n < 0 || !opacity_logit || !log_scale || !grad_accum || !denom || !max_radii || !temp || !src_of || !counts)
-        return record_error(GSR_ERR_INVALID_ARG);
+        return GSR_ERR_INVALID_ARG;
     if (misaligned(opacity_logit, 4) || misaligned(log_scale, 4) || misaligned(grad_accum, 4) || misaligned(denom, 4) ||
         misaligned(max_radii, 4) || misaligned(temp, 16) || misaligned(src_of, 4) || misaligned(counts, 4))
-        return record_error(GSR_ERR_INVALID_ARG);
-    if (n > kPlanMaxRows) return record_error(GSR_ERR_TOO_LARGE);
+        return GSR_ERR_INVALID_ARG;
+    if (n > kPlanMaxRows) return GSR_ERR_TOO_LARGE;
     const hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
         GSR_HIP_TRY(hipMemsetAsync(counts, 0, 4 * sizeof(int32_t), st));
@@ -322,22 +323,28 @@ extern "C" int gsr_densify_plan(int64_t n, const float* opacity_logit, const flo
     GSR_LAUNCH_CHECK("densify_scatter_kernel");
     return GSR_OK;
 }
+extern "C" int gsr_densify_plan(int64_t n, const float* opacity_logit, const float* log_scale, const float* grad_accum, const int32_t* denom,
+                                const int32_t* max_radii, float max_grad, float log_dense, float logit_min_opacity, float log_world,
+                                float log_shrink, int32_t max_screen, void* temp, int32_t* src_of, int32_t* counts, void* stream) {
+    return entry_point(densify_plan_impl, n, opacity_logit, log_scale, grad_accum, denom, max_radii, max_grad, log_dense, logit_min_opacity,
+                       log_world, log_shrink, max_screen, temp, src_of, counts, stream);
+}
 
-extern "C" int gsr_densify_apply(const gsr_densify_apply_args* args) {
-    if (!args || args->struct_size != sizeof(gsr_densify_apply_args)) return record_error(GSR_ERR_INVALID_ARG);
+static int densify_apply_impl(const gsr_densify_apply_args* args) {
+    if (!args || args->struct_size != sizeof(gsr_densify_apply_args)) return GSR_ERR_INVALID_ARG;
     const long long n = args->n_src, K = args->counts[0], C = args->counts[1], S = args->counts[2], total = args->counts[3];
-    if (n < 0 || K < 0 || C < 0 || S < 0 || total != K + C + 2 * S || K + S > n || C + S > n) return record_error(GSR_ERR_INVALID_ARG);
+    if (n < 0 || K < 0 || C < 0 || S < 0 || total != K + C + 2 * S || K + S > n || C + S > n) return GSR_ERR_INVALID_ARG;
     if (!args->src_of || misaligned(args->src_of, 4) || (S > 0 && !args->noise) || misaligned(args->noise, 4))
-        return record_error(GSR_ERR_INVALID_ARG);
+        return GSR_ERR_INVALID_ARG;
     const gsr_densify_array* in[kArrays] = {&args->xyz, &args->opacity_logit, &args->log_scale, &args->rotation, &args->shs};
     for (int k = 0; k < kArrays; ++k) {
         const gsr_densify_array& a = *in[k];
-        if (!a.src || !a.dst) return record_error(GSR_ERR_INVALID_ARG);
+        if (!a.src || !a.dst) return GSR_ERR_INVALID_ARG;
         const int set = (a.src_exp_avg != nullptr) + (a.src_exp_avg_sq != nullptr) + (a.dst_exp_avg != nullptr) + (a.dst_exp_avg_sq != nullptr);
-        if (set != 0 && set != 4) return record_error(GSR_ERR_INVALID_ARG);
+        if (set != 0 && set != 4) return GSR_ERR_INVALID_ARG;
         if (misaligned(a.src, 16) || misaligned(a.dst, 16) || misaligned(a.src_exp_avg, 16) || misaligned(a.src_exp_avg_sq, 16) ||
             misaligned(a.dst_exp_avg, 16) || misaligned(a.dst_exp_avg_sq, 16))
-            return record_error(GSR_ERR_INVALID_ARG);
+            return GSR_ERR_INVALID_ARG;
     }
     if (total == 0) return GSR_OK;
     ApplyParams q;
@@ -357,8 +364,9 @@ extern "C" int gsr_densify_apply(const gsr_densify_apply_args* args) {
         q.a[k] = ApplyArray{a.src, a.src_exp_avg, a.src_exp_avg_sq, a.dst, a.dst_exp_avg, a.dst_exp_avg_sq, units};
     }
     const long long blocks = (units + 3) / 4;
-    if (blocks > 0x7FFFFFFFll) return record_error(GSR_ERR_TOO_LARGE);
+    if (exceeds_grid(blocks)) return GSR_ERR_TOO_LARGE;
     hipLaunchKernelGGL(densify_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)args->stream, q);
     GSR_LAUNCH_CHECK("densify_apply_kernel");
     return GSR_OK;
 }
+extern "C" int gsr_densify_apply(const gsr_densify_apply_args* args) { return entry_point(densify_apply_impl, args); }

@@ -142,40 +142,42 @@ static int exchange_impl(gsr_exchange* x, float* frame, int width, int height, c
     return GSR_OK;
 }
 
+// The exchange's entry points: entry_point() (gsr_common.hpp) behind a fresh gsr_exchange_last_error() text.
+template <typename Impl, typename... Args>
+static int exchange_entry(Impl impl, Args... args) { g_exchange_error[0] = 0; return entry_point(impl, args...); }
+
 extern "C" {
 
 const char* gsr_exchange_last_error(void) { return g_exchange_error; }
 
-int gsr_exchange_unique_id(const char* rccl_path, char* id128) {
-    g_exchange_error[0] = 0;
-    if (!id128) return record_error(GSR_ERR_INVALID_ARG);
-    int rc = load_rccl(rccl_path);
-    if (rc != GSR_OK) return record_error(rc);
+static int exchange_unique_id_impl(const char* rccl_path, char* id128) {
+    if (!id128) return GSR_ERR_INVALID_ARG;
+    GSR_TRY(load_rccl(rccl_path));
     UniqueId id;
-    const int c = g_rccl.get_unique_id(&id);
-    if (c != 0) return record_error(rccl_failed(c, "ncclGetUniqueId"));
+    GSR_RCCL_TRY(g_rccl.get_unique_id(&id), "ncclGetUniqueId");
     memcpy(id128, id.internal, sizeof(id.internal));
-    return record_error(GSR_OK);
+    return GSR_OK;
 }
+int gsr_exchange_unique_id(const char* rccl_path, char* id128) { return exchange_entry(exchange_unique_id_impl, rccl_path, id128); }
 
-int gsr_exchange_create(const char* rccl_path, const char* id128, int rank, int world, gsr_exchange** out) {
-    g_exchange_error[0] = 0;
-    if (!id128 || !out || world < 1 || rank < 0 || rank >= world) return record_error(GSR_ERR_INVALID_ARG);
+static int exchange_create_impl(const char* rccl_path, const char* id128, int rank, int world, gsr_exchange** out) {
+    if (!id128 || !out || world < 1 || rank < 0 || rank >= world) return GSR_ERR_INVALID_ARG;
     *out = nullptr;
-    int rc = load_rccl(rccl_path);
-    if (rc != GSR_OK) return record_error(rc);
+    GSR_TRY(load_rccl(rccl_path));
     UniqueId id;
     memcpy(id.internal, id128, sizeof(id.internal));
     void* comm = nullptr;
-    const int c = g_rccl.comm_init_rank(&comm, world, id, rank);       // collective: every rank calls, on its own device
-    if (c != 0) return record_error(rccl_failed(c, "ncclCommInitRank"));
+    GSR_RCCL_TRY(g_rccl.comm_init_rank(&comm, world, id, rank), "ncclCommInitRank");       // collective: every rank calls, on its own device
     gsr_exchange* x = new gsr_exchange;
     x->comm = comm; x->rank = rank; x->world = world;
     *out = x;
-    return record_error(GSR_OK);
+    return GSR_OK;
+}
+int gsr_exchange_create(const char* rccl_path, const char* id128, int rank, int world, gsr_exchange** out) {
+    return exchange_entry(exchange_create_impl, rccl_path, id128, rank, world, out);
 }
 
-int gsr_exchange_destroy(gsr_exchange* x) {
+static int exchange_destroy_impl(gsr_exchange* x) {
     if (!x) return GSR_OK;
     int rc = GSR_OK;
     if (x->comm && g_rccl.comm_destroy) {
@@ -183,8 +185,9 @@ int gsr_exchange_destroy(gsr_exchange* x) {
         if (c != 0) rc = rccl_failed(c, "ncclCommDestroy");
     }
     delete x;
-    return record_error(rc);
+    return rc;
 }
+int gsr_exchange_destroy(gsr_exchange* x) { return exchange_entry(exchange_destroy_impl, x); }
 
 // The plan of gsr_exchange_bands without a communicator (host only): what rank `rank` would issue. Returns the number of
 // transfers (<= 6 (world - 1)), or -GSR_ERR_INVALID_ARG; fills up to max_ops entries of each array that is not NULL.
@@ -207,28 +210,26 @@ int gsr_exchange_plan(int rank, int world, int width, int height, const int32_t*
 // A rank's transfer to itself: `planes` pieces of `count` floats from src to dst through ncclSend / ncclRecv in one group,
 // the shape of a peer's band. What a one-GPU box can run of the transfer path (RCCL matches a send to the own rank with
 // the receive from it inside a group).
+static int exchange_loopback_impl(gsr_exchange* x, const float* src, float* dst, uint64_t count, int planes, void* stream) {
+    if (!x || !src || !dst || planes < 1) return GSR_ERR_INVALID_ARG;
+    GSR_RCCL_TRY(g_rccl.group_start(), "ncclGroupStart");
+    int rc = GSR_OK;
+    for (int c = 0; c < planes && rc == GSR_OK; ++c) {
+        int e = g_rccl.send(src + (size_t)c * count, (size_t)count, kNcclFloat32, x->rank, x->comm, (hipStream_t)stream);
+        if (e == 0) e = g_rccl.recv(dst + (size_t)c * count, (size_t)count, kNcclFloat32, x->rank, x->comm, (hipStream_t)stream);
+        if (e != 0) rc = rccl_failed(e, "ncclSend / ncclRecv to the own rank");
+    }
+    const int ce = g_rccl.group_end();
+    if (rc != GSR_OK) return rc;
+    if (ce != 0) return rccl_failed(ce, "ncclGroupEnd");
+    return GSR_OK;
+}
 int gsr_exchange_loopback(gsr_exchange* x, const float* src, float* dst, uint64_t count, int planes, void* stream) {
-    g_exchange_error[0] = 0;
-    if (!x || !src || !dst || planes < 1) return record_error(GSR_ERR_INVALID_ARG);
-    auto run = [&]() -> int {
-        GSR_RCCL_TRY(g_rccl.group_start(), "ncclGroupStart");
-        int rc = GSR_OK;
-        for (int c = 0; c < planes && rc == GSR_OK; ++c) {
-            int e = g_rccl.send(src + (size_t)c * count, (size_t)count, kNcclFloat32, x->rank, x->comm, (hipStream_t)stream);
-            if (e == 0) e = g_rccl.recv(dst + (size_t)c * count, (size_t)count, kNcclFloat32, x->rank, x->comm, (hipStream_t)stream);
-            if (e != 0) rc = rccl_failed(e, "ncclSend / ncclRecv to the own rank");
-        }
-        const int ce = g_rccl.group_end();
-        if (rc != GSR_OK) return rc;
-        if (ce != 0) return rccl_failed(ce, "ncclGroupEnd");
-        return GSR_OK;
-    };
-    return record_error(run());
+    return exchange_entry(exchange_loopback_impl, x, src, dst, count, planes, stream);
 }
 
 int gsr_exchange_bands(gsr_exchange* x, float* frame, int width, int height, const int32_t* bounds, int root, void* stream) {
-    g_exchange_error[0] = 0;
-    return record_error(exchange_impl(x, frame, width, height, bounds, root, (hipStream_t)stream));
+    return exchange_entry(exchange_impl, x, frame, width, height, bounds, root, (hipStream_t)stream);
 }
 
 }  // extern "C"

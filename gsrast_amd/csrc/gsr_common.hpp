@@ -13,10 +13,19 @@ namespace gsr {
 constexpr int kTile = 16;          // BLOCK_W / BLOCK_H, reference GSCuda.cu:20-21
 constexpr int kWave = 64;          // gfx950 wavefront
 
-// Records the failing HIP call for gsr_last_hip_error().
+// Records the failing HIP call for gsr_last_hip_error(), and forgets it: entry_point() starts every entry point with that
+// (the one other caller, history_of_call, swallows an expected allocation failure).
 void set_hip_error(hipError_t e, const char* what);
+void clear_hip_error();
 // Sets the calling thread's sticky error (gsr_last_error) and returns `code`.
 int record_error(int code);
+// The error contract of include/gsrast_amd.h, for every extern "C" function that returns a GSR_* code: the previous HIP text
+// is forgotten, `impl` runs and returns plain codes (GSR_HIP_TRY, GSR_TRY and GSR_LAUNCH_CHECK included), its code is recorded.
+template <typename Impl, typename... Args>
+inline int entry_point(Impl impl, Args... args) { clear_hip_error(); return record_error(impl(args...)); }
+// Refused before a launch: a pointer off a `to`-byte boundary (a power of two; null passes), more workgroups than a grid holds.
+inline bool misaligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
+inline bool exceeds_grid(long long blocks) { return blocks > 0x7FFFFFFFll; }
 
 #define GSR_HIP_TRY(expr)                                   \
     do {                                                    \

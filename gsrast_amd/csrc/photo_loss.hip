@@ -254,8 +254,6 @@ int photo_shape(int channels, int width, int height, PhotoShape* s) {
     return GSR_OK;
 }
 
-inline bool misaligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
-
 // What both calls refuse, and the parameters both kernels take.
 int photo_params(const gsr_photo_loss_args* a, PhotoShape* s, PhotoParams* q) {
     if (!a || a->struct_size != sizeof(gsr_photo_loss_args)) return GSR_ERR_INVALID_ARG;
@@ -291,12 +289,11 @@ extern "C" size_t gsr_photo_loss_scratch_bytes(int channels, int width, int heig
     return (size_t)(16 * s.workgroups + 3 * 4 * s.floats);        // partial pairs, then the three maps (16-byte aligned: the pairs are)
 }
 
-extern "C" int gsr_photo_loss_forward(const gsr_photo_loss_args* args) {
+static int photo_loss_forward_impl(const gsr_photo_loss_args* args) {
     PhotoShape s;
     PhotoParams q;
-    const int rc = photo_params(args, &s, &q);
-    if (rc != GSR_OK) return record_error(rc);
-    if (!args->out || misaligned(args->out, 4)) return record_error(GSR_ERR_INVALID_ARG);
+    GSR_TRY(photo_params(args, &s, &q));
+    if (!args->out || misaligned(args->out, 4)) return GSR_ERR_INVALID_ARG;
     const hipStream_t stream = (hipStream_t)args->stream;
     const dim3 grid((unsigned)s.tiles_x, (unsigned)s.tiles_y, (unsigned)args->channels);
     if ((args->width & 3) == 0) hipLaunchKernelGGL(photo_loss_forward_kernel<true>, grid, dim3(kThreads), 0, stream, q);
@@ -307,14 +304,14 @@ extern "C" int gsr_photo_loss_forward(const gsr_photo_loss_args* args) {
     GSR_LAUNCH_CHECK("photo_loss_finalize_kernel");
     return GSR_OK;
 }
+extern "C" int gsr_photo_loss_forward(const gsr_photo_loss_args* args) { return entry_point(photo_loss_forward_impl, args); }
 
-extern "C" int gsr_photo_loss_backward(const gsr_photo_loss_args* args) {
+static int photo_loss_backward_impl(const gsr_photo_loss_args* args) {
     PhotoShape s;
     PhotoParams q;
-    const int rc = photo_params(args, &s, &q);
-    if (rc != GSR_OK) return record_error(rc);
+    GSR_TRY(photo_params(args, &s, &q));
     if (!args->dL_dloss || misaligned(args->dL_dloss, 4) || !args->dL_dimage || misaligned(args->dL_dimage, 16))
-        return record_error(GSR_ERR_INVALID_ARG);
+        return GSR_ERR_INVALID_ARG;
     const hipStream_t stream = (hipStream_t)args->stream;
     const dim3 grid((unsigned)s.tiles_x, (unsigned)s.tiles_y, (unsigned)args->channels);
     if ((args->width & 3) == 0) hipLaunchKernelGGL(photo_loss_backward_kernel<true>, grid, dim3(kThreads), 0, stream, q);
@@ -322,3 +319,4 @@ extern "C" int gsr_photo_loss_backward(const gsr_photo_loss_args* args) {
     GSR_LAUNCH_CHECK("photo_loss_backward_kernel");
     return GSR_OK;
 }
+extern "C" int gsr_photo_loss_backward(const gsr_photo_loss_args* args) { return entry_point(photo_loss_backward_impl, args); }

@@ -74,7 +74,7 @@ using namespace gsr;
 
 extern "C" {
 
-int gsr_ply_parse_header(const char* path, int* num_splats, long long* data_offset) {
+static int ply_parse_header_impl(const char* path, int* num_splats, long long* data_offset) {
     if (!path || !num_splats || !data_offset) return GSR_ERR_INVALID_ARG;
     FILE* f = fopen(path, "rb");
     if (!f) return GSR_ERR_INVALID_ARG;
@@ -97,14 +97,10 @@ int gsr_ply_parse_header(const char* path, int* num_splats, long long* data_offs
     fclose(f);
     return ok ? GSR_OK : GSR_ERR_INVALID_ARG;
 }
+int gsr_ply_parse_header(const char* path, int* num_splats, long long* data_offset) { return entry_point(ply_parse_header_impl, path, num_splats, data_offset); }
 
-int gsr_ply_activate(const float* raw_device, int n, float* means3D, float* scales, float* rotations, float* opacities,
-                     float* shs, void* stream) {
-    return gsr_ply_activate_layout(raw_device, n, means3D, scales, rotations, opacities, shs, GSR_SH_LAYOUT_FILE, stream);
-}
-
-int gsr_ply_activate_layout(const float* raw_device, int n, float* means3D, float* scales, float* rotations, float* opacities,
-                            float* shs, int sh_layout, void* stream) {
+static int ply_activate_impl(const float* raw_device, int n, float* means3D, float* scales, float* rotations, float* opacities,
+                             float* shs, int sh_layout, void* stream) {
     if (n <= 0) return GSR_OK;
     if (!raw_device || !means3D || !scales || !rotations || !opacities || !shs) return GSR_ERR_INVALID_ARG;
     if (sh_layout != GSR_SH_LAYOUT_FILE && sh_layout != GSR_SH_LAYOUT_COEFFICIENT_MAJOR) return GSR_ERR_INVALID_ARG;
@@ -114,6 +110,14 @@ int gsr_ply_activate_layout(const float* raw_device, int n, float* means3D, floa
                        reinterpret_cast<float4*>(rotations), opacities, shs, sh_layout);
     GSR_LAUNCH_CHECK("ply_activate_kernel");
     return GSR_OK;
+}
+int gsr_ply_activate(const float* raw_device, int n, float* means3D, float* scales, float* rotations, float* opacities,
+                     float* shs, void* stream) {
+    return entry_point(ply_activate_impl, raw_device, n, means3D, scales, rotations, opacities, shs, (int)GSR_SH_LAYOUT_FILE, stream);
+}
+int gsr_ply_activate_layout(const float* raw_device, int n, float* means3D, float* scales, float* rotations, float* opacities,
+                            float* shs, int sh_layout, void* stream) {
+    return entry_point(ply_activate_impl, raw_device, n, means3D, scales, rotations, opacities, shs, sh_layout, stream);
 }
 
 }  // extern "C"

@@ -122,6 +122,6 @@ static int forward_points_impl(gsr_forward_args* a) {
     return GSR_OK;
 }
 
-int gsr_forward_points(gsr_forward_args* a) { return record_error(forward_points_impl(a)); }
+int gsr_forward_points(gsr_forward_args* a) { return entry_point(forward_points_impl, a); }
 
 }  // extern "C"

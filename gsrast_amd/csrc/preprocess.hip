@@ -274,6 +274,8 @@ int launch_colors_visible(int n, const uint32_t* tiles_touched, const float* shs
 }
 
 int launch_colors_from_dc(int n, const float* shs, float* colors, hipStream_t stream) {
+    if (n <= 0) return GSR_OK;
+    if (!shs || !colors) return GSR_ERR_INVALID_ARG;
     const size_t floats = 3 * (size_t)n;
     hipLaunchKernelGGL(colors_from_dc_kernel, dim3((unsigned)((floats + 255) / 256)), dim3(256), 0, stream, n, shs, colors);
     GSR_LAUNCH_CHECK("colors_from_dc_kernel");

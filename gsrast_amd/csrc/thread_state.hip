@@ -239,63 +239,63 @@ using namespace gsr;
 
 extern "C" {
 
-int gsr_tile_history_create(gsr_tile_history** out) {
-    clear_hip_error();
-    if (!out) return record_error(GSR_ERR_INVALID_ARG);
+static int tile_history_create_impl(gsr_tile_history** out) {
+    if (!out) return GSR_ERR_INVALID_ARG;
     *out = nullptr;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return record_error(GSR_ERR_NO_DEVICE);
-    return record_error(tile_history_new(out));
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return GSR_ERR_NO_DEVICE;
+    return tile_history_new(out);
 }
+int gsr_tile_history_create(gsr_tile_history** out) { return entry_point(tile_history_create_impl, out); }
 
-int gsr_tile_history_destroy(gsr_tile_history* h) {
-    clear_hip_error();
-    if (!h) return record_error(GSR_OK);
-    if (h->magic != kHistoryMagic) return record_error(GSR_ERR_INVALID_ARG);
+static int tile_history_destroy_impl(gsr_tile_history* h) {
+    if (!h) return GSR_OK;
+    if (h->magic != kHistoryMagic) return GSR_ERR_INVALID_ARG;
     destroy_history(h);
-    return record_error(GSR_OK);
+    return GSR_OK;
 }
+int gsr_tile_history_destroy(gsr_tile_history* h) { return entry_point(tile_history_destroy_impl, h); }
 
 void gsr_reread_environment(void) { env_knobs_storage() = read_env_knobs(); }
 
-int gsr_thread_release(void) {
-    clear_hip_error();
-    g_thread.release();
-    return record_error(GSR_OK);
-}
+static int thread_release_impl() { g_thread.release(); return GSR_OK; }
+int gsr_thread_release(void) { return entry_point(thread_release_impl); }
 
 void gsr_device_shape(int cus, uint32_t out[4]) {
     const DeviceShape s = device_shape_of(cus);
     out[0] = (uint32_t)s.cus; out[1] = s.blend_slots; out[2] = s.blend_slots_beside; out[3] = (uint32_t)(s.light_frame_ticks / 25000ull);
 }
 
-int gsr_tile_history_stats(const gsr_tile_history* h, uint32_t out[6]) {
-    if (!h || h->magic != kHistoryMagic || !out) return record_error(GSR_ERR_INVALID_ARG);
+static int tile_history_stats_impl(const gsr_tile_history* h, uint32_t* out) {
+    if (!h || h->magic != kHistoryMagic || !out) return GSR_ERR_INVALID_ARG;
     out[0] = h->stats[0] != 0u ? h->stats[2] : h->view.mean;          // (words the last sort has left and no call has read yet come first)
     out[1] = h->stats[1];
     out[2] = h->stats[3];
     out[3] = (h->stats[0] != 0u ? h->stats[4] != 0u : h->view.decorrelated) ? 1u : 0u;
     out[4] = h->view.calls;
     out[5] = h->view.overlapped ? 1u : 0u;
-    return record_error(GSR_OK);
+    return GSR_OK;
 }
+int gsr_tile_history_stats(const gsr_tile_history* h, uint32_t out[6]) { return entry_point(tile_history_stats_impl, h, out); }
 
-int gsr_tile_history_forget_stream(gsr_tile_history* h) {
-    clear_hip_error();
-    if (!h || h->magic != kHistoryMagic) return record_error(GSR_ERR_INVALID_ARG);
+static int tile_history_forget_stream_impl(gsr_tile_history* h) {
+    if (!h || h->magic != kHistoryMagic) return GSR_ERR_INVALID_ARG;
     h->used = false;
     h->last_stream = nullptr;
-    return record_error(GSR_OK);
+    return GSR_OK;
 }
+int gsr_tile_history_forget_stream(gsr_tile_history* h) { return entry_point(tile_history_forget_stream_impl, h); }
 
-int gsr_tile_history_times(const gsr_tile_history* h, uint32_t* times, int count, uint32_t* deep_tiles) {
-    clear_hip_error();
-    if (!h || h->magic != kHistoryMagic || !times || count < 0 || count > kTileOrderMax) return record_error(GSR_ERR_INVALID_ARG);
+static int tile_history_times_impl(const gsr_tile_history* h, uint32_t* times, int count, uint32_t* deep_tiles) {
+    if (!h || h->magic != kHistoryMagic || !times || count < 0 || count > kTileOrderMax) return GSR_ERR_INVALID_ARG;
     // (a tool's call: it synchronises the device — the history's calls may be on any stream)
     GSR_HIP_TRY(hipDeviceSynchronize());
     GSR_HIP_TRY(hipMemcpy(times, h->ticks[h->cur ^ 1], sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToHost));
     if (deep_tiles) GSR_HIP_TRY(hipMemcpy(deep_tiles, h->deep, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return record_error(GSR_OK);
+    return GSR_OK;
+}
+int gsr_tile_history_times(const gsr_tile_history* h, uint32_t* times, int count, uint32_t* deep_tiles) {
+    return entry_point(tile_history_times_impl, h, times, count, deep_tiles);
 }
 
 }  // extern "C"

@@ -67,11 +67,8 @@ class DensityStats:
                 or radii.device != self.device or grad.device != self.device or not radii.is_contiguous() or not grad.is_contiguous()):
             raise ValueError(f"DensityStats.update: the statistics have {n} rows on {self.device}; the slot's radii are "
                              f"{radii.dtype} {tuple(radii.shape)} on {radii.device}, its dL_dmean2D {grad.dtype} {tuple(grad.shape)}")
-        with torch.cuda.device(self.device):
-            rc = _capi.lib().gsr_densify_accumulate(n, grad.data_ptr(), radii.data_ptr(), 0.5 * width, 0.5 * height,
-                                                    self.grad_accum.data_ptr(), self.denom.data_ptr(), self.max_radii.data_ptr(),
-                                                    torch.cuda.current_stream(self.device).cuda_stream)
-        _capi.check(rc, "gsr_densify_accumulate")
+        _capi.call("gsr_densify_accumulate", n, grad.data_ptr(), radii.data_ptr(), 0.5 * width, 0.5 * height, self.grad_accum.data_ptr(),
+                   self.denom.data_ptr(), self.max_radii.data_ptr(), _capi.stream(self.device), device=self.device)
 
 
 def _refuse(t: torch.Tensor, name: str, shape, dev) -> None:
@@ -133,35 +130,32 @@ def densify_and_prune(params: GaussianParams, opt, stats: DensityStats, *, max_g
     scalars = plan_scalars(float(max_grad), float(min_opacity), float(extent), float(percent_dense))
     max_screen = int(max_screen_size) if max_screen_size is not None else 0
     # ---- nothing is refused from here on ----
-    L = _capi.lib()
     new_i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
     if n == 0:
         return new_i32(0), (0, 0, 0, 0)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        temp = torch.empty(int(L.gsr_densify_plan_temp_bytes(n)), dtype=torch.uint8, device=dev)
-        src_of, counts = new_i32(3 * n), new_i32(4)
-        rc = L.gsr_densify_plan(n, old["opacity_logit"].data_ptr(), old["log_scale"].data_ptr(), stats.grad_accum.data_ptr(),
-                                stats.denom.data_ptr(), stats.max_radii.data_ptr(), *scalars, max_screen, temp.data_ptr(),
-                                src_of.data_ptr(), counts.data_ptr(), stream)
-        _capi.check(rc, "gsr_densify_plan")
-        kept, clones, splits, total = (int(c) for c in counts.tolist())                    # (the one synchronisation)
-        noise_dev = generator.device if generator is not None else dev
-        noise = torch.randn((splits, 2, 3), generator=generator, dtype=torch.float32, device=noise_dev).to(dev).contiguous()
-        fresh = {k: torch.empty((total,) + tuple(old[k].shape[1:]), dtype=torch.float32, device=dev) for k in RAW}
-        fresh_moments = {k: tuple(torch.empty_like(fresh[k]) for _ in MOMENTS) for k in held}
-        if total > 0:
-            a = _capi.DensifyApplyArgs()
-            a.struct_size, a.log_shrink, a.n_src = C.sizeof(_capi.DensifyApplyArgs), scalars[4], n
-            a.counts[:] = [kept, clones, splits, total]
-            a.src_of, a.noise, a.stream = src_of.data_ptr(), noise.data_ptr() if splits else None, stream
-            for k in RAW:
-                arr = getattr(a, k)
-                arr.src, arr.dst = old[k].data_ptr(), fresh[k].data_ptr()
-                if k in held:
-                    arr.src_exp_avg, arr.src_exp_avg_sq = (t.data_ptr() for t in held[k])
-                    arr.dst_exp_avg, arr.dst_exp_avg_sq = (t.data_ptr() for t in fresh_moments[k])
-            _capi.check(L.gsr_densify_apply(C.byref(a)), "gsr_densify_apply")
+    stream = _capi.stream(dev)
+    temp = torch.empty(int(_capi.lib().gsr_densify_plan_temp_bytes(n)), dtype=torch.uint8, device=dev)
+    src_of, counts = new_i32(3 * n), new_i32(4)
+    _capi.call("gsr_densify_plan", n, old["opacity_logit"].data_ptr(), old["log_scale"].data_ptr(), stats.grad_accum.data_ptr(),
+               stats.denom.data_ptr(), stats.max_radii.data_ptr(), *scalars, max_screen, temp.data_ptr(), src_of.data_ptr(),
+               counts.data_ptr(), stream, device=dev)
+    kept, clones, splits, total = (int(c) for c in counts.tolist())                    # (the one synchronisation)
+    noise_dev = generator.device if generator is not None else dev
+    noise = torch.randn((splits, 2, 3), generator=generator, dtype=torch.float32, device=noise_dev).to(dev).contiguous()
+    fresh = {k: torch.empty((total,) + tuple(old[k].shape[1:]), dtype=torch.float32, device=dev) for k in RAW}
+    fresh_moments = {k: tuple(torch.empty_like(fresh[k]) for _ in MOMENTS) for k in held}
+    if total > 0:
+        a = _capi.DensifyApplyArgs()
+        a.struct_size, a.log_shrink, a.n_src = C.sizeof(_capi.DensifyApplyArgs), scalars[4], n
+        a.counts[:] = [kept, clones, splits, total]
+        a.src_of, a.noise, a.stream = src_of.data_ptr(), noise.data_ptr() if splits else None, stream
+        for k in RAW:
+            arr = getattr(a, k)
+            arr.src, arr.dst = old[k].data_ptr(), fresh[k].data_ptr()
+            if k in held:
+                arr.src_exp_avg, arr.src_exp_avg_sq = (t.data_ptr() for t in held[k])
+                arr.dst_exp_avg, arr.dst_exp_avg_sq = (t.data_ptr() for t in fresh_moments[k])
+        _capi.call("gsr_densify_apply", C.byref(a), device=dev)
     for k in RAW:
         p = torch.nn.Parameter(fresh[k], requires_grad=old[k].requires_grad)
         setattr(params, k, p)

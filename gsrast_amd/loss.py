@@ -22,20 +22,13 @@ from . import _capi
 F32 = torch.float32
 
 
-def _aligned(t: torch.Tensor) -> torch.Tensor:
-    """(autograd._f32c's rule: the kernels move rows in 16-byte vectors; a strided view or one that starts in the middle of a
-    vector is copied)"""
-    t = t.contiguous()
-    return t if t.data_ptr() % 16 == 0 else t.clone()
-
-
 def _args(image, target, lam, scratch):
     a = _capi.PhotoLossArgs()
     a.struct_size = C.sizeof(_capi.PhotoLossArgs)
     a.channels, a.height, a.width = (int(s) for s in image.shape)
     a.lambda_dssim = lam
     a.image, a.target, a.scratch = image.data_ptr(), target.data_ptr(), scratch.data_ptr()
-    a.stream = torch.cuda.current_stream(image.device).cuda_stream
+    a.stream = _capi.stream(image.device)
     return a
 
 
@@ -43,16 +36,14 @@ class _PhotoLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, image, target, lam):
         dev = image.device
-        image, target = _aligned(image.detach()), _aligned(target.detach())
+        image, target = _capi.aligned16(image.detach()), _capi.aligned16(target.detach())
         want = bool(ctx.needs_input_grad[0])
-        L = _capi.lib()
         c, h, w = (int(s) for s in image.shape)
-        scratch = torch.empty(L.gsr_photo_loss_scratch_bytes(c, w, h), dtype=torch.uint8, device=dev)
+        scratch = torch.empty(_capi.lib().gsr_photo_loss_scratch_bytes(c, w, h), dtype=torch.uint8, device=dev)
         out = torch.empty(3, dtype=F32, device=dev)
         a = _args(image, target, lam, scratch)
         a.out, a.want_backward = out.data_ptr(), int(want)
-        with torch.cuda.device(dev):
-            _capi.check(L.gsr_photo_loss_forward(C.byref(a)), "gsr_photo_loss_forward")
+        _capi.call("gsr_photo_loss_forward", C.byref(a), device=dev)
         if want:
             ctx.save_for_backward(image, target)                # (a write to either before backward() is reported)
             ctx.scratch, ctx.out, ctx.lam = scratch, out, lam
@@ -71,8 +62,7 @@ class _PhotoLoss(torch.autograd.Function):
         grad = torch.empty_like(image)
         a = _args(image, target, ctx.lam, ctx.scratch)
         a.dL_dloss, a.dL_dimage = up.data_ptr(), grad.data_ptr()
-        with torch.cuda.device(dev):
-            _capi.check(_capi.lib().gsr_photo_loss_backward(C.byref(a)), "gsr_photo_loss_backward")
+        _capi.call("gsr_photo_loss_backward", C.byref(a), device=dev)
         return grad, None, None
 
 

@@ -116,21 +116,18 @@ class GaussianAdam(torch.optim.Optimizer):
             beta1, beta2 = group["betas"]
             scalars = adam_scalars(float(group["lr"]), float(beta1), float(beta2), float(group["eps"]), t)
             calls.setdefault((p.device, rows), []).append((p, p.grad, state["exp_avg"], state["exp_avg_sq"], p.numel() // rows, scalars))
-        L = _capi.lib()
         for (dev, rows), tensors in calls.items():
-            with torch.cuda.device(dev):
-                stream = torch.cuda.current_stream(dev).cuda_stream
-                for at in range(0, len(tensors), _capi.GSR_ADAM_MAX_TENSORS):
-                    part = tensors[at:at + _capi.GSR_ADAM_MAX_TENSORS]
-                    a = _capi.AdamArgs()
-                    a.struct_size, a.num_tensors, a.num_rows = C.sizeof(_capi.AdamArgs), len(part), rows
-                    a.visible = visibility.data_ptr() if visibility is not None else None
-                    a.stream = stream
-                    for slot, (p, g, m, v, row_floats, scalars) in zip(a.tensors, part):
-                        slot.param, slot.grad, slot.exp_avg, slot.exp_avg_sq = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
-                        slot.row_floats = row_floats
-                        slot.step_size, slot.rs, slot.b1c, slot.b2, slot.b2c, slot.eps = scalars
-                    _capi.check(L.gsr_adam_step(C.byref(a)), "gsr_adam_step")
+            for at in range(0, len(tensors), _capi.GSR_ADAM_MAX_TENSORS):
+                part = tensors[at:at + _capi.GSR_ADAM_MAX_TENSORS]
+                a = _capi.AdamArgs()
+                a.struct_size, a.num_tensors, a.num_rows = C.sizeof(_capi.AdamArgs), len(part), rows
+                a.visible = visibility.data_ptr() if visibility is not None else None
+                a.stream = _capi.stream(dev)
+                for slot, (p, g, m, v, row_floats, scalars) in zip(a.tensors, part):
+                    slot.param, slot.grad, slot.exp_avg, slot.exp_avg_sq = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
+                    slot.row_floats = row_floats
+                    slot.step_size, slot.rs, slot.b1c, slot.b2, slot.b2c, slot.eps = scalars
+                _capi.call("gsr_adam_step", C.byref(a), device=dev)
             for p, _, m, v, _, _ in tensors:
                 # the kernel wrote through raw pointers: autograd's saved-tensor check and whatever keys on ._version
                 # (SplatRasterizer.precomputed_colors) must see the write

@@ -48,11 +48,8 @@ def load_ply(path: str, device="cuda:0", sh_layout: str = "file") -> dict:
         "opacities": torch.empty((n,), dtype=torch.float32, device=dev),
         "shs": torch.empty((n, 48), dtype=torch.float32, device=dev),
     }
-    with torch.cuda.device(dev):
-        rc = _capi.lib().gsr_ply_activate_layout(raw_dev.data_ptr(), n, out["means3D"].data_ptr(), out["scales"].data_ptr(),
-                                                 out["rotations"].data_ptr(), out["opacities"].data_ptr(),
-                                                 out["shs"].data_ptr(), layout, torch.cuda.current_stream(dev).cuda_stream)
-    _capi.check(rc, "gsr_ply_activate_layout")
+    _capi.call("gsr_ply_activate_layout", raw_dev.data_ptr(), n, out["means3D"].data_ptr(), out["scales"].data_ptr(),
+               out["rotations"].data_ptr(), out["opacities"].data_ptr(), out["shs"].data_ptr(), layout, _capi.stream(dev), device=dev)
     out["sh_layout"] = sh_layout
     torch.cuda.current_stream(dev).synchronize()
     pos = out["means3D"][:, :3]

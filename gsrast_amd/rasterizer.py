@@ -155,8 +155,7 @@ class SplatRasterizer:
         # this view's tile history (gsr_tile_history: how long the tiles of its last frames took; the blend starts the slow
         # ones first). One per rasterizer object, so two of them on one thread do not feed each other's frames.
         self._history = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _capi.check(self.lib.gsr_tile_history_create(C.byref(self._history)), "gsr_tile_history_create")
+        _capi.call("gsr_tile_history_create", C.byref(self._history), device=self.device)
 
     _history = None             # (until __init__ has created it: __del__ also runs after an __init__ that raised)
 
@@ -248,7 +247,7 @@ class SplatRasterizer:
         a.view_matrix, a.proj_matrix, a.cam_pos = self._view.data_ptr(), self._proj.data_ptr(), self._cam_pos.data_ptr()
         a.tan_fovx, a.tan_fovy = self._tan
         a.out_color = out_color.data_ptr()
-        a.stream = torch.cuda.current_stream(self.device).cuda_stream
+        a.stream = _capi.stream(self.device)
         return a
 
     def draw(self, cam: Camera | None = None, *, profile: bool = False, count_staged: bool = False,
@@ -332,9 +331,7 @@ class SplatRasterizer:
             a.out_depth = out_depth.data_ptr()
         if tile_rows is not None:
             a.tile_row_begin, a.tile_row_end = int(tile_rows[0]), int(tile_rows[1])
-        with torch.cuda.device(self.device):
-            rc = self.lib.gsr_forward(C.byref(a))
-        _capi.check(rc, "gsr_forward")
+        _capi.call("gsr_forward", C.byref(a), device=self.device)
         self.last_receipt = a.receipt.copy()
         self.last_colors_precomp = colors_used is not None
         self.last_depth = depth
@@ -359,7 +356,7 @@ class SplatRasterizer:
     def tile_history_stats(self) -> dict:
         """gsr_tile_history_stats of this object's history (host side; what the last sort of the blend's tile order found)."""
         out = (C.c_uint32 * 6)()
-        _capi.check(self.lib.gsr_tile_history_stats(self._history, out), "gsr_tile_history_stats")
+        _capi.call("gsr_tile_history_stats", self._history, out)
         return {"mean_ticks": int(out[0]), "longest_ticks": int(out[1]), "similarity": int(out[2]) / 1000.0,
                 "order_dropped": bool(out[3]), "calls": int(out[4]), "overlapped": bool(out[5])}
 
@@ -368,7 +365,7 @@ class SplatRasterizer:
         bool[tiles] (composited by four waves), and the number of deep tiles of the last sorted order (gsr_tile_history_times)."""
         tiles = ((self.width + 15) // 16) * ((self.height + 15) // 16)
         out, deep = (C.c_uint32 * tiles)(), C.c_uint32(0)
-        _capi.check(self.lib.gsr_tile_history_times(self._history, out, tiles, C.byref(deep)), "gsr_tile_history_times")
+        _capi.call("gsr_tile_history_times", self._history, out, tiles, C.byref(deep))
         raw = np.frombuffer(out, dtype=np.uint32).copy()
         return raw & 0x7FFFFFFF, (raw >> 31).astype(bool), int(deep.value)
 
@@ -377,17 +374,15 @@ class SplatRasterizer:
         key = (self.shs.data_ptr(), self.shs._version)          # (callers may replace or write rast.shs between frames)
         if self._colors_dc is None or self._colors_key != key:
             c = torch.empty((self.num_gaussians, 3), dtype=torch.float32, device=self.device)
-            with torch.cuda.device(self.device):
-                rc = self.lib.gsr_colors_from_dc(self.num_gaussians, self.shs.data_ptr(), c.data_ptr(),
-                                                 torch.cuda.current_stream(self.device).cuda_stream)
-            _capi.check(rc, "gsr_colors_from_dc")
+            _capi.call("gsr_colors_from_dc", self.num_gaussians, self.shs.data_ptr(), c.data_ptr(), _capi.stream(self.device),
+                       device=self.device)
             self._colors_dc, self._colors_key = c, key
         return self._colors_dc
 
     def poll_async_error(self, receipt: "_capi.ForwardReceipt | None" = None) -> None:
         """After the stream of a draw() has been synchronised: raises if a device-side wait of that call gave up."""
         r = receipt if receipt is not None else self.last_receipt
-        _capi.check(self.lib.gsr_poll_async_error(C.byref(r)), "gsr_forward (device side)")
+        _capi.call("gsr_poll_async_error", C.byref(r), where="gsr_forward (device side)")
 
     # -- point-splat path (gscuda::forwardPoints, GSCuda.cu:110-155) -----------------------------
     def draw_points(self, cam: Camera | None = None, sync: bool = True) -> torch.Tensor:
@@ -399,9 +394,7 @@ class SplatRasterizer:
         if self._means3 is None or self._means3.shape[0] != self.num_gaussians:
             self._means3 = self.means3D[:, :3].contiguous()        # this path reads a stride of three floats
         a = self._forward_args(self._means3, self.out_color)
-        with torch.cuda.device(self.device):
-            rc = self.lib.gsr_forward_points(C.byref(a))
-        _capi.check(rc, "gsr_forward_points")
+        _capi.call("gsr_forward_points", C.byref(a), device=self.device)
         if sync:
             torch.cuda.current_stream(self.device).synchronize()
         return self.out_color
@@ -439,7 +432,7 @@ class SplatRasterizer:
         a.point_list = bst.values
         a.means3D, a.view_matrix = self.means3D.data_ptr(), self._view.data_ptr()
         a.tan_fovx, a.tan_fovy = self._tan
-        a.stream = torch.cuda.current_stream(self.device).cuda_stream
+        a.stream = _capi.stream(self.device)
         if rcpt is not None:
             a.receipt = rcpt
         return a
@@ -512,12 +505,13 @@ class SplatRasterizer:
             a.scale_modifier = scale_modifier
         if tile_rows is not None:
             a.tile_row_begin, a.tile_row_end = int(tile_rows[0]), int(tile_rows[1])
-        with torch.cuda.device(dev):
-            rc = self.lib.gsr_backward(C.byref(a))
-        if rc != _capi.GSR_OK and wide_sums:     # (a call that failed half way may have left sums behind: the next starts from zeroed ones)
-            self._bw.scratch.pop("sums_f64", None)
-            self._bw.scratch.pop("depth_sums_f64", None)
-        _capi.check(rc, "gsr_backward")
+        try:
+            _capi.call("gsr_backward", C.byref(a), device=dev)
+        except _capi.GsrError:
+            if wide_sums:                        # (a call that failed half way may have left sums behind: the next starts from zeroed ones)
+                self._bw.scratch.pop("sums_f64", None)
+                self._bw.scratch.pop("depth_sums_f64", None)
+            raise
         self.last_backward_ms = (float(a.stage_ms[0]), float(a.stage_ms[1])) if profile else ()
         if camera:
             arrays.update(self.camera_backward({k: arrays[k] for k in plan.camera_inputs}, semantics=semantics,
@@ -581,10 +575,8 @@ class SplatRasterizer:
             g = into
         a.dL_dview_matrix, a.dL_dproj_matrix, a.dL_dcam_pos = g[0:16].data_ptr(), g[16:32].data_ptr(), g[32:35].data_ptr()
         a.scratch = scratch.data_ptr()
-        a.stream = torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            rc = self.lib.gsr_camera_backward(C.byref(a))
-        _capi.check(rc, "gsr_camera_backward")
+        a.stream = _capi.stream(dev)
+        _capi.call("gsr_camera_backward", C.byref(a), device=dev)
         self.last_camera_ms = float(a.stage_ms) if profile else None
         if sync:
             torch.cuda.current_stream(dev).synchronize()
@@ -635,31 +627,24 @@ class SplatRasterizer:
 
 # ---- stage-level wrappers (unit parity tests) ------------------------------------------
 def inclusive_scan_u32(x: torch.Tensor) -> torch.Tensor:
-    L = _capi.lib()
     assert x.dtype == torch.int32 and x.is_cuda and x.is_contiguous()
     out = torch.empty_like(x)
-    temp = torch.empty(max(int(L.gsr_scan_temp_bytes(x.numel())), 128), dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = L.gsr_inclusive_scan_u32(x.data_ptr(), out.data_ptr(), x.numel(), temp.data_ptr(),
-                                      torch.cuda.current_stream(x.device).cuda_stream)
-    _capi.check(rc, "gsr_inclusive_scan_u32")
+    temp = torch.empty(max(int(_capi.lib().gsr_scan_temp_bytes(x.numel())), 128), dtype=torch.uint8, device=x.device)
+    _capi.call("gsr_inclusive_scan_u32", x.data_ptr(), out.data_ptr(), x.numel(), temp.data_ptr(), _capi.stream(x.device), device=x.device)
     torch.cuda.current_stream(x.device).synchronize()
     return out
 
 
 def sort_pairs(keys: torch.Tensor, values: torch.Tensor, end_bit: int = 64, begin_bit: int = 0, sync: bool = True,
                out=None, temp=None):
-    L = _capi.lib()
     assert keys.dtype == torch.int64 and values.dtype == torch.int32 and keys.is_cuda
     assert keys.is_contiguous() and values.is_contiguous() and keys.numel() == values.numel()
     n = keys.numel()
     ko, vo = out if out is not None else (torch.empty_like(keys), torch.empty_like(values))
     if temp is None:
-        temp = torch.empty(max(int(L.gsr_sort_temp_bytes(n)), 128), dtype=torch.uint8, device=keys.device)
-    with torch.cuda.device(keys.device):
-        rc = L.gsr_sort_pairs_u64_u32(keys.data_ptr(), ko.data_ptr(), values.data_ptr(), vo.data_ptr(), n, begin_bit,
-                                      end_bit, temp.data_ptr(), torch.cuda.current_stream(keys.device).cuda_stream)
-    _capi.check(rc, "gsr_sort_pairs_u64_u32")
+        temp = torch.empty(max(int(_capi.lib().gsr_sort_temp_bytes(n)), 128), dtype=torch.uint8, device=keys.device)
+    _capi.call("gsr_sort_pairs_u64_u32", keys.data_ptr(), ko.data_ptr(), values.data_ptr(), vo.data_ptr(), n, begin_bit, end_bit,
+               temp.data_ptr(), _capi.stream(keys.device), device=keys.device)
     if sync:
         torch.cuda.current_stream(keys.device).synchronize()
     return ko, vo

@@ -348,10 +348,13 @@ typedef struct gsr_forward_args {
  * R == 0 returns GSR_OK and leaves out_color untouched (GSCuda.cu:775-778); out_depth, if given, is zeroed. */
 int gsr_forward(gsr_forward_args* args);
 
-/* Sticky last error of the calling thread's most recent gsr_* call + its text. */
+/* The error contract. It covers every function of this header that returns a GSR_* code — not the queries that return a
+ * size_t, the *_from_chunk functions, gsr_exchange_plan (a count), gsr_higher_msb, gsr_device_shape, gsr_reread_environment
+ * and the three functions below. Each covered call forgets the previous HIP text on entry and leaves the code it returns as
+ * the calling thread's last error: a successful call sets it to GSR_OK. */
 int gsr_last_error(void);
 const char* gsr_error_string(int code);
-/* Text of the HIP error behind the last GSR_ERR_HIP ("" if none). */
+/* Text of the HIP error behind the GSR_ERR_HIP of the calling thread's most recent covered call ("" if it did not fail in HIP). */
 const char* gsr_last_hip_error(void);
 
 /* After the caller has synchronised the stream of the gsr_forward call that issued `receipt`: GSR_OK, or

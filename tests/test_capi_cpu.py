@@ -221,3 +221,106 @@ def test_device_shape_follows_the_compute_unit_count():
 def test_thread_release_without_any_call_is_a_no_op():
     L = _capi.lib()
     assert L.gsr_thread_release() == _capi.GSR_OK and L.gsr_thread_release() == _capi.GSR_OK
+
+
+# ---- the error contract of every entry point that returns a GSR_* code (include/gsrast_amd.h, entry_point in csrc/gsr_common.hpp) ----
+_NOT_STATUS = {"gsr_last_error", "gsr_exchange_plan"}      # c_int too: the last error itself; a count or a negated code
+_AT = 0x10000                                               # an invented, 16-byte aligned address: only in calls of ZERO elements
+
+
+def _adam_args(rows):
+    a = _capi.AdamArgs()
+    a.struct_size, a.num_tensors, a.num_rows = C.sizeof(_capi.AdamArgs), 1, rows
+    t = a.tensors[0]
+    t.param, t.grad, t.exp_avg, t.exp_avg_sq, t.row_floats = _AT, _AT, _AT, _AT, 3
+    return C.byref(a)
+
+
+def _apply_args_of_no_rows():
+    a = _capi.DensifyApplyArgs()
+    a.struct_size, a.src_of = C.sizeof(_capi.DensifyApplyArgs), _AT                     # (n_src and the four counts: 0)
+    for k in ("xyz", "opacity_logit", "log_scale", "rotation", "shs"):
+        getattr(a, k).src, getattr(a, k).dst = _AT, _AT
+    return C.byref(a)
+
+
+def _live_receipt():
+    """A receipt whose call has nothing to report: words {N-sized sort, R-sized sort, owner, 0} in host memory."""
+    words = (C.c_uint32 * 4)(0, 0, 7, 0)
+    r = _capi.ForwardReceipt()
+    r.magic, r.serial, r.async_words = _capi.GSR_RECEIPT_MAGIC, 7, C.addressof(words)
+    r._words = words
+    return C.byref(r)
+
+
+def _ply_header(tmp_path, good):
+    p = tmp_path / ("good.ply" if good else "absent.ply")
+    if good:
+        p.write_bytes(b"ply\nformat binary_little_endian 1.0\nelement vertex 5\nproperty float x\nend_header\n")
+    return (str(p).encode(), C.byref(C.c_int(0)), C.byref(C.c_longlong(0)))
+
+
+_HOST = (C.c_uint32 * 256)()                                # real, zeroed host memory: refused by its content, never a device address
+_HOST_AT = C.addressof(_HOST)
+_INVALID = _capi.GSR_ERR_INVALID_ARG
+_forward_nulls = lambda _=None: (C.byref(_capi.ForwardArgs(struct_size=C.sizeof(_capi.ForwardArgs))),)
+# name -> (arguments that are refused, the code, arguments of a success that makes no HIP call); None: the entry point has no
+# such call. A callable is given tmp_path. No row reaches a HIP call: refusals and empty inputs only.
+ERROR_CONTRACT = {
+    "gsr_forward": (_forward_nulls, _INVALID, None),
+    "gsr_backward": ((None,), _INVALID, None),
+    "gsr_camera_backward": ((None,), _INVALID, None),
+    "gsr_forward_points": ((None,), _INVALID, None),
+    "gsr_poll_async_error": ((None,), _INVALID, lambda _: (_live_receipt(),)),
+    "gsr_tile_history_create": ((None,), _INVALID, None),
+    "gsr_tile_history_destroy": ((_HOST_AT,), _INVALID, (None,)),                      # (zeroed memory is no history: the magic)
+    "gsr_tile_history_stats": ((None, None), _INVALID, None),
+    "gsr_tile_history_forget_stream": ((None,), _INVALID, None),
+    "gsr_tile_history_times": ((None, None, 0, None), _INVALID, None),
+    "gsr_thread_release": (None, None, ()),
+    "gsr_inclusive_scan_u32": ((None, None, 1, None, None), _INVALID, (None, None, 0, None, None)),
+    "gsr_sort_pairs_u64_u32": ((None, None, None, None, 1, 0, 64, None, None), _INVALID, (None, None, None, None, 0, 0, 64, None, None)),
+    "gsr_exchange_unique_id": ((None, None), _INVALID, None),
+    "gsr_exchange_create": ((None, None, 0, 1, None), _INVALID, None),
+    "gsr_exchange_bands": ((None, None, 64, 64, None, -1, None), _INVALID, None),
+    "gsr_exchange_loopback": ((None, None, None, 0, 1, None), _INVALID, None),
+    "gsr_exchange_destroy": (None, None, (None,)),
+    "gsr_ply_parse_header": (lambda tmp: _ply_header(tmp, False), _INVALID, lambda tmp: _ply_header(tmp, True)),
+    "gsr_ply_activate": ((None, 1) + (None,) * 6, _INVALID, (_AT, 0) + (_AT,) * 5 + (None,)),
+    "gsr_ply_activate_layout": ((None, 1) + (None,) * 5 + (0, None), _INVALID, (_AT, 0) + (_AT,) * 5 + (0, None)),
+    "gsr_colors_from_dc": ((1, None, None, None), _INVALID, (0, _AT, _AT, None)),
+    "gsr_blend_expf": ((1, None, None, None), _INVALID, (0, _AT, _AT, None)),
+    "gsr_footprint_misses_tile": ((1, None, None, None, 16, 16, None, None), _INVALID, (0, _AT, _AT, _AT, 16, 16, _AT, None)),
+    "gsr_activate_params": ((1,) + (None,) * 9, _INVALID, (0,) + (_AT,) * 8 + (None,)),
+    # (an output asked for — host memory, never reached — without the gradient it is computed from)
+    "gsr_activate_params_backward": ((1,) + (None,) * 8 + (_HOST_AT,) + (None,) * 4, _INVALID, (0,) + (_AT,) * 12 + (None,)),
+    "gsr_adam_step": (lambda _: (_adam_args(-1),), _INVALID, lambda _: (_adam_args(0),)),
+    "gsr_photo_loss_forward": ((None,), _INVALID, None),
+    "gsr_photo_loss_backward": ((None,), _INVALID, None),
+    "gsr_densify_accumulate": ((1, None, None, 32.0, 32.0, None, None, None, None), _INVALID, (0, _AT, _AT, 32.0, 32.0, _AT, _AT, _AT, None)),
+    "gsr_densify_plan": ((1,) + (None,) * 5 + (0.0,) * 5 + (0,) + (None,) * 4, _INVALID, None),   # (n == 0 clears the counts: a HIP call)
+    "gsr_densify_apply": ((None,), _INVALID, lambda _: (_apply_args_of_no_rows(),)),
+}
+
+
+def test_the_error_contract_table_names_every_status_returning_entry_point():
+    derived = {name for name, (res, _) in _capi.SIGNATURES.items() if res is C.c_int} - _NOT_STATUS
+    assert derived == set(ERROR_CONTRACT), sorted(derived ^ set(ERROR_CONTRACT))
+
+
+@pytest.mark.parametrize("name", sorted(ERROR_CONTRACT))
+def test_every_status_returning_entry_point_keeps_the_error_contract(name, tmp_path):
+    """A refusal returns its code and leaves it as the last error; a success returns GSR_OK and leaves GSR_OK, directly after
+    another entry point was refused; neither leaves a HIP text (none of these calls reaches the HIP runtime)."""
+    L = _capi.lib()
+    refused, code, fine = ERROR_CONTRACT[name]
+    args_of = lambda a: a(tmp_path) if callable(a) else a
+    assert refused is not None or fine is not None
+    if refused is not None:
+        assert L.gsr_tile_history_destroy(None) == _capi.GSR_OK and L.gsr_last_error() == _capi.GSR_OK
+        assert getattr(L, name)(*args_of(refused)) == code
+        assert L.gsr_last_error() == code and L.gsr_last_hip_error() == b""
+    if fine is not None:
+        assert L.gsr_forward(*_forward_nulls()) == _INVALID and L.gsr_last_error() == _INVALID
+        assert getattr(L, name)(*args_of(fine)) == _capi.GSR_OK
+        assert L.gsr_last_error() == _capi.GSR_OK and L.gsr_last_hip_error() == b""
