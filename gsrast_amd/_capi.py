@@ -1,4 +1,4 @@
-"""ctypes binding of include/gsrast_amd.h (the C ABI of libgsrast_amd.so).
+"""ctypes binding of include/gsrast_amd.h and include/gsrast_amd_init.h (the C ABI of libgsrast_amd.so).
 
 There is no fallback: if the HIP library has not been built, importing the product path
 raises. Field order and types below mirror the header exactly.
@@ -248,6 +248,16 @@ SIGNATURES = {
     "gsr_densify_apply": (C.c_int, [C.POINTER(DensifyApplyArgs)]),
 }
 
+# include/gsrast_amd_init.h (initialisation from a point cloud), in the same shape; its own symbol test checks it against that header.
+GSR_KNN_LEAF = 64
+GSR_KNN_NODE = 32
+GSR_KNN_MORTON_BITS = 21
+GSR_KNN_MAX_POINTS = 1 << 30
+INIT_SIGNATURES = {
+    "gsr_knn_temp_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_knn_mean_dist2": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -272,7 +282,7 @@ def lib() -> C.CDLL:
         # library resolves that soname, otherwise two HIP runtimes end up in the process and
         # torch's device pointers mean nothing to ours ("no HIP device"): this module imports torch first.
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(INIT_SIGNATURES.items()):
             fn = getattr(L, name, None)
             if fn is None and _TAG:
                 continue                       # (a tagged A/B build of an older tree may lack the newest entry points)

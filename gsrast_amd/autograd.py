@@ -292,6 +292,33 @@ class GaussianParams(torch.nn.Module):
             sh = _rest_to_coefficient_major(sh)
         return cls(rec[:, 0:3], rec[:, 54], rec[:, 55:58], rec[:, 58:62], sh, sh_layout, device)
 
+    @classmethod
+    def from_points(cls, xyz, rgb, sh_layout: str = "file", device="cuda:0") -> "GaussianParams":
+        """Initial Gaussians of a point cloud, as upstream's create_from_pcd makes them (init.initial_values): xyz [N,3]
+        and rgb [N,3], arrays or tensors; rgb float in [0, 1], or uint8, which is divided by 255. The positions are
+        checked once (one synchronisation, at initialisation): a non-finite one is a ValueError."""
+        from . import init as _init
+        dev = torch.device(device)
+
+        def on_device(a, name):
+            t = a.detach() if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+            if t.dim() != 2 or t.shape[1] != 3:
+                raise ValueError(f"from_points: {name} is {tuple(t.shape)}, not [N, 3]")
+            return t.to(dev)
+        pos, col = on_device(xyz, "xyz"), on_device(rgb, "rgb")
+        if col.shape[0] != pos.shape[0]:
+            raise ValueError(f"from_points: {pos.shape[0]} positions and {col.shape[0]} colours")
+        col = col.to(F32) / 255.0 if col.dtype == torch.uint8 else col.to(F32)
+        pos = pos.to(F32).contiguous()
+        if not bool(torch.isfinite(pos).all()):
+            raise ValueError("from_points: a position is not finite")
+        return cls(*_init.initial_values(pos, col), sh_layout, device)
+
+    @classmethod
+    def from_points_ply(cls, path: str, sh_layout: str = "file", device="cuda:0") -> "GaussianParams":
+        """`from_points` of a points3D.ply (ply.read_points_ply)."""
+        return cls.from_points(*_ply.read_points_ply(path), sh_layout, device)
+
     @property
     def num_gaussians(self) -> int:
         return int(self.xyz.shape[0])
