@@ -117,18 +117,7 @@ int check_arguments(gsr_forward_args* a, Readback** out) {
 int carve_chunks(ForwardCall& c) {
     gsr_forward_args* const a = c.a;
     FrameDims& d = c.d;
-    d.width = a->width;
-    d.height = a->height;
-    d.grid_x = (a->width + kTile - 1) / kTile;
-    d.grid_y = (a->height + kTile - 1) / kTile;
-    d.row_begin = 0;
-    d.row_end = d.grid_y;
-    if (a->tile_row_begin != 0 || a->tile_row_end != 0) {
-        if (a->tile_row_begin < 0 || a->tile_row_end > d.grid_y || a->tile_row_begin > a->tile_row_end)
-            return GSR_ERR_INVALID_ARG;
-        d.row_begin = a->tile_row_begin;
-        d.row_end = a->tile_row_end;
-    }
+    GSR_TRY(tile_band(a->width, a->height, a->tile_row_begin, a->tile_row_end, &d));
     c.num_tiles = d.grid_x * d.grid_y;
     c.tiles = (unsigned long long)(d.row_end - d.row_begin) * (unsigned long long)d.grid_x;
     c.xy_plan = d.grid_x <= 255 && d.grid_y <= 255;

@@ -14,9 +14,14 @@
 // (nContrib) starting at its final transmittance, re-deriving T_i = T_{i+1} / (1 - alpha_i); the nine
 // partial sums of a record are reduced over the wave with DPP row shifts / broadcasts and leave as
 // nine float atomics per (record, tile) — only records that some pixel of the tile composited.
+//
+// The host call (the end of this file): which pointers of gsr_backward_args must come together, the band of tile rows, the
+// profiles' focal lengths and the table of the output arrays are backward_policy.hpp's (pure, tested on the CPU);
+// gsr_backward makes one BackwardCall context from its answer and runs backward_stages() over it, a function per stage.
 #include <hip/hip_runtime.h>
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
+#include "backward_policy.hpp"
 #include "blend_core.hpp"
 #include "blockbin.hpp"
 
@@ -883,106 +888,71 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(const Preproce
     }
 }
 
-// Events of one profiled call: created on the device that is current for THIS call, destroyed when it returns.
-struct CallEvents {
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    int create() {
-        for (auto& e : ev) GSR_HIP_TRY(hipEventCreate(&e));
-        return GSR_OK;
-    }
-    ~CallEvents() {
-        for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
+// ---- the host call: one context (BackwardCall) and one function per stage over it, in the order backward_stages() calls them ----
+
+// The state of one gsr_backward call: what its stages hand to each other.
+struct BackwardCall {
+    gsr_backward_args* const a;
+    const hipStream_t stream;
+    const BackwardChoice choice;        // (backward_policy.hpp: the call's modes and its band of tile rows)
+    BlockFeed feed = {};
+    bool from_blocks = false, lists_written = true, nothing_rendered = false;
+    CallEvents<3> events;               // GSR_FLAG_PROFILE: before the render backward, between it and the chain, behind the chain
+
+    BackwardCall(gsr_backward_args* a_, const BackwardChoice& choice_) : a(a_), stream((hipStream_t)a_->stream), choice(choice_) {}
+    int begin_profile() { if (choice.profile) GSR_TRY(events.create()); return mark(0); }
+    int mark(int k) { if (choice.profile) GSR_HIP_TRY(hipEventRecord(events.ev[k], stream)); return GSR_OK; }
 };
 
-}  // namespace
-}  // namespace gsr
-
-using namespace gsr;
-
-static int backward_impl(gsr_backward_args* a) {
-    if (!a || a->struct_size != sizeof(gsr_backward_args)) return GSR_ERR_INVALID_ARG;
-    a->stage_ms[0] = a->stage_ms[1] = 0.0f;
-    const int n = a->num_gaussians;
-    if (n <= 0 || a->width <= 0 || a->height <= 0 || !a->background || !a->means2D || !a->conic_opacity || !a->colors ||
-        !a->ranges || !a->n_contrib || !a->final_t || !a->dL_dout_color)
-        return GSR_ERR_INVALID_ARG;
-    // (the float arrays of the sums are where the sums are kept unless sums_f64 keeps them: optional outputs then)
-    const bool wide = a->sums_f64 != nullptr;
-    if (!wide && (!a->dL_dmean2D || !a->dL_dconic_opacity || !a->dL_dcolors)) return GSR_ERR_INVALID_ARG;
-    // the chain runs for whichever of its outputs is asked for; without sums_f64 it starts from dL_dcov3D's presence as before
-    const bool chain = a->dL_dcov3D || (wide && (a->dL_dmeans3D || a->dL_dscales || a->dL_dshs));
-    if (chain && (!a->cov3D || !a->means3D || !a->view_matrix || !a->radii)) return GSR_ERR_INVALID_ARG;
-    if ((a->dL_dmeans3D || a->dL_dscales || a->dL_drotations) && !chain) return GSR_ERR_INVALID_ARG;
-    if (a->dL_dmeans3D && !a->proj_matrix) return GSR_ERR_INVALID_ARG;
-    if ((a->dL_dscales || a->dL_drotations) && (!a->scales || !a->rotations || !a->dL_dscales)) return GSR_ERR_INVALID_ARG;
-    const bool inria = (a->flags & GSR_FLAG_SEMANTICS_INRIA) != 0;
-    // the upstream profile's chain needs what its colour was computed from
-    if (inria && a->dL_dshs && (!a->shs || !a->cam_pos || !a->clamped || !a->means3D)) return GSR_ERR_INVALID_ARG;
-    // the depth channel: d_i is recomputed from means3D and the view; its sums go to depth_sums_f64 beside sums_f64, else to dL_ddepths
-    const bool depth = a->dL_dout_depth != nullptr;
-    if (depth && (!a->means3D || !a->view_matrix || (wide ? !a->depth_sums_f64 : !a->dL_ddepths))) return GSR_ERR_INVALID_ARG;
-    hipStream_t stream = (hipStream_t)a->stream;
-    const bool profile = (a->flags & GSR_FLAG_PROFILE) != 0;
-    CallEvents g_bw;
-    hipEvent_t* const g_bw_ev = g_bw.ev;
-    if (profile) {
-        const int rc = g_bw.create();
-        if (rc != GSR_OK) return rc;
-    }
-
-    FrameDims d;
-    d.width = a->width; d.height = a->height;
-    d.grid_x = (a->width + kTile - 1) / kTile; d.grid_y = (a->height + kTile - 1) / kTile;
-    d.row_begin = 0; d.row_end = d.grid_y;
-    if (a->tile_row_begin != 0 || a->tile_row_end != 0) {
-        if (a->tile_row_begin < 0 || a->tile_row_end > d.grid_y || a->tile_row_begin > a->tile_row_end) return GSR_ERR_INVALID_ARG;
-        d.row_begin = a->tile_row_begin; d.row_end = a->tile_row_end;
-    }
-    // Which lists the forward call left (see gsr_backward_args.receipt). With a receipt: from the receipt and the chunk
-    // layouts — where that call ran the block plan, its block lists serve the tiles of shallow blocks (per-entry gradient
-    // sums, see block_acc_fits) and, if it left the sorted lists unwritten (GSR_FLAG_NO_SORTED_LISTS), all tiles. Without
-    // one only the reference's contract can hold (sorted lists in point_list), and whether it does is read off
-    // point_list[0]: a call that skipped the lists left GSR_LISTS_SKIPPED_STAMP there.
-    BlockFeed feed = {};
-    bool from_blocks = false, lists_written = true;
-    const bool have_receipt = a->receipt.magic != 0;        // (any other magic than the library's: refused below)
-    bool nothing_rendered = false;
-    if (have_receipt) {
-        const int rc = lists_of_receipt(a->receipt, n, a->width, a->height, d.row_begin, d.row_end, a->point_list, &feed,
-                                        &from_blocks, &lists_written);
-        if (rc != GSR_OK) return rc;
-        nothing_rendered = a->receipt.num_rendered == 0;
-    } else {
-        if (!a->point_list) return GSR_ERR_INVALID_ARG;
-        uint32_t first = 0;
-        GSR_HIP_TRY(hipMemcpyAsync(&first, a->point_list, sizeof(first), hipMemcpyDeviceToHost, stream));
-        GSR_HIP_TRY(hipStreamSynchronize(stream));
-        if (first == GSR_LISTS_SKIPPED_STAMP) return GSR_ERR_INVALID_ARG;
-    }
-    // (with sums_f64 the float arrays are written once, by the kernel that rounds the double sums: no clearing)
-    if (!wide || nothing_rendered) {
-        if (a->dL_dmean2D) GSR_HIP_TRY(hipMemsetAsync(a->dL_dmean2D, 0, sizeof(float) * 2 * (size_t)n, stream));
-        if (a->dL_dconic_opacity) GSR_HIP_TRY(hipMemsetAsync(a->dL_dconic_opacity, 0, sizeof(float) * 4 * (size_t)n, stream));
-        if (a->dL_dcolors) GSR_HIP_TRY(hipMemsetAsync(a->dL_dcolors, 0, sizeof(float) * 3 * (size_t)n, stream));
-        if (a->dL_dcov2D) GSR_HIP_TRY(hipMemsetAsync(a->dL_dcov2D, 0, sizeof(float) * 4 * (size_t)n, stream));
-        if (depth && a->dL_ddepths) GSR_HIP_TRY(hipMemsetAsync(a->dL_ddepths, 0, sizeof(float) * (size_t)n, stream));
-    }
-    if (nothing_rendered) {
-        // R == 0: no Gaussian reached a pixel (the forward call left even the tile ranges unwritten, GSCuda.cu:775-778)
-        if (a->dL_dcov3D) GSR_HIP_TRY(hipMemsetAsync(a->dL_dcov3D, 0, sizeof(float) * 6 * (size_t)n, stream));
-        if (a->dL_dshs) GSR_HIP_TRY(hipMemsetAsync(a->dL_dshs, 0, sizeof(float) * 48 * (size_t)n, stream));
-        if (a->dL_dmeans3D) GSR_HIP_TRY(hipMemsetAsync(a->dL_dmeans3D, 0, sizeof(float) * 4 * (size_t)n, stream));
-        if (a->dL_dscales) GSR_HIP_TRY(hipMemsetAsync(a->dL_dscales, 0, sizeof(float) * 4 * (size_t)n, stream));
-        if (a->dL_drotations) GSR_HIP_TRY(hipMemsetAsync(a->dL_drotations, 0, sizeof(float) * 4 * (size_t)n, stream));
+// Which lists the forward call left (see gsr_backward_args.receipt). With a receipt: from the receipt and the chunk
+// layouts — where that call ran the block plan, its block lists serve the tiles of shallow blocks (per-entry gradient
+// sums, see block_acc_fits) and, if it left the sorted lists unwritten (GSR_FLAG_NO_SORTED_LISTS), all tiles. Without
+// one only the reference's contract can hold (sorted lists in point_list), and whether it does is read off
+// point_list[0]: a call that skipped the lists left GSR_LISTS_SKIPPED_STAMP there.
+int resolve_lists(BackwardCall& c) {
+    const gsr_backward_args* const a = c.a;
+    const FrameDims& d = c.choice.d;
+    if (c.choice.have_receipt) {
+        GSR_TRY(lists_of_receipt(a->receipt, a->num_gaussians, a->width, a->height, d.row_begin, d.row_end, a->point_list, &c.feed,
+                                 &c.from_blocks, &c.lists_written));
+        c.nothing_rendered = a->receipt.num_rendered == 0;
         return GSR_OK;
     }
-    if (profile) GSR_HIP_TRY(hipEventRecord(g_bw_ev[0], stream));
+    uint32_t first = 0;
+    GSR_HIP_TRY(hipMemcpyAsync(&first, a->point_list, sizeof(first), hipMemcpyDeviceToHost, c.stream));
+    GSR_HIP_TRY(hipStreamSynchronize(c.stream));
+    return first == GSR_LISTS_SKIPPED_STAMP ? GSR_ERR_INVALID_ARG : GSR_OK;
+}
+
+// Zeros in the output arrays [first, last) of kBackwardOutputs that the caller gave.
+int clear_range(const BackwardCall& c, int first, int last) {
+    for (int k = first; k < last; ++k) {
+        const BackwardOutput& o = kBackwardOutputs[k];
+        float* const array = c.a->*o.array;
+        if (!array || (o.array == &gsr_backward_args::dL_ddepths && !c.choice.depth)) continue;
+        GSR_HIP_TRY(hipMemsetAsync(array, 0, sizeof(float) * (size_t)o.row_floats * (size_t)c.a->num_gaussians, c.stream));
+    }
+    return GSR_OK;
+}
+
+// Where the render backward's float atomics land
+// (with sums_f64 the float arrays are written once, by the kernel that rounds the double sums: no clearing)
+int clear_outputs(const BackwardCall& c) {
+    return (!c.choice.wide || c.nothing_rendered) ? clear_range(c, 0, kBackwardSums) : GSR_OK;
+}
+
+// R == 0: no Gaussian reached a pixel (the forward call left even the tile ranges unwritten, GSCuda.cu:775-778)
+int finish_without_instances(const BackwardCall& c) {
+    return clear_range(c, kBackwardSums, (int)(sizeof(kBackwardOutputs) / sizeof(kBackwardOutputs[0])));
+}
+
+RenderBackwardParams render_params(const BackwardCall& c) {
+    const gsr_backward_args* const a = c.a;
+    const FrameDims& d = c.choice.d;
     RenderBackwardParams r;
     r.ranges = reinterpret_cast<const uint2*>(a->ranges);
-    r.point_list = lists_written ? a->point_list : nullptr;
-    r.feed = feed;
+    r.point_list = c.lists_written ? a->point_list : nullptr;
+    r.feed = c.feed;
     r.means2D = reinterpret_cast<const float2*>(a->means2D);
     r.colors = a->colors;
     r.conic_opacity = reinterpret_cast<const float4*>(a->conic_opacity);
@@ -998,87 +968,129 @@ static int backward_impl(gsr_backward_args* a) {
     r.dims = d;
     r.num_tiles = (d.row_end - d.row_begin) * d.grid_x;
     // (the tiles that were slow in the forward blend are the slow ones here: they go first, as they did there)
-    r.tile_order = have_receipt ? tile_order_of_call(a->receipt, d.row_begin, d.row_end) : nullptr;
+    r.tile_order = c.choice.have_receipt ? tile_order_of_call(a->receipt, d.row_begin, d.row_end) : nullptr;
     r.dL_dout_depth = a->dL_dout_depth;
     r.means3D = reinterpret_cast<const float4*>(a->means3D);
     r.view = a->view_matrix;
-    r.depth_inverse = (a->flags & GSR_FLAG_DEPTH_INVERSE) ? 1u : 0u;
+    r.depth_inverse = c.choice.depth_inverse ? 1u : 0u;
     r.dL_ddepths = a->dL_ddepths;
-    r.depth_sums64 = wide ? a->depth_sums_f64 : nullptr;
+    r.depth_sums64 = c.choice.wide ? a->depth_sums_f64 : nullptr;
+    return r;
+}
+
+PreprocessBackwardParams chain_params(const BackwardCall& c, const RenderBackwardParams& r) {
+    const gsr_backward_args* const a = c.a;
+    // (the kernel reads `focal` under the reference's profile, focal_x / focal_y / w_eps under the upstream one)
+    const ProfileLens lens = profile_lens(c.choice.inria, a->width, a->height, a->tan_fovx, a->tan_fovy, a->sh_dims);
+    PreprocessBackwardParams q;
+    q.n = a->num_gaussians;
+    q.means3D = reinterpret_cast<const float4*>(a->means3D);
+    q.cov3D = a->cov3D;
+    q.radii = a->radii;
+    q.view = a->view_matrix;
+    q.tan_fovx = a->tan_fovx; q.tan_fovy = a->tan_fovy;
+    q.focal = lens.focal_y;
+    q.dL_dconic_opacity = reinterpret_cast<const float4*>(a->dL_dconic_opacity);
+    q.dL_dcov2D = reinterpret_cast<const float4*>(a->dL_dcov2D);
+    q.sums64 = a->sums_f64;
+    q.out_mean2D = reinterpret_cast<float2*>(a->dL_dmean2D);
+    q.out_conic_opacity = reinterpret_cast<float4*>(a->dL_dconic_opacity);
+    q.out_colors = a->dL_dcolors;
+    q.out_cov2D = reinterpret_cast<float4*>(a->dL_dcov2D);
+    q.dL_dcolors = a->dL_dcolors;
+    q.dL_dcov3D = a->dL_dcov3D;
+    q.chain = c.choice.chain ? 1 : 0;                      // (without the chain the kernel only rounds the double sums)
+    q.dL_dshs = c.choice.chain ? a->dL_dshs : nullptr;
+    q.proj = a->proj_matrix;
+    q.scales = reinterpret_cast<const float4*>(a->scales);
+    q.rotations = reinterpret_cast<const float4*>(a->rotations);
+    q.scale_modifier = a->scale_modifier;
+    q.width = a->width; q.height = a->height;
+    q.dL_dmean2D = reinterpret_cast<const float2*>(a->dL_dmean2D);
+    q.dL_dmeans3D = reinterpret_cast<float4*>(a->dL_dmeans3D);
+    q.dL_dscales = reinterpret_cast<float4*>(a->dL_dscales);
+    q.dL_drotations = reinterpret_cast<float4*>(a->dL_drotations);
+    q.inria = c.choice.inria ? 1 : 0;
+    q.sh_deg = lens.sh_deg;
+    q.focal_x = lens.focal_x; q.focal_y = lens.focal_y; q.w_eps = lens.w_eps;
+    q.depth = c.choice.depth ? 1 : 0;
+    q.depth_inverse = (int)r.depth_inverse;
+    q.dL_ddepths = a->dL_ddepths;
+    q.depth_sums64 = r.depth_sums64;
+    q.out_ddepths = a->dL_ddepths;
+    q.shs = a->shs; q.cam_pos = a->cam_pos; q.clamped = a->clamped;
+    return q;
+}
+
+// The render backward, between the two kernels that clear and flush the per-entry sums where the block lists feed it.
+template <bool DEPTH>
+int launch_render_as(const BackwardCall& c, const RenderBackwardParams& r) {
+    const gsr_backward_args* const a = c.a;
+    const FrameDims& d = c.choice.d;
     // (all blocks of the frame, also in a sharded call: the blocks outside the band were not walked)
     const unsigned acc_wgs = (unsigned)(((d.grid_x + kBW - 1) / kBW) * ((d.grid_y + kBH - 1) / kBH)) * kAccParts;
-    if (r.num_tiles > 0) {
-        const dim3 grid((unsigned)patch_workgroups(d.grid_x, d.row_end - d.row_begin));
-        auto launch = [&](auto with_depth) -> int {
-            constexpr bool D = decltype(with_depth)::value;
-            if (from_blocks && feed.acc) {
-                hipLaunchKernelGGL(zero_block_acc_kernel<D>, dim3(acc_wgs), dim3(256), 0, stream, feed);
-                GSR_LAUNCH_CHECK("zero_block_acc_kernel");
-            }
-            hipLaunchKernelGGL(render_backward_kernel<D>, grid, dim3(kWave), 0, stream, r);
-            GSR_LAUNCH_CHECK("render_backward_kernel");
-            if (from_blocks && feed.acc) {
-                hipLaunchKernelGGL(flush_block_acc_kernel<D>, dim3(acc_wgs), dim3(256), 0, stream, feed, a->dL_dmean2D, a->dL_dconic_opacity,
-                                   a->dL_dcolors, a->dL_dcov2D, a->sums_f64, r.dL_ddepths, r.depth_sums64);
-                GSR_LAUNCH_CHECK("flush_block_acc_kernel");
-            }
-            return GSR_OK;
-        };
-        const int rc = depth ? launch(std::true_type{}) : launch(std::false_type{});
-        if (rc != GSR_OK) return rc;
+    const bool per_entry = c.from_blocks && c.feed.acc;
+    if (per_entry) {
+        hipLaunchKernelGGL(zero_block_acc_kernel<DEPTH>, dim3(acc_wgs), dim3(256), 0, c.stream, c.feed);
+        GSR_LAUNCH_CHECK("zero_block_acc_kernel");
     }
-    if (profile) GSR_HIP_TRY(hipEventRecord(g_bw_ev[1], stream));
-    if (chain || wide) {
-        PreprocessBackwardParams q;
-        q.n = n;
-        q.means3D = reinterpret_cast<const float4*>(a->means3D);
-        q.cov3D = a->cov3D;
-        q.radii = a->radii;
-        q.view = a->view_matrix;
-        q.tan_fovx = a->tan_fovx; q.tan_fovy = a->tan_fovy;
-        q.focal = (float)a->height / (2.0f * a->tan_fovy);
-        q.dL_dconic_opacity = reinterpret_cast<const float4*>(a->dL_dconic_opacity);
-        q.dL_dcov2D = reinterpret_cast<const float4*>(a->dL_dcov2D);
-        q.sums64 = a->sums_f64;
-        q.out_mean2D = reinterpret_cast<float2*>(a->dL_dmean2D);
-        q.out_conic_opacity = reinterpret_cast<float4*>(a->dL_dconic_opacity);
-        q.out_colors = a->dL_dcolors;
-        q.out_cov2D = reinterpret_cast<float4*>(a->dL_dcov2D);
-        q.dL_dcolors = a->dL_dcolors;
-        q.dL_dcov3D = a->dL_dcov3D;
-        q.chain = chain ? 1 : 0;                               // (without the chain the kernel only rounds the double sums)
-        q.dL_dshs = chain ? a->dL_dshs : nullptr;
-        q.proj = a->proj_matrix;
-        q.scales = reinterpret_cast<const float4*>(a->scales);
-        q.rotations = reinterpret_cast<const float4*>(a->rotations);
-        q.scale_modifier = a->scale_modifier;
-        q.width = a->width; q.height = a->height;
-        q.dL_dmean2D = reinterpret_cast<const float2*>(a->dL_dmean2D);
-        q.dL_dmeans3D = reinterpret_cast<float4*>(a->dL_dmeans3D);
-        q.dL_dscales = reinterpret_cast<float4*>(a->dL_dscales);
-        q.dL_drotations = reinterpret_cast<float4*>(a->dL_drotations);
-        q.inria = inria ? 1 : 0;
-        q.sh_deg = a->sh_dims < 0 ? 0 : (a->sh_dims > 3 ? 3 : a->sh_dims);
-        q.focal_x = (float)a->width / (2.0f * a->tan_fovx);
-        q.focal_y = (float)a->height / (2.0f * a->tan_fovy);
-        q.w_eps = 0.0000001f;
-        q.depth = depth ? 1 : 0;
-        q.depth_inverse = (int)r.depth_inverse;
-        q.dL_ddepths = a->dL_ddepths;
-        q.depth_sums64 = r.depth_sums64;
-        q.out_ddepths = a->dL_ddepths;
-        q.shs = a->shs; q.cam_pos = a->cam_pos; q.clamped = a->clamped;
-        if (inria) hipLaunchKernelGGL(preprocess_backward_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, q);
-        else hipLaunchKernelGGL(preprocess_backward_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, q);
-        GSR_LAUNCH_CHECK("preprocess_backward_kernel");
-    }
-    if (profile) {
-        GSR_HIP_TRY(hipEventRecord(g_bw_ev[2], stream));
-        GSR_HIP_TRY(hipStreamSynchronize(stream));
-        GSR_HIP_TRY(hipEventElapsedTime(&a->stage_ms[0], g_bw_ev[0], g_bw_ev[1]));
-        GSR_HIP_TRY(hipEventElapsedTime(&a->stage_ms[1], g_bw_ev[1], g_bw_ev[2]));
+    const dim3 grid((unsigned)patch_workgroups(d.grid_x, d.row_end - d.row_begin));
+    hipLaunchKernelGGL(render_backward_kernel<DEPTH>, grid, dim3(kWave), 0, c.stream, r);
+    GSR_LAUNCH_CHECK("render_backward_kernel");
+    if (per_entry) {
+        hipLaunchKernelGGL(flush_block_acc_kernel<DEPTH>, dim3(acc_wgs), dim3(256), 0, c.stream, c.feed, a->dL_dmean2D,
+                           a->dL_dconic_opacity, a->dL_dcolors, a->dL_dcov2D, a->sums_f64, r.dL_ddepths, r.depth_sums64);
+        GSR_LAUNCH_CHECK("flush_block_acc_kernel");
     }
     return GSR_OK;
+}
+int launch_render(const BackwardCall& c, const RenderBackwardParams& r) {
+    if (r.num_tiles <= 0) return GSR_OK;                   // (an empty band)
+    return c.choice.depth ? launch_render_as<true>(c, r) : launch_render_as<false>(c, r);
+}
+
+int launch_chain(const BackwardCall& c, const PreprocessBackwardParams& q) {
+    const dim3 grid((unsigned)((q.n + 255) / 256));
+    if (c.choice.inria) hipLaunchKernelGGL(preprocess_backward_kernel<true>, grid, dim3(256), 0, c.stream, q);
+    else hipLaunchKernelGGL(preprocess_backward_kernel<false>, grid, dim3(256), 0, c.stream, q);
+    GSR_LAUNCH_CHECK("preprocess_backward_kernel");
+    return GSR_OK;
+}
+
+int read_profile(BackwardCall& c) {
+    if (!c.choice.profile) return GSR_OK;
+    GSR_HIP_TRY(hipStreamSynchronize(c.stream));
+    GSR_HIP_TRY(hipEventElapsedTime(&c.a->stage_ms[0], c.events.ev[0], c.events.ev[1]));
+    GSR_HIP_TRY(hipEventElapsedTime(&c.a->stage_ms[1], c.events.ev[1], c.events.ev[2]));
+    return GSR_OK;
+}
+
+// The host call sequence of gsr_backward (DESIGN.md lists it)
+int backward_stages(BackwardCall& c) {
+    GSR_TRY(resolve_lists(c));
+    GSR_TRY(clear_outputs(c));
+    if (c.nothing_rendered) return finish_without_instances(c);
+    GSR_TRY(c.begin_profile());
+    const RenderBackwardParams r = render_params(c);
+    GSR_TRY(launch_render(c, r));
+    GSR_TRY(c.mark(1));
+    if (c.choice.chain || c.choice.wide) GSR_TRY(launch_chain(c, chain_params(c, r)));
+    GSR_TRY(c.mark(2));
+    return read_profile(c);
+}
+
+}  // namespace
+}  // namespace gsr
+
+using namespace gsr;
+
+static int backward_impl(gsr_backward_args* a) {
+    if (!a || a->struct_size != sizeof(gsr_backward_args)) return GSR_ERR_INVALID_ARG;
+    a->stage_ms[0] = a->stage_ms[1] = 0.0f;
+    BackwardChoice choice;
+    GSR_TRY(choose_backward(*a, &choice));
+    BackwardCall call(a, choice);
+    return backward_stages(call);
 }
 
 extern "C" int gsr_backward(gsr_backward_args* a) { return entry_point(backward_impl, a); }

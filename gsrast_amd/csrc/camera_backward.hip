@@ -11,6 +11,7 @@
 // input give the same bits on any device.
 #include <hip/hip_runtime.h>
 
+#include "backward_policy.hpp"
 #include "gsr_common.hpp"
 
 namespace gsr {
@@ -323,32 +324,24 @@ static int camera_backward_impl(gsr_camera_backward_args* a) {
     p.radii = a->radii;
     p.shs = sh ? a->shs : nullptr;
     p.clamped = a->clamped;
-    p.sh_deg = a->sh_dims < 0 ? 0 : (a->sh_dims > 3 ? 3 : a->sh_dims);
+    // the focal lengths, w epsilon and SH degree of gsr_backward's chain
+    const ProfileLens lens = profile_lens(inria, a->width, a->height, a->tan_fovx, a->tan_fovy, a->sh_dims);
+    p.sh_deg = lens.sh_deg;
     p.dL_dmean2D = reinterpret_cast<const float2*>(a->dL_dmean2D);
     p.dL_dcov2D = reinterpret_cast<const float4*>(a->dL_dcov2D);
     p.dL_ddepths = a->dL_ddepths;
     p.dL_dcolors = a->dL_dcolors;
     p.tan_fovx = a->tan_fovx; p.tan_fovy = a->tan_fovy;
-    // the focal lengths and w epsilon of gsr_backward's chain (backward.hip)
-    p.focal_x = inria ? (float)a->width / (2.0f * a->tan_fovx) : (float)a->height / (2.0f * a->tan_fovy);
-    p.focal_y = (float)a->height / (2.0f * a->tan_fovy);
-    p.w_eps = inria ? 0.0000001f : 0.001f;
+    p.focal_x = lens.focal_x; p.focal_y = lens.focal_y; p.w_eps = lens.w_eps;
     p.width = a->width; p.height = a->height;
     p.inria = inria ? 1 : 0;
     p.depth_inverse = (a->flags & GSR_FLAG_DEPTH_INVERSE) ? 1 : 0;
     p.partial = static_cast<double*>(a->scratch);
 
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct Events {
-        hipEvent_t* e;
-        ~Events() {
-            for (int k = 0; k < 2; ++k)
-                if (e[k]) (void)hipEventDestroy(e[k]);
-        }
-    } events{ev};
+    CallEvents<2> events;
+    hipEvent_t* const ev = events.ev;
     if (profile) {
-        GSR_HIP_TRY(hipEventCreate(&ev[0]));
-        GSR_HIP_TRY(hipEventCreate(&ev[1]));
+        GSR_TRY(events.create());
         GSR_HIP_TRY(hipEventRecord(ev[0], stream));
     }
     const int blocks = camera_blocks(n);

@@ -11,6 +11,32 @@
 
 namespace gsr {
 
+constexpr int kTile = 16;          // BLOCK_W / BLOCK_H, reference GSCuda.cu:20-21
+
+struct FrameDims {
+    int width, height;
+    int grid_x, grid_y;            // tile grid of the whole image
+    int row_begin, row_end;        // tile rows this call bins / sorts / blends
+};
+
+// The tile grid of a width x height image and the band of tile rows a call works on (tile_row_begin / tile_row_end of
+// gsr_forward_args and gsr_backward_args: both zero = every row; begin == end = an empty band). A band that does not lie
+// inside the grid is refused.
+inline int tile_band(int width, int height, int row_begin_arg, int row_end_arg, FrameDims* d) {
+    d->width = width;
+    d->height = height;
+    d->grid_x = (width + kTile - 1) / kTile;
+    d->grid_y = (height + kTile - 1) / kTile;
+    d->row_begin = 0;
+    d->row_end = d->grid_y;
+    if (row_begin_arg != 0 || row_end_arg != 0) {
+        if (row_begin_arg < 0 || row_end_arg > d->grid_y || row_begin_arg > row_end_arg) return GSR_ERR_INVALID_ARG;
+        d->row_begin = row_begin_arg;
+        d->row_end = row_end_arg;
+    }
+    return GSR_OK;
+}
+
 // Instances per visible Gaussian (R / V) at which the plans and the blend's feed change hands (each with the frames it was
 // measured on; `profiles/r05_trained_like.txt` has all of them on a scene of flat, opaque splats on surfaces):
 constexpr uint64_t kBlockPlanMinInstances = 6;    // block plan from here on, sort plan below

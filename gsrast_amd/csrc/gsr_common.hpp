@@ -5,12 +5,11 @@
 #include <stdint.h>
 
 #include "../../include/gsrast_amd.h"
-#include "frame_policy.hpp"      // (DeviceShape, the launch heuristics' switch points)
+#include "frame_policy.hpp"      // (kTile, FrameDims, DeviceShape, the launch heuristics' switch points)
 #include "shared_words.hpp"      // (the pinned host block, sort_info)
 
 namespace gsr {
 
-constexpr int kTile = 16;          // BLOCK_W / BLOCK_H, reference GSCuda.cu:20-21
 constexpr int kWave = 64;          // gfx950 wavefront
 
 // Records the failing HIP call for gsr_last_hip_error(), and forgets it: entry_point() starts every entry point with that
@@ -52,6 +51,20 @@ inline bool exceeds_grid(long long blocks) { return blocks > 0x7FFFFFFFll; }
         }                                                   \
     } while (0)
 
+// The N events of one profiled call: created on the device that is current for THIS call, destroyed when it returns.
+template <int N>
+struct CallEvents {
+    hipEvent_t ev[N] = {};
+    int create() {
+        for (auto& e : ev) GSR_HIP_TRY(hipEventCreate(&e));
+        return GSR_OK;
+    }
+    ~CallEvents() {
+        for (auto& e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
 // What the scan wants to know of a preprocess wave's 64 Gaussians, left as ONE 16-byte record per wave so that its first
 // launch reads 0.25 bytes per Gaussian instead of re-reading tilesTouched (50 M Gaussians: 80 -> 13 us): {sum of tilesTouched,
 // Gaussians with a tile, the instances of those of big_from tiles and more, those with a tile whose depth key has another
@@ -74,12 +87,6 @@ __device__ __forceinline__ void store_wave_sums(uint4* __restrict__ wave_sums, i
     }
     if ((threadIdx.x & 63) == 0) wave_sums[idx >> 6] = make_uint4(s, z, b, o);
 }
-
-struct FrameDims {
-    int width, height;
-    int grid_x, grid_y;            // tile grid of the whole image
-    int row_begin, row_end;        // tile rows this call bins / sorts / blends
-};
 
 // Where the depth channel of a blend comes from and goes to (gsr_forward_args.out_depth; out == null: no depth channel).
 struct DepthTarget {

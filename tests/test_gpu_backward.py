@@ -450,6 +450,30 @@ def test_backward_of_a_frame_without_instances_is_all_zero():
         assert float(v.abs().sum()) == 0.0, k
 
 
+def test_float_sums_of_a_frame_without_instances_are_cleared():
+    """R == 0 without sums_f64 (wide_sums=False) and with a depth gradient: all ten arrays, dL_ddepths among them, filled
+    with NaN beforehand, come back as exact zeros (64 x 48 pixels, eight Gaussians behind the camera)."""
+    import torch
+    from gsrast_amd import camera
+    from gsrast_amd.backward_plan import ROW_FLOATS
+    from gsrast_amd.rasterizer import SplatRasterizer
+    from helpers import single_gaussian_scene
+    W, H = 64, 48
+    r = SplatRasterizer(W, H)
+    r.configure_from_scene(single_gaussian_scene(n=8, scale=0.3))
+    r.draw(camera.default_camera(W, H, near=0.05, far=50.0, position=(0.0, 0.0, 5.0)))
+    assert r.last_num_rendered == 0 and r.last_receipt.magic != 0
+    dl, gd = torch.ones((3, H, W), device="cuda"), torch.ones((H, W), device="cuda")
+    first = r.backward(dl, dL_ddepth=gd, wide_sums=False)
+    assert set(first) == set(ROW_FLOATS) | {"dL_ddepths"}
+    for v in first.values():
+        v.fill_(float("nan"))
+    out = r.backward(dl, dL_ddepth=gd, wide_sums=False)
+    for k, v in out.items():
+        assert v.data_ptr() == first[k].data_ptr(), k               # (this object's buffers: the ones filled above)
+        assert torch.equal(v.view(torch.int32), torch.zeros_like(v).view(torch.int32)), k
+
+
 # ---- SplatRasterizer.backward()'s host side: who owns which buffer, and for how long (128 x 96, forty Gaussians) ---------
 _W, _H = 128, 96
 _CAM_KEYS = ("dL_dview_matrix", "dL_dproj_matrix", "dL_dcam_pos")
