@@ -84,6 +84,7 @@ struct EnvKnobs {
     int depth_records;         // GSR_DEPTH_RECORDS=0|1: the depth order's triples as three arrays / as 12-byte records between its passes; -1: records without the compaction
     bool deep_by_history;      // GSR_DEEP_BY_HISTORY=1: above that, the history's slowest tiles get four waves (tile_order_kernel's
                                // count; measured neutral, `profiles/r06_deep_tiles.txt`: off by default)
+    int sort_single_ticket = -1;   // GSR_SORT_SINGLE_TICKET=0|1: the onesweep's tiles in XCD runs / by one ticket (radix_sort.hip take_tile); -1: by CU count
 };
 
 // What the rules read of the call's tile history (gsr_tile_history, api_internal.hpp: the same fields, copied). A call without a

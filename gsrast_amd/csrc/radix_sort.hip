@@ -23,6 +23,7 @@
 
 namespace gsr {
 int sweep_clear(const SweepScratch& sc, uint32_t n, uint32_t nbins, hipStream_t stream);
+const EnvKnobs& env_knobs();                            // (thread_state.hip)
 namespace {
 
 constexpr int kThreads = 512;
@@ -493,7 +494,9 @@ int launch_pass(const KeyT* keys_in, const uint32_t* vals_in, KeyT* keys_out, ui
         DeviceShape shape;
         const int rc = current_device_shape(&shape);
         if (rc != GSR_OK) return rc;
-        spec.single_ticket = xcd_runs_fit(shape.cus) ? 0u : 1u;
+        // (GSR_SORT_SINGLE_TICKET=0|1 decides instead of the CU count: the tests' way to run the single ticket on a whole chip)
+        const int knob = env_knobs().sort_single_ticket;
+        spec.single_ticket = (knob == 0 || knob == 1) ? (uint32_t)knob : (xcd_runs_fit(shape.cus) ? 0u : 1u);
     }
     const int bits = radix_bits_for(spec.nbins);
     if (bits > 8) return GSR_ERR_INVALID_ARG;

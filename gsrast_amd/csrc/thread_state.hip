@@ -117,6 +117,8 @@ EnvKnobs read_env_knobs() {
     e.depth_records = dr && (dr[0] == '0' || dr[0] == '1') ? dr[0] - '0' : -1;
     const char* dh = getenv("GSR_DEEP_BY_HISTORY");
     e.deep_by_history = dh && dh[0] == '1';
+    const char* st = getenv("GSR_SORT_SINGLE_TICKET");
+    e.sort_single_ticket = st && (st[0] == '0' || st[0] == '1') ? st[0] - '0' : -1;
     return e;
 }
 // (read when the first call needs them; gsr_reread_environment — the tests' and A/B scripts' way of changing a knob inside one

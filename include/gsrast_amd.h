@@ -375,7 +375,10 @@ uint32_t gsr_higher_msb(uint32_t n);
 size_t gsr_scan_temp_bytes(size_t n);
 int gsr_inclusive_scan_u32(const uint32_t* in, uint32_t* out, size_t n, char* temp, void* stream);
 /* Stable LSD radix sort of (u64 key, u32 value) pairs on key bits [begin_bit, end_bit)
- * (replaces cub::DeviceRadixSort::SortPairs, GSCuda.cu:794-797). Inputs are preserved. */
+ * (replaces cub::DeviceRadixSort::SortPairs, GSCuda.cu:794-797). Inputs are preserved. Bits outside the window take no
+ * part: pairs whose windows are equal keep their input order. The window is clamped, in this order: end_bit > 64 becomes 64,
+ * begin_bit < 0 becomes 0, and end_bit <= begin_bit becomes begin_bit + 1 (the one bit at begin_bit); begin_bit must be
+ * below 64. temp needs gsr_sort_temp_bytes(n) bytes and need not be cleared; n == 0 does nothing. */
 size_t gsr_sort_temp_bytes(size_t n);
 int gsr_sort_pairs_u64_u32(const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* values_in,
                            uint32_t* values_out, size_t n, int begin_bit, int end_bit, char* temp, void* stream);
