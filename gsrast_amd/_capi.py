@@ -1,4 +1,4 @@
-"""ctypes binding of include/gsrast_amd.h and include/gsrast_amd_init.h (the C ABI of libgsrast_amd.so).
+"""ctypes binding of include/gsrast_amd.h, include/gsrast_amd_init.h and include/gsrast_amd_opacity.h (the C ABI of libgsrast_amd.so).
 
 There is no fallback: if the HIP library has not been built, importing the product path
 raises. Field order and types below mirror the header exactly.
@@ -258,6 +258,11 @@ INIT_SIGNATURES = {
     "gsr_knn_mean_dist2": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# include/gsrast_amd_opacity.h (the accumulated opacity's gradient), in the same shape, with its own symbol test.
+OPACITY_SIGNATURES = {
+    "gsr_backward_alpha": (C.c_int, [C.POINTER(BackwardArgs), C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -282,7 +287,7 @@ def lib() -> C.CDLL:
         # library resolves that soname, otherwise two HIP runtimes end up in the process and
         # torch's device pointers mean nothing to ours ("no HIP device"): this module imports torch first.
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(INIT_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(INIT_SIGNATURES.items()) + list(OPACITY_SIGNATURES.items()):
             fn = getattr(L, name, None)
             if fn is None and _TAG:
                 continue                       # (a tagged A/B build of an older tree may lack the newest entry points)

@@ -156,11 +156,14 @@ class _Rasterize(torch.autograd.Function):
         ctx.view_shapes = (view.shape, proj.shape, cam_pos.shape)
         ctx.has_colors = colors_precomp is not None
         ctx.save_for_backward(means3D, scales, rotations, opacities, shs)      # (a write to one of them before backward() is reported)
-        ctx.mark_non_differentiable(opacity_map)
+        if not opts["opacity_grad"]:
+            ctx.mark_non_differentiable(opacity_map)
+        else:
+            ctx.set_materialize_grads(False)                  # (a map the loss does not use arrives as None, not as zeros to run through)
         return into["out_color"], into.get("out_depth"), opacity_map
 
     @staticmethod
-    def backward(ctx, g_color, g_depth, _g_opacity_map):
+    def backward(ctx, g_color, g_depth, g_opacity_map):
         rast, opts = ctx.rast, ctx.opts
         if rast._state_epoch != ctx.epoch:
             raise RuntimeError(STALE_MESSAGE)
@@ -168,7 +171,8 @@ class _Rasterize(torch.autograd.Function):
         need = dict(zip(("means3D", "scales", "rotations", "opacities", "shs", "view", "proj", "cam_pos", "colors_precomp"),
                         ctx.needs_input_grad[2:]))
         n, dev = rast.num_gaussians, rast.device
-        if g_color is None and g_depth is None:
+        g_alpha = g_opacity_map if opts["opacity_grad"] else None
+        if g_color is None and g_depth is None and g_alpha is None:
             return (None,) * 11
         if g_color is None:
             g_color = torch.zeros((3, rast.height, rast.width), dtype=F32, device=dev)
@@ -199,7 +203,7 @@ class _Rasterize(torch.autograd.Function):
             into["dL_dmean2D"] = new(n, 2)
         res = rast.backward(g_color, semantics=opts["semantics"], sh_degree=opts["sh_degree"], scale_modifier=opts["scale_modifier"],
                             receipt=ctx.receipt, wide_sums=True, dL_ddepth=g_depth if opts["depth"] else None,
-                            depth=opts["depth"] or None, camera=camera, into=into, sync=False)
+                            depth=opts["depth"] or None, camera=camera, into=into, sync=False, dL_dalpha=g_alpha)
         if frame_slot is not None:
             frame_slot.dL_dmean2D = res["dL_dmean2D"]
         g = lambda k, on=True: res[k] if (on and k in res) else None
@@ -212,7 +216,8 @@ class _Rasterize(torch.autograd.Function):
 
 def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, tan_fov, *,
               semantics: str = "gscuda", sh_degree: int = 3, scale_modifier: float = 1.0, depth: "bool | str" = False,
-              colors_precomp: "torch.Tensor | None" = None, radii_slot: "RadiiSlot | None" = None, **draw_options):
+              colors_precomp: "torch.Tensor | None" = None, radii_slot: "RadiiSlot | None" = None, opacity_grad: bool = False,
+              **draw_options):
     """One differentiable frame: SplatRasterizer.draw forward, .backward / .camera_backward backward.
 
     Tensors in the library's layouts, float32 on rast.device: means3D / scales / rotations [N,4], opacities [N], shs [N,48]
@@ -221,9 +226,11 @@ def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs,
     (bind_scene: nothing is copied) and the camera is copied on the device. draw_options: plan, overlap_emit, tile_history,
     deep_tiles, passed to draw(); the sorted lists are always written.
 
-    Returns (color [3,H,W], depth [H,W] or None, opacity_map [H,W]), each a new tensor. opacity_map (1 - finalT) is NOT
-    differentiable: a gradient with respect to the accumulated opacity would be a further sum in render_backward_kernel,
-    which does not exist yet (out of scope here); dividing the depth channel by it treats it as a constant.
+    Returns (color [3,H,W], depth [H,W] or None, opacity_map [H,W]), each a new tensor. opacity_map is the accumulated
+    opacity 1 - finalT. opacity_grad=True makes it differentiable: its incoming gradient goes to gsr_backward_alpha as
+    dL_dout_alpha (a seed of the render backward: no further sum, output or scratch), so depth / opacity_map.clamp_min(eps),
+    a mask loss or an opacity regulariser reach every parameter and the camera. With the default, False, the map is marked
+    non-differentiable: it carries no requires_grad, and dividing the depth channel by it treats it as a constant.
 
     The backward asks gsr_backward (double sums: the gradients do not depend on the order of the tiles' atomics) for exactly
     the per-Gaussian outputs whose input requires a gradient, written into new tensors; when view, proj or cam_pos requires
@@ -233,7 +240,8 @@ def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs,
     assert set(draw_options) <= set(_DRAW_OPTIONS), sorted(draw_options)
     assert depth in (False, True, "inverse"), depth
     opts = {"tan_fov": (float(tan_fov[0]), float(tan_fov[1])), "semantics": semantics, "sh_degree": int(sh_degree),
-            "scale_modifier": float(scale_modifier), "depth": depth, "radii_slot": radii_slot, "draw": dict(draw_options)}
+            "scale_modifier": float(scale_modifier), "depth": depth, "radii_slot": radii_slot, "draw": dict(draw_options),
+            "opacity_grad": bool(opacity_grad)}
     return _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp)
 
 
@@ -349,14 +357,16 @@ def _camera_tensors(camera, dev):
 
 
 def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: str = "gscuda", sh_degree: int = 3,
-           scale_modifier: float = 1.0, depth: "bool | str" = False, radii_slot: "RadiiSlot | None" = None, **draw_options):
+           scale_modifier: float = 1.0, depth: "bool | str" = False, radii_slot: "RadiiSlot | None" = None,
+           opacity_grad: bool = False, **draw_options):
     """`activate` then `rasterize`: (color [3,H,W], depth [H,W] or None, opacity_map [H,W]) of `params` seen from `camera`
     — a Camera (its matrices are uploaded once per device and kept with it; write to a Camera's arrays and it must be a new
     object) or a tuple (view, proj, cam_pos, tan_fovx, tan_fovy) whose first three are device tensors, which may require
     gradients. `loss.backward()` fills params.*.grad (and the camera tensors' .grad). Gaussians the frame culled get zero
     gradients without their rows being read. radii_slot: a RadiiSlot of the caller's, used instead of the call's own; after
     the call its `.radii` is the frame's radii (i32[N], a new tensor per frame) — what optim.GaussianAdam.step() takes. A
-    FrameSlot also receives, in the backward, the frame's dL_dmean2D [N,2] — what densify.DensityStats.update() takes."""
+    FrameSlot also receives, in the backward, the frame's dL_dmean2D [N,2] — what densify.DensityStats.update() takes.
+    opacity_grad=True: the opacity map is differentiable too (see `rasterize`)."""
     if semantics == "inria" and sh_degree >= 1:
         assert params.sh_layout == "coefficient_major", 'semantics="inria" reads shs as [N][16][3]: sh_layout="coefficient_major"'
     slot = radii_slot if radii_slot is not None else RadiiSlot()
@@ -364,4 +374,4 @@ def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: 
     view, proj, cam_pos, tan_fovx, tan_fovy = _camera_tensors(camera, rast.device)
     return rasterize(rast, means3D, scales, rotations, opacities, params.shs, view, proj, cam_pos, (tan_fovx, tan_fovy),
                      semantics=semantics, sh_degree=sh_degree, scale_modifier=scale_modifier, depth=depth, radii_slot=slot,
-                     **draw_options)
+                     opacity_grad=opacity_grad, **draw_options)

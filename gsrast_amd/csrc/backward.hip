@@ -8,6 +8,8 @@
 //   blend loop          apps/gsrast/gscuda/GSCuda.cu:623-676
 //   computeCov2D, conic GSCuda.cu:197-231, :329-335        colour  GSCuda.cu:362-366
 // Parity unpinned; oracle/backward_np.py (float64, checked against finite differences) is the checker.
+// L may carry two more terms: sum(dL_dout_depth * out_depth) (a thirteenth sum, DEPTH below) and sum(dL_dout_alpha * (1 - final T))
+// (gsr_backward_alpha; no sum of its own: 1 - T_f is linear in the T_f that seeds every pixel's walk, see S[k] in render_backward_kernel).
 //
 // render_backward_kernel: one wavefront per 16 x 16 tile, four pixels per lane (the layout of
 // blend_wave_kernel). Every pixel walks its tile's list BACK TO FRONT from its own last contributor
@@ -22,6 +24,7 @@
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 #include "backward_policy.hpp"
+#include "../../include/gsrast_amd_opacity.h"
 #include "blend_core.hpp"
 #include "blockbin.hpp"
 
@@ -47,13 +50,14 @@ struct RenderBackwardParams {
     FrameDims dims;
     int num_tiles;
     const uint32_t* tile_order;  // the forward blend's workgroup order (slow tiles first), or null: patch order
-    // depth channel (read by render_backward_kernel<true> only; gsr_backward_args.dL_dout_depth)
+    // depth channel (read by the DEPTH instances of render_backward_kernel only; gsr_backward_args.dL_dout_depth)
     const float* dL_dout_depth;  // f32[W H]
     const float4* means3D;       // d_i is recomputed from these (blend_core.hpp: depth_value)
     const float* view;           // the view matrix (row 2 is read)
     uint32_t depth_inverse;      // GSR_FLAG_DEPTH_INVERSE
     float* dL_ddepths;           // f32[N]: float atomics, unless depth_sums64 keeps the sums
     double* depth_sums64;        // f64[N] or null (with sums64)
+    const float* dL_dout_alpha;  // f32[W H]: the accumulated opacity's term, read by the ALPHA instances only (gsr_backward_alpha)
 };
 
 // Sums of TWELVE per-lane values over the 64 lanes in about half the steps of twelve separate reductions: v_permlane32_swap
@@ -195,7 +199,11 @@ template <> struct DepthSlots<true> {
 
 // DEPTH: the depth channel too (gsr_backward_args.dL_dout_depth): d_i is staged beside the colour, its g_d joins the colour dot
 // product cg (and through it the sum S of what lies behind), and a thirteenth sum, dL/dd_i, leaves from lane 2.
-template <bool DEPTH>
+// ALPHA: the accumulated opacity's term (gsr_backward_alpha's dL_dout_alpha): g_a is loaded beside g0..g2 and lowers the seed of S; it
+// is dead before the record loop. An instance of its own, not a null check: with the check (one scalar branch per pixel row) the
+// call without the term measured 2.7 us over the kernel's 0.201 ms on the bench frame, outside its own quartiles; the instances
+// without ALPHA are the kernel as it was.
+template <bool DEPTH, bool ALPHA>
 __global__ __launch_bounds__(64) void render_backward_kernel(const RenderBackwardParams p) {
     float* const s_dep = DepthSlots<DEPTH>::get();
     __shared__ uint32_t s_id[kWave];
@@ -227,14 +235,19 @@ __global__ __launch_bounds__(64) void render_backward_kernel(const RenderBackwar
         fy[k] = (float)py;
         const bool inside = px < p.dims.width && py < p.dims.height;
         last[k] = 0; T[k] = 1.0f; g0[k] = g1[k] = g2[k] = 0.0f;
+        [[maybe_unused]] float ga = 0.0f;            // dL/d out_alpha (ALPHA)
         if (inside) {
             const size_t pid = (size_t)py * (size_t)p.dims.width + (size_t)px;
             last[k] = p.n_contrib[pid];
             T[k] = p.final_t[pid];
             g0[k] = p.dL_dout[pid]; g1[k] = p.dL_dout[pid + plane]; g2[k] = p.dL_dout[pid + 2 * plane];
             if constexpr (DEPTH) gd[k] = p.dL_dout_depth[pid];
+            if constexpr (ALPHA) ga = p.dL_dout_alpha[pid];
         }
-        S[k] = T[k] * (bg0 * g0[k] + bg1 * g1[k] + bg2 * g2[k]);     // what lies behind, dotted with dL/dC
+        // What lies behind, dotted with dL/dC. The accumulated opacity 1 - T_f is linear in the same T_f: its whole term is
+        // this seed, S = T_f ((bg . g) - g_a)
+        if constexpr (ALPHA) S[k] = T[k] * ((bg0 * g0[k] + bg1 * g1[k] + bg2 * g2[k]) - ga);
+        else S[k] = T[k] * (bg0 * g0[k] + bg1 * g1[k] + bg2 * g2[k]);
         hi = max(hi, last[k]);
     }
 #pragma unroll
@@ -895,11 +908,13 @@ struct BackwardCall {
     gsr_backward_args* const a;
     const hipStream_t stream;
     const BackwardChoice choice;        // (backward_policy.hpp: the call's modes and its band of tile rows)
+    const float* const dL_dout_alpha;   // gsr_backward_alpha's second argument, or null
     BlockFeed feed = {};
     bool from_blocks = false, lists_written = true, nothing_rendered = false;
     CallEvents<3> events;               // GSR_FLAG_PROFILE: before the render backward, between it and the chain, behind the chain
 
-    BackwardCall(gsr_backward_args* a_, const BackwardChoice& choice_) : a(a_), stream((hipStream_t)a_->stream), choice(choice_) {}
+    BackwardCall(gsr_backward_args* a_, const BackwardChoice& choice_, const float* alpha_)
+        : a(a_), stream((hipStream_t)a_->stream), choice(choice_), dL_dout_alpha(alpha_) {}
     int begin_profile() { if (choice.profile) GSR_TRY(events.create()); return mark(0); }
     int mark(int k) { if (choice.profile) GSR_HIP_TRY(hipEventRecord(events.ev[k], stream)); return GSR_OK; }
 };
@@ -975,6 +990,7 @@ RenderBackwardParams render_params(const BackwardCall& c) {
     r.depth_inverse = c.choice.depth_inverse ? 1u : 0u;
     r.dL_ddepths = a->dL_ddepths;
     r.depth_sums64 = c.choice.wide ? a->depth_sums_f64 : nullptr;
+    r.dL_dout_alpha = c.dL_dout_alpha;
     return r;
 }
 
@@ -1035,7 +1051,8 @@ int launch_render_as(const BackwardCall& c, const RenderBackwardParams& r) {
         GSR_LAUNCH_CHECK("zero_block_acc_kernel");
     }
     const dim3 grid((unsigned)patch_workgroups(d.grid_x, d.row_end - d.row_begin));
-    hipLaunchKernelGGL(render_backward_kernel<DEPTH>, grid, dim3(kWave), 0, c.stream, r);
+    if (c.choice.alpha) hipLaunchKernelGGL((render_backward_kernel<DEPTH, true>), grid, dim3(kWave), 0, c.stream, r);
+    else hipLaunchKernelGGL((render_backward_kernel<DEPTH, false>), grid, dim3(kWave), 0, c.stream, r);
     GSR_LAUNCH_CHECK("render_backward_kernel");
     if (per_entry) {
         hipLaunchKernelGGL(flush_block_acc_kernel<DEPTH>, dim3(acc_wgs), dim3(256), 0, c.stream, c.feed, a->dL_dmean2D,
@@ -1084,13 +1101,14 @@ int backward_stages(BackwardCall& c) {
 
 using namespace gsr;
 
-static int backward_impl(gsr_backward_args* a) {
+static int backward_impl(gsr_backward_args* a, const float* dL_dout_alpha) {
     if (!a || a->struct_size != sizeof(gsr_backward_args)) return GSR_ERR_INVALID_ARG;
     a->stage_ms[0] = a->stage_ms[1] = 0.0f;
     BackwardChoice choice;
-    GSR_TRY(choose_backward(*a, &choice));
-    BackwardCall call(a, choice);
+    GSR_TRY(choose_backward(*a, &choice, dL_dout_alpha));
+    BackwardCall call(a, choice, dL_dout_alpha);
     return backward_stages(call);
 }
 
-extern "C" int gsr_backward(gsr_backward_args* a) { return entry_point(backward_impl, a); }
+extern "C" int gsr_backward(gsr_backward_args* a) { return entry_point(backward_impl, a, (const float*)nullptr); }
+extern "C" int gsr_backward_alpha(gsr_backward_args* a, const float* dL_dout_alpha) { return entry_point(backward_impl, a, dL_dout_alpha); }

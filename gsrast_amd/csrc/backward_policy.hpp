@@ -19,11 +19,13 @@ struct BackwardChoice {
     bool have_receipt;     // (any other magic than the library's: refused by lists_of_receipt)
     bool profile;          // GSR_FLAG_PROFILE
     bool depth_inverse;    // GSR_FLAG_DEPTH_INVERSE
+    bool alpha;            // dL_dout_alpha of gsr_backward_alpha: the accumulated opacity's term (a seed of the render backward: nothing else comes with it)
     FrameDims d;
 };
 
 // The rules of include/gsrast_amd.h (gsr_backward_args), in the order a call that breaks several is answered for.
-inline int choose_backward(const gsr_backward_args& a, BackwardChoice* out) {
+// dL_dout_alpha: the second argument of gsr_backward_alpha (include/gsrast_amd_opacity.h), null for gsr_backward: it adds no rule.
+inline int choose_backward(const gsr_backward_args& a, BackwardChoice* out, const float* dL_dout_alpha = nullptr) {
     BackwardChoice c{};
     if (a.num_gaussians <= 0 || a.width <= 0 || a.height <= 0 || !a.background || !a.means2D || !a.conic_opacity || !a.colors ||
         !a.ranges || !a.n_contrib || !a.final_t || !a.dL_dout_color)
@@ -43,6 +45,7 @@ inline int choose_backward(const gsr_backward_args& a, BackwardChoice* out) {
     // the depth channel: d_i is recomputed from means3D and the view; its sums go to depth_sums_f64 beside sums_f64, else to dL_ddepths
     c.depth = a.dL_dout_depth != nullptr;
     if (c.depth && (!a.means3D || !a.view_matrix || (c.wide ? !a.depth_sums_f64 : !a.dL_ddepths))) return GSR_ERR_INVALID_ARG;
+    c.alpha = dL_dout_alpha != nullptr;
     c.profile = (a.flags & GSR_FLAG_PROFILE) != 0;
     c.depth_inverse = (a.flags & GSR_FLAG_DEPTH_INVERSE) != 0;
     if (tile_band(a.width, a.height, a.tile_row_begin, a.tile_row_end, &c.d) != GSR_OK) return GSR_ERR_INVALID_ARG;

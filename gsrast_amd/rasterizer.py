@@ -350,7 +350,8 @@ class SplatRasterizer:
         return out_color
 
     def opacity_map(self) -> torch.Tensor:
-        """(H, W) accumulated opacity of the last draw(), 1 - finalT: divide out_depth by it for expected depth."""
+        """(H, W) accumulated opacity of the last draw(), 1 - finalT: divide out_depth by it for expected depth. A gradient
+        w.r.t. this map goes back through backward(dL_dalpha=...); under autograd, rasterize(opacity_grad=True)."""
         return 1.0 - self.map_image_state()["finalT"]
 
     def tile_history_stats(self) -> dict:
@@ -442,7 +443,7 @@ class SplatRasterizer:
                  sh_degree: int = 3, receipt: "_capi.ForwardReceipt | None | bool" = None, wide_sums: bool = True,
                  outputs: "tuple[str, ...] | None" = None, dL_ddepth: "torch.Tensor | None" = None,
                  depth: "bool | str | None" = None, camera: bool = False, into: "dict | None" = None,
-                 sync: bool = True) -> dict:
+                 sync: bool = True, dL_dalpha: "torch.Tensor | None" = None) -> dict:
         """Gradients of sum(dL_dout * out_color) of the LAST draw() through gsr_backward; `semantics` / `sh_degree`
         must be those of that draw(). receipt: the gsr_forward_receipt of the draw() this is the backward of (default:
         this object's last draw(); any host thread may call); False = none, the reference's contract only (sorted lists
@@ -460,6 +461,10 @@ class SplatRasterizer:
         not, writes) and dL_dmeans3D includes the term through z. depth: the channel's mode,
         True or "inverse" (default: that of the last draw(depth=...), else True) — the backward recomputes d_i, so any
         draw() serves, whether or not it wrote out_depth.
+        dL_dalpha: (H, W) float32 tensor on this device, the gradient w.r.t. the accumulated opacity 1 - finalT (opacity_map();
+        gsr_backward_alpha of include/gsrast_amd_opacity.h). The loss gains sum(dL_dalpha * opacity_map) and every output receives its share
+        (dL_dcolors none: the opacity does not depend on the colours); no further output, no further scratch. Another shape,
+        dtype or device is refused (AssertionError) before anything is launched. For this term alone pass zeros as dL_dout.
         camera: the result also holds the gradients w.r.t. the camera, dL_dview_matrix (16,), dL_dproj_matrix (16,) and
         dL_dcam_pos (3,) in the layouts of Camera.view / .proj / .cam_pos (camera_backward(), right behind gsr_backward on the
         same stream). gsr_backward then also writes what that pass reads — dL_dmean2D, dL_dcov2D, and under inria with SH
@@ -476,6 +481,10 @@ class SplatRasterizer:
         col = self._colors_of(rcpt)
         plan = backward_plan.plan_backward(semantics, with_cov3D, wide_sums, None if outputs is None else tuple(outputs),
                                            None if into is None else tuple(into), dL_ddepth is not None, camera, col is not None)
+        if dL_dalpha is not None:                # (checked before the first copy or launch of this call)
+            assert isinstance(dL_dalpha, torch.Tensor) and dL_dalpha.dtype == torch.float32, "dL_dalpha: a float32 tensor"
+            assert dL_dalpha.device == dev, ("dL_dalpha", dL_dalpha.device, dev)
+            assert tuple(dL_dalpha.shape) == (self.height, self.width), ("dL_dalpha", tuple(dL_dalpha.shape))
         g = dL_dout.to(device=dev, dtype=torch.float32).contiguous()
         assert g.shape == (3, self.height, self.width)
         for k, t in (into or {}).items():
@@ -506,7 +515,11 @@ class SplatRasterizer:
         if tile_rows is not None:
             a.tile_row_begin, a.tile_row_end = int(tile_rows[0]), int(tile_rows[1])
         try:
-            _capi.call("gsr_backward", C.byref(a), device=dev)
+            if dL_dalpha is None:
+                _capi.call("gsr_backward", C.byref(a), device=dev)
+            else:
+                ga = dL_dalpha.contiguous()
+                _capi.call("gsr_backward_alpha", C.byref(a), ga.data_ptr(), device=dev)
         except _capi.GsrError:
             if wide_sums:                        # (a call that failed half way may have left sums behind: the next starts from zeroed ones)
                 self._bw.scratch.pop("sums_f64", None)

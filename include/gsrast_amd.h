@@ -505,7 +505,8 @@ int gsr_backward(gsr_backward_args* args);
 
 /* ---- camera gradients: the backward pass on to the camera (after gsr_backward, on the same stream) ----
  * The derivatives of the same scalar L that gsr_backward differentiates (the colour term sum dL_dout_color * out_color,
- * plus sum dL_dout_depth * out_depth when that call had a depth gradient) w.r.t. the 16 + 16 + 3 floats exactly as passed
+ * plus sum dL_dout_depth * out_depth when that call had a depth gradient, plus sum dL_dout_alpha * (1 - final_t) when it was
+ * gsr_backward_alpha of gsrast_amd_opacity.h: that term is in the per-Gaussian gradients, nothing more is needed here) w.r.t. the 16 + 16 + 3 floats exactly as passed
  * to gsr_forward: view_matrix and proj_matrix column-major (the view's row 2 negated, as the reference's caller builds it),
  * cam_pos. Entry (row r, column c) of a matrix is element 4 c + r. Only visible Gaussians (radii[i] > 0) contribute, and the
  * camera reaches L only through each one's
