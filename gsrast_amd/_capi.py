@@ -1,4 +1,5 @@
-"""ctypes binding of include/gsrast_amd.h, include/gsrast_amd_init.h and include/gsrast_amd_opacity.h (the C ABI of libgsrast_amd.so).
+"""ctypes binding of include/gsrast_amd.h, include/gsrast_amd_init.h, include/gsrast_amd_opacity.h and include/gsrast_amd_mcmc.h
+(the C ABI of libgsrast_amd.so).
 
 There is no fallback: if the HIP library has not been built, importing the product path
 raises. Field order and types below mirror the header exactly.
@@ -263,6 +264,36 @@ OPACITY_SIGNATURES = {
     "gsr_backward_alpha": (C.c_int, [C.POINTER(BackwardArgs), C.c_void_p]),
 }
 
+# include/gsrast_amd_mcmc.h (3DGS-MCMC: noise, plan, relocate), in the same shape, with its own symbol test.
+GSR_MCMC_MAX_ROWS = (1 << 31) - 1
+GSR_MCMC_MAX_RATIO = 51
+
+
+class McmcNoiseArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("scaler", C.c_float), ("n", C.c_int64), ("xyz", C.c_void_p),
+                ("opacity_logit", C.c_void_p), ("log_scale", C.c_void_p), ("rotation", C.c_void_p), ("noise", C.c_void_p),
+                ("stream", C.c_void_p)]
+
+
+class McmcArray(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p)]
+
+
+class McmcRelocateArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_opacity", C.c_float), ("n", C.c_int64), ("m", C.c_int64),
+                ("sampled", C.c_void_p), ("dst", C.c_void_p),
+                ("xyz", McmcArray), ("opacity_logit", McmcArray), ("log_scale", McmcArray), ("rotation", McmcArray), ("shs", McmcArray),
+                ("temp", C.c_void_p), ("stream", C.c_void_p)]
+
+
+MCMC_SIGNATURES = {
+    "gsr_mcmc_noise": (C.c_int, [C.POINTER(McmcNoiseArgs)]),
+    "gsr_mcmc_plan_temp_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_mcmc_plan": (C.c_int, [C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsr_mcmc_relocate_temp_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_mcmc_relocate": (C.c_int, [C.POINTER(McmcRelocateArgs)]),
+}
+
 _lib = None
 
 
@@ -287,7 +318,8 @@ def lib() -> C.CDLL:
         # library resolves that soname, otherwise two HIP runtimes end up in the process and
         # torch's device pointers mean nothing to ours ("no HIP device"): this module imports torch first.
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(INIT_SIGNATURES.items()) + list(OPACITY_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(INIT_SIGNATURES.items()) + list(OPACITY_SIGNATURES.items())
+                                  + list(MCMC_SIGNATURES.items())):
             fn = getattr(L, name, None)
             if fn is None and _TAG:
                 continue                       # (a tagged A/B build of an older tree may lack the newest entry points)

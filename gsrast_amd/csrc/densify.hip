@@ -19,6 +19,7 @@
 // unit's loads come before its first store.
 #include "activation_math.hpp"
 #include "gsr_common.hpp"
+#include "rotation_math.hpp"
 #include "wave_triples.hpp"
 
 namespace gsr {
@@ -137,15 +138,12 @@ struct ApplyParams {
 __device__ __forceinline__ void child_position(float (&p)[3], const float* __restrict__ ls, const float4 rot,
                                                const float* __restrict__ z) {
     const float4 sd = activate_scale(ls[0], ls[1], ls[2]);
-    const float4 q = activate_rotation(rot.x, rot.y, rot.z, rot.w);
-    const float r = q.x, x = q.y, y = q.z, w = q.w;                          // (r, x, y, z): w stands for z
-    const float d0 = sd.x * z[0], d1 = sd.y * z[1], d2 = sd.z * z[2];
-    const float R00 = 1.0f - 2.0f * (y * y + w * w), R01 = 2.0f * (x * y - r * w), R02 = 2.0f * (x * w + r * y);
-    const float R10 = 2.0f * (x * y + r * w), R11 = 1.0f - 2.0f * (x * x + w * w), R12 = 2.0f * (y * w - r * x);
-    const float R20 = 2.0f * (x * w - r * y), R21 = 2.0f * (y * w + r * x), R22 = 1.0f - 2.0f * (x * x + y * y);
-    p[0] = p[0] + ((R00 * d0 + R01 * d1) + R02 * d2);
-    p[1] = p[1] + ((R10 * d0 + R11 * d1) + R12 * d2);
-    p[2] = p[2] + ((R20 * d0 + R21 * d1) + R22 * d2);
+    const Rotation3 R = rotation_matrix(activate_rotation(rot.x, rot.y, rot.z, rot.w));
+    const float d[3] = {sd.x * z[0], sd.y * z[1], sd.z * z[2]};
+    float moved[3];
+    rotate(R, d, moved);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) p[a] = p[a] + moved[a];
 }
 
 __global__ __launch_bounds__(256) void densify_apply_kernel(const ApplyParams q) {

@@ -71,19 +71,81 @@ class DensityStats:
                    self.denom.data_ptr(), self.max_radii.data_ptr(), _capi.stream(self.device), device=self.device)
 
 
-def _refuse(t: torch.Tensor, name: str, shape, dev) -> None:
+def _refuse(t: torch.Tensor, name: str, shape, dev, where: str = "densify_and_prune") -> None:
     if t.dtype != torch.float32:
-        raise ValueError(f"densify_and_prune: {name} is {t.dtype}, not float32")
+        raise ValueError(f"{where}: {name} is {t.dtype}, not float32")
     if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"densify_and_prune: {name} is {tuple(t.shape)}, not {tuple(shape)}")
+        raise ValueError(f"{where}: {name} is {tuple(t.shape)}, not {tuple(shape)}")
     if t.device != dev:
-        raise ValueError(f"densify_and_prune: {name} is on {t.device}, not on {dev}")
+        raise ValueError(f"{where}: {name} is on {t.device}, not on {dev}")
     if not t.is_contiguous() or t.data_ptr() % 16 != 0:
-        raise ValueError(f"densify_and_prune: {name} is not contiguous from a 16-byte boundary")
+        raise ValueError(f"{where}: {name} is not contiguous from a 16-byte boundary")
 
 
 def _group_slots(opt, p):
     return [(g, i) for g in opt.param_groups for i, q in enumerate(g["params"]) if q is p]
+
+
+def held_arrays(params: GaussianParams, opt, where: str):
+    """The five raw arrays of `params` and the moments `opt` holds of them, refused (ValueError, `where` in front) unless the
+    kernels can take them: see densify_and_prune. -> (old {name: parameter}, n, device, held {name: (exp_avg, exp_avg_sq)})"""
+    old = {k: getattr(params, k) for k in RAW}
+    n, dev = int(old["xyz"].shape[0]), old["xyz"].device
+    if not old["xyz"].is_cuda:
+        raise ValueError(f"{where}: the parameters are on {dev}, not on a GPU")
+    held = {}
+    for k in RAW:
+        shape = (n,) if k == "opacity_logit" else (n, ROW_FLOATS[k])
+        _refuse(old[k], k, shape, dev, where)
+        if opt is not None:
+            if not _group_slots(opt, old[k]):
+                raise ValueError(f"{where}: the optimiser does not hold {k}")
+            state = opt.state[old[k]] if old[k] in opt.state else {}
+            have = [m for m in MOMENTS if m in state]
+            if len(have) == 1:
+                raise ValueError(f"{where}: the optimiser's state of {k} has {have[0]} alone")
+            for m in have:
+                _refuse(state[m], f"state {m} of {k}", shape, dev, where)
+            if have:
+                held[k] = (state["exp_avg"], state["exp_avg_sq"])
+    return old, n, dev, held
+
+
+def gather_rows(old, held, n: int, counts, src_of: torch.Tensor, noise, log_shrink: float, dev):
+    """gsr_densify_apply into fresh arrays of counts[3] rows. -> (fresh {name: tensor}, fresh_moments {name: (m, v)})"""
+    kept, clones, splits, total = counts
+    fresh = {k: torch.empty((total,) + tuple(old[k].shape[1:]), dtype=torch.float32, device=dev) for k in RAW}
+    fresh_moments = {k: tuple(torch.empty_like(fresh[k]) for _ in MOMENTS) for k in held}
+    if total > 0:
+        a = _capi.DensifyApplyArgs()
+        a.struct_size, a.log_shrink, a.n_src = C.sizeof(_capi.DensifyApplyArgs), log_shrink, n
+        a.counts[:] = [kept, clones, splits, total]
+        a.src_of, a.noise, a.stream = src_of.data_ptr(), noise.data_ptr() if splits else None, _capi.stream(dev)
+        for k in RAW:
+            arr = getattr(a, k)
+            arr.src, arr.dst = old[k].data_ptr(), fresh[k].data_ptr()
+            if k in held:
+                arr.src_exp_avg, arr.src_exp_avg_sq = (t.data_ptr() for t in held[k])
+                arr.dst_exp_avg, arr.dst_exp_avg_sq = (t.data_ptr() for t in fresh_moments[k])
+        _capi.call("gsr_densify_apply", C.byref(a), device=dev)
+    return fresh, fresh_moments
+
+
+def replace_parameters(params: GaussianParams, opt, old, held, fresh, fresh_moments) -> None:
+    """The five nn.Parameters of `params` replaced by new ones over `fresh`; opt's param_groups entries swapped in place and
+    its state re-keyed ("step" kept, the moments — only where there were any — replaced by fresh_moments)."""
+    for k in RAW:
+        p = torch.nn.Parameter(fresh[k], requires_grad=old[k].requires_grad)
+        setattr(params, k, p)
+        if opt is None:
+            continue
+        for group, i in _group_slots(opt, old[k]):
+            group["params"][i] = p
+        if old[k] in opt.state:
+            state = opt.state.pop(old[k])
+            if k in held:
+                state["exp_avg"], state["exp_avg_sq"] = fresh_moments[k]
+            opt.state[p] = state
 
 
 def densify_and_prune(params: GaussianParams, opt, stats: DensityStats, *, max_grad: float = 0.0002, min_opacity: float = 0.005,
@@ -104,25 +166,7 @@ def densify_and_prune(params: GaussianParams, opt, stats: DensityStats, *, max_g
     Raises ValueError before anything is launched or replaced: a parameter of `params` that `opt` does not hold; parameters
     or moments that are not float32, of the wrong shape, on another device, not contiguous from a 16-byte boundary; one
     moment without the other; `stats` of another length or device."""
-    old = {k: getattr(params, k) for k in RAW}
-    n, dev = int(old["xyz"].shape[0]), old["xyz"].device
-    if not old["xyz"].is_cuda:
-        raise ValueError(f"densify_and_prune: the parameters are on {dev}, not on a GPU")
-    held = {}
-    for k in RAW:
-        shape = (n,) if k == "opacity_logit" else (n, ROW_FLOATS[k])
-        _refuse(old[k], k, shape, dev)
-        if opt is not None:
-            if not _group_slots(opt, old[k]):
-                raise ValueError(f"densify_and_prune: the optimiser does not hold {k}")
-            state = opt.state[old[k]] if old[k] in opt.state else {}
-            have = [m for m in MOMENTS if m in state]
-            if len(have) == 1:
-                raise ValueError(f"densify_and_prune: the optimiser's state of {k} has {have[0]} alone")
-            for m in have:
-                _refuse(state[m], f"state {m} of {k}", shape, dev)
-            if have:
-                held[k] = (state["exp_avg"], state["exp_avg_sq"])
+    old, n, dev, held = held_arrays(params, opt, "densify_and_prune")
     if not isinstance(stats, DensityStats) or stats.num_gaussians != n or stats.device != dev:
         raise ValueError(f"densify_and_prune: the statistics are not those of {n} Gaussians on {dev}")
     if not (0.0 < min_opacity < 1.0 and extent > 0.0 and percent_dense > 0.0):
@@ -142,32 +186,8 @@ def densify_and_prune(params: GaussianParams, opt, stats: DensityStats, *, max_g
     kept, clones, splits, total = (int(c) for c in counts.tolist())                    # (the one synchronisation)
     noise_dev = generator.device if generator is not None else dev
     noise = torch.randn((splits, 2, 3), generator=generator, dtype=torch.float32, device=noise_dev).to(dev).contiguous()
-    fresh = {k: torch.empty((total,) + tuple(old[k].shape[1:]), dtype=torch.float32, device=dev) for k in RAW}
-    fresh_moments = {k: tuple(torch.empty_like(fresh[k]) for _ in MOMENTS) for k in held}
-    if total > 0:
-        a = _capi.DensifyApplyArgs()
-        a.struct_size, a.log_shrink, a.n_src = C.sizeof(_capi.DensifyApplyArgs), scalars[4], n
-        a.counts[:] = [kept, clones, splits, total]
-        a.src_of, a.noise, a.stream = src_of.data_ptr(), noise.data_ptr() if splits else None, stream
-        for k in RAW:
-            arr = getattr(a, k)
-            arr.src, arr.dst = old[k].data_ptr(), fresh[k].data_ptr()
-            if k in held:
-                arr.src_exp_avg, arr.src_exp_avg_sq = (t.data_ptr() for t in held[k])
-                arr.dst_exp_avg, arr.dst_exp_avg_sq = (t.data_ptr() for t in fresh_moments[k])
-        _capi.call("gsr_densify_apply", C.byref(a), device=dev)
-    for k in RAW:
-        p = torch.nn.Parameter(fresh[k], requires_grad=old[k].requires_grad)
-        setattr(params, k, p)
-        if opt is None:
-            continue
-        for group, i in _group_slots(opt, old[k]):
-            group["params"][i] = p
-        if old[k] in opt.state:
-            state = opt.state.pop(old[k])
-            if k in held:
-                state["exp_avg"], state["exp_avg_sq"] = fresh_moments[k]
-            opt.state[p] = state
+    fresh, fresh_moments = gather_rows(old, held, n, (kept, clones, splits, total), src_of, noise, scalars[4], dev)
+    replace_parameters(params, opt, old, held, fresh, fresh_moments)
     stats.reset(total)
     return src_of[:total], (kept, clones, splits, total)
 
