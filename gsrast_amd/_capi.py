@@ -1,5 +1,5 @@
-"""ctypes binding of include/gsrast_amd.h, include/gsrast_amd_init.h, include/gsrast_amd_opacity.h and include/gsrast_amd_mcmc.h
-(the C ABI of libgsrast_amd.so).
+"""ctypes binding of include/gsrast_amd.h, include/gsrast_amd_init.h, include/gsrast_amd_opacity.h, include/gsrast_amd_mcmc.h
+and include/gsrast_amd_contrib.h (the C ABI of libgsrast_amd.so).
 
 There is no fallback: if the HIP library has not been built, importing the product path
 raises. Field order and types below mirror the header exactly.
@@ -294,6 +294,20 @@ MCMC_SIGNATURES = {
     "gsr_mcmc_relocate": (C.c_int, [C.POINTER(McmcRelocateArgs)]),
 }
 
+# include/gsrast_amd_contrib.h (per-Gaussian contribution statistics of a frame), in the same shape, with its own symbol test.
+class ContributionArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32),
+                ("num_gaussians", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("means2D", C.c_void_p), ("conic_opacity", C.c_void_p), ("ranges", C.c_void_p), ("n_contrib", C.c_void_p),
+                ("point_list", C.c_void_p), ("receipt", ForwardReceipt),
+                ("weight_sum", C.c_void_p), ("weight_max", C.c_void_p), ("pixels", C.c_void_p), ("dominant", C.c_void_p),
+                ("stream", C.c_void_p), ("stage_ms", C.c_float)]
+
+
+CONTRIB_SIGNATURES = {
+    "gsr_contribution": (C.c_int, [C.POINTER(ContributionArgs)]),
+}
+
 _lib = None
 
 
@@ -319,7 +333,7 @@ def lib() -> C.CDLL:
         # torch's device pointers mean nothing to ours ("no HIP device"): this module imports torch first.
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(INIT_SIGNATURES.items()) + list(OPACITY_SIGNATURES.items())
-                                  + list(MCMC_SIGNATURES.items())):
+                                  + list(MCMC_SIGNATURES.items()) + list(CONTRIB_SIGNATURES.items())):
             fn = getattr(L, name, None)
             if fn is None and _TAG:
                 continue                       # (a tagged A/B build of an older tree may lack the newest entry points)
