@@ -1,5 +1,5 @@
-"""ctypes binding of include/gsrast_amd.h, include/gsrast_amd_init.h, include/gsrast_amd_opacity.h, include/gsrast_amd_mcmc.h
-and include/gsrast_amd_contrib.h (the C ABI of libgsrast_amd.so).
+"""ctypes binding of include/gsrast_amd.h, include/gsrast_amd_init.h, include/gsrast_amd_opacity.h, include/gsrast_amd_mcmc.h,
+include/gsrast_amd_contrib.h and include/gsrast_amd_antialias.h (the C ABI of libgsrast_amd.so).
 
 There is no fallback: if the HIP library has not been built, importing the product path
 raises. Field order and types below mirror the header exactly.
@@ -308,6 +308,29 @@ CONTRIB_SIGNATURES = {
     "gsr_contribution": (C.c_int, [C.POINTER(ContributionArgs)]),
 }
 
+# include/gsrast_amd_antialias.h (antialiased splatting: the opacity compensation and its gradient), in the same shape, with its own symbol test.
+_ANTIALIAS_COMMON = [("struct_size", C.c_uint32), ("flags", C.c_uint32),
+                     ("num_gaussians", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                     ("tan_fovx", C.c_float), ("tan_fovy", C.c_float), ("scale_modifier", C.c_float),
+                     ("means3D", C.c_void_p), ("scales", C.c_void_p), ("rotations", C.c_void_p), ("opacities", C.c_void_p),
+                     ("view_matrix", C.c_void_p), ("proj_matrix", C.c_void_p)]
+
+
+class AntialiasArgs(C.Structure):
+    _fields_ = _ANTIALIAS_COMMON + [("opacities_out", C.c_void_p), ("compensation", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class AntialiasBackwardArgs(C.Structure):
+    _fields_ = _ANTIALIAS_COMMON + [("dL_dopacities_out", C.c_void_p), ("radii", C.c_void_p),
+                                    ("dL_dopacities", C.c_void_p), ("dL_dmeans3D", C.c_void_p), ("dL_dscales", C.c_void_p),
+                                    ("dL_drotations", C.c_void_p), ("stream", C.c_void_p)]
+
+
+ANTIALIAS_SIGNATURES = {
+    "gsr_antialias_forward": (C.c_int, [C.POINTER(AntialiasArgs)]),
+    "gsr_antialias_backward": (C.c_int, [C.POINTER(AntialiasBackwardArgs)]),
+}
+
 _lib = None
 
 
@@ -333,7 +356,7 @@ def lib() -> C.CDLL:
         # torch's device pointers mean nothing to ours ("no HIP device"): this module imports torch first.
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(INIT_SIGNATURES.items()) + list(OPACITY_SIGNATURES.items())
-                                  + list(MCMC_SIGNATURES.items()) + list(CONTRIB_SIGNATURES.items())):
+                                  + list(MCMC_SIGNATURES.items()) + list(CONTRIB_SIGNATURES.items()) + list(ANTIALIAS_SIGNATURES.items())):
             fn = getattr(L, name, None)
             if fn is None and _TAG:
                 continue                       # (a tagged A/B build of an older tree may lack the newest entry points)

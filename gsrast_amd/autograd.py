@@ -1,6 +1,7 @@
 """torch.autograd over the rasterizer: raw (trainable) parameters -> image, and `loss.backward()` back to them.
 
   activate   raw parameters -> the arrays gsr_forward takes (gsr_activate_params / _backward, csrc/activations.hip)
+  (antialias.compensate   opacities -> opacities * c, between the two with antialiased=True: gsrast_amd/antialias.py)
   rasterize  SplatRasterizer.draw / backward / camera_backward as one differentiable function
   GaussianParams, render   the two joined for a trainer: `render(params, rast, cam)` then `loss.backward()`
 
@@ -17,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from . import antialias as _antialias
 from . import ply as _ply
 from .camera import Camera
 from .rasterizer import SplatRasterizer
@@ -121,7 +123,9 @@ def activate(xyz, opacity_logit, log_scale, rotation, *, radii_slot: "RadiiSlot 
     Differentiable: the backward is one kernel, computes only the gradients of the inputs that require one, and returns
     fresh tensors. radii_slot: filled by `rasterize` with the frame's radii; culled Gaussians then get exact zeros. Pass
     one only when the rasterizer is the sole consumer of the four outputs (as `render` does): a regulariser on `scales`
-    reaches culled Gaussians too."""
+    reaches culled Gaussians too. The opacity compensation of antialiased=True (antialias.compensate) is a second consumer
+    that keeps the assumption: its gradient is exactly zero wherever the rasterizer's is, because dL/do' = 0 for a Gaussian
+    that blended nothing."""
     return _Activate.apply(xyz, opacity_logit, log_scale, rotation, radii_slot)
 
 
@@ -217,7 +221,7 @@ class _Rasterize(torch.autograd.Function):
 def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, tan_fov, *,
               semantics: str = "gscuda", sh_degree: int = 3, scale_modifier: float = 1.0, depth: "bool | str" = False,
               colors_precomp: "torch.Tensor | None" = None, radii_slot: "RadiiSlot | None" = None, opacity_grad: bool = False,
-              **draw_options):
+              antialiased: bool = False, **draw_options):
     """One differentiable frame: SplatRasterizer.draw forward, .backward / .camera_backward backward.
 
     Tensors in the library's layouts, float32 on rast.device: means3D / scales / rotations [N,4], opacities [N], shs [N,48]
@@ -236,12 +240,21 @@ def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs,
     the per-Gaussian outputs whose input requires a gradient, written into new tensors; when view, proj or cam_pos requires
     one, it runs with camera=True and returns the three camera gradients in the inputs' shapes. With a FrameSlot as radii_slot
     it also asks for dL_dmean2D, into a new [N,2] tensor left in the slot. It raises RuntimeError
-    before launching anything if `rast` drew again, or was rebound, after this call (see the module docstring)."""
+    before launching anything if `rast` drew again, or was rebound, after this call (see the module docstring).
+
+    antialiased=True: upstream's `antialiasing`. The opacities pass through antialias.compensate first — o' = o * c with
+    c = sqrt(det(cov2D) / det(cov2D + 0.3 I)), for the same semantics, scale_modifier, camera tensors, radii slot and the
+    rasterizer's width and height — and the frame is the ordinary frame of o': the geometry chunk, the depth channel, the
+    opacity map and gsr_contribution all see o'. Its backward adds c's gradients to the mean, the scales and the rotation.
+    No 3D filter, and no gradient to the camera through c: a view that requires a gradient is a ValueError."""
     assert set(draw_options) <= set(_DRAW_OPTIONS), sorted(draw_options)
     assert depth in (False, True, "inverse"), depth
     opts = {"tan_fov": (float(tan_fov[0]), float(tan_fov[1])), "semantics": semantics, "sh_degree": int(sh_degree),
             "scale_modifier": float(scale_modifier), "depth": depth, "radii_slot": radii_slot, "draw": dict(draw_options),
             "opacity_grad": bool(opacity_grad)}
+    if antialiased:
+        opacities = _antialias.compensate(means3D, scales, rotations, opacities, view, opts["tan_fov"], rast.width, rast.height,
+                                          semantics=semantics, scale_modifier=opts["scale_modifier"], proj=proj, radii_slot=radii_slot)
     return _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp)
 
 
@@ -358,7 +371,7 @@ def _camera_tensors(camera, dev):
 
 def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: str = "gscuda", sh_degree: int = 3,
            scale_modifier: float = 1.0, depth: "bool | str" = False, radii_slot: "RadiiSlot | None" = None,
-           opacity_grad: bool = False, **draw_options):
+           opacity_grad: bool = False, antialiased: bool = False, **draw_options):
     """`activate` then `rasterize`: (color [3,H,W], depth [H,W] or None, opacity_map [H,W]) of `params` seen from `camera`
     — a Camera (its matrices are uploaded once per device and kept with it; write to a Camera's arrays and it must be a new
     object) or a tuple (view, proj, cam_pos, tan_fovx, tan_fovy) whose first three are device tensors, which may require
@@ -366,7 +379,8 @@ def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: 
     gradients without their rows being read. radii_slot: a RadiiSlot of the caller's, used instead of the call's own; after
     the call its `.radii` is the frame's radii (i32[N], a new tensor per frame) — what optim.GaussianAdam.step() takes. A
     FrameSlot also receives, in the backward, the frame's dL_dmean2D [N,2] — what densify.DensityStats.update() takes.
-    opacity_grad=True: the opacity map is differentiable too (see `rasterize`)."""
+    opacity_grad=True: the opacity map is differentiable too (see `rasterize`). antialiased=True: the opacities are
+    compensated for the 0.3 dilation first (see `rasterize`); the view matrix must then not require a gradient."""
     if semantics == "inria" and sh_degree >= 1:
         assert params.sh_layout == "coefficient_major", 'semantics="inria" reads shs as [N][16][3]: sh_layout="coefficient_major"'
     slot = radii_slot if radii_slot is not None else RadiiSlot()
@@ -374,4 +388,4 @@ def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: 
     view, proj, cam_pos, tan_fovx, tan_fovy = _camera_tensors(camera, rast.device)
     return rasterize(rast, means3D, scales, rotations, opacities, params.shs, view, proj, cam_pos, (tan_fovx, tan_fovy),
                      semantics=semantics, sh_degree=sh_degree, scale_modifier=scale_modifier, depth=depth, radii_slot=slot,
-                     opacity_grad=opacity_grad, **draw_options)
+                     opacity_grad=opacity_grad, antialiased=antialiased, **draw_options)
