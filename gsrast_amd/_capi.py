@@ -1,5 +1,5 @@
 """ctypes binding of include/gsrast_amd.h, include/gsrast_amd_init.h, include/gsrast_amd_opacity.h, include/gsrast_amd_mcmc.h,
-include/gsrast_amd_contrib.h and include/gsrast_amd_antialias.h (the C ABI of libgsrast_amd.so).
+include/gsrast_amd_contrib.h, include/gsrast_amd_antialias.h and include/gsrast_amd_filter3d.h (the C ABI of libgsrast_amd.so).
 
 There is no fallback: if the HIP library has not been built, importing the product path
 raises. Field order and types below mirror the header exactly.
@@ -331,6 +331,44 @@ ANTIALIAS_SIGNATURES = {
     "gsr_antialias_backward": (C.c_int, [C.POINTER(AntialiasBackwardArgs)]),
 }
 
+# include/gsrast_amd_filter3d.h (Mip-Splatting's 3D smoothing filter: sampling rate, smoothing, gradient), in the same shape, with its own symbol test.
+GSR_FILTER3D_CAMERA_FLOATS = 20
+GSR_FILTER3D_CAMERA_CHUNK = 64
+
+
+class Filter3dObserveArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32),
+                ("num_gaussians", C.c_int32), ("position_stride", C.c_int32), ("num_cameras", C.c_int32),
+                ("positions", C.c_void_p), ("cameras", C.c_void_p), ("min_depth", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class Filter3dFinalizeArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("num_gaussians", C.c_int32), ("max_focal", C.c_float),
+                ("min_depth", C.c_void_p), ("filter", C.c_void_p), ("temp", C.c_void_p), ("temp_bytes", C.c_size_t),
+                ("stream", C.c_void_p)]
+
+
+class Filter3dArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("num_gaussians", C.c_int32),
+                ("scales", C.c_void_p), ("opacities", C.c_void_p), ("filter", C.c_void_p),
+                ("scales_out", C.c_void_p), ("opacities_out", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class Filter3dBackwardArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("num_gaussians", C.c_int32),
+                ("scales", C.c_void_p), ("opacities", C.c_void_p), ("filter", C.c_void_p),
+                ("dL_dscales_out", C.c_void_p), ("dL_dopacities_out", C.c_void_p), ("radii", C.c_void_p),
+                ("dL_dscales", C.c_void_p), ("dL_dopacities", C.c_void_p), ("stream", C.c_void_p)]
+
+
+FILTER3D_SIGNATURES = {
+    "gsr_filter3d_temp_bytes": (C.c_size_t, [C.c_int32]),
+    "gsr_filter3d_observe": (C.c_int, [C.POINTER(Filter3dObserveArgs)]),
+    "gsr_filter3d_finalize": (C.c_int, [C.POINTER(Filter3dFinalizeArgs)]),
+    "gsr_filter3d_forward": (C.c_int, [C.POINTER(Filter3dArgs)]),
+    "gsr_filter3d_backward": (C.c_int, [C.POINTER(Filter3dBackwardArgs)]),
+}
+
 _lib = None
 
 
@@ -356,7 +394,8 @@ def lib() -> C.CDLL:
         # torch's device pointers mean nothing to ours ("no HIP device"): this module imports torch first.
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(INIT_SIGNATURES.items()) + list(OPACITY_SIGNATURES.items())
-                                  + list(MCMC_SIGNATURES.items()) + list(CONTRIB_SIGNATURES.items()) + list(ANTIALIAS_SIGNATURES.items())):
+                                  + list(MCMC_SIGNATURES.items()) + list(CONTRIB_SIGNATURES.items()) + list(ANTIALIAS_SIGNATURES.items())
+                                  + list(FILTER3D_SIGNATURES.items())):
             fn = getattr(L, name, None)
             if fn is None and _TAG:
                 continue                       # (a tagged A/B build of an older tree may lack the newest entry points)

@@ -9,8 +9,10 @@ opacity. An antialiased frame is therefore the ordinary frame of the opacities o
   compensate     the same as a torch.autograd.Function, for trainers: what `rasterize(..., antialiased=True)` and
                  `render(..., antialiased=True)` put in front of the rasterizer.
 
-What the mode is not: there is no 3D smoothing filter, and no gradient reaches the camera through c — the view matrix is
-read, not differentiated; pose refinement in antialiased mode is out of scope and refused.
+This is the 2D half of Mip-Splatting; the other half, the 3D smoothing filter, is gsrast_amd/filter3d.py, whose smoothed
+scales and opacities this pass then sees (`render(..., filter_3d=values, antialiased=True)`). What the mode is not: no
+gradient reaches the camera through c — the view matrix is read, not differentiated; pose refinement in antialiased mode is
+out of scope and refused.
 """
 from __future__ import annotations
 

@@ -1,6 +1,7 @@
 """torch.autograd over the rasterizer: raw (trainable) parameters -> image, and `loss.backward()` back to them.
 
   activate   raw parameters -> the arrays gsr_forward takes (gsr_activate_params / _backward, csrc/activations.hip)
+  (filter3d.smooth   scales, opacities -> the 3D-filtered ones, between the two with filter_3d=values: gsrast_amd/filter3d.py)
   (antialias.compensate   opacities -> opacities * c, between the two with antialiased=True: gsrast_amd/antialias.py)
   rasterize  SplatRasterizer.draw / backward / camera_backward as one differentiable function
   GaussianParams, render   the two joined for a trainer: `render(params, rast, cam)` then `loss.backward()`
@@ -19,6 +20,7 @@ import torch
 
 from . import _capi
 from . import antialias as _antialias
+from . import filter3d as _filter3d
 from . import ply as _ply
 from .camera import Camera
 from .rasterizer import SplatRasterizer
@@ -125,7 +127,8 @@ def activate(xyz, opacity_logit, log_scale, rotation, *, radii_slot: "RadiiSlot 
     one only when the rasterizer is the sole consumer of the four outputs (as `render` does): a regulariser on `scales`
     reaches culled Gaussians too. The opacity compensation of antialiased=True (antialias.compensate) is a second consumer
     that keeps the assumption: its gradient is exactly zero wherever the rasterizer's is, because dL/do' = 0 for a Gaussian
-    that blended nothing."""
+    that blended nothing. So does the 3D smoothing filter of filter_3d=values (filter3d.smooth), which stands between the two:
+    the pass is elementwise, so its gradient is exactly zero wherever the gradients it receives are."""
     return _Activate.apply(xyz, opacity_logit, log_scale, rotation, radii_slot)
 
 
@@ -246,7 +249,8 @@ def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs,
     c = sqrt(det(cov2D) / det(cov2D + 0.3 I)), for the same semantics, scale_modifier, camera tensors, radii slot and the
     rasterizer's width and height — and the frame is the ordinary frame of o': the geometry chunk, the depth channel, the
     opacity map and gsr_contribution all see o'. Its backward adds c's gradients to the mean, the scales and the rotation.
-    No 3D filter, and no gradient to the camera through c: a view that requires a gradient is a ValueError."""
+    No gradient to the camera through c: a view that requires a gradient is a ValueError. (Mip-Splatting's 3D filter is
+    `render`'s filter_3d, or filter3d.smooth on the scales and opacities handed in here.)"""
     assert set(draw_options) <= set(_DRAW_OPTIONS), sorted(draw_options)
     assert depth in (False, True, "inverse"), depth
     opts = {"tan_fov": (float(tan_fov[0]), float(tan_fov[1])), "semantics": semantics, "sh_degree": int(sh_degree),
@@ -371,7 +375,7 @@ def _camera_tensors(camera, dev):
 
 def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: str = "gscuda", sh_degree: int = 3,
            scale_modifier: float = 1.0, depth: "bool | str" = False, radii_slot: "RadiiSlot | None" = None,
-           opacity_grad: bool = False, antialiased: bool = False, **draw_options):
+           opacity_grad: bool = False, antialiased: bool = False, filter_3d: "torch.Tensor | None" = None, **draw_options):
     """`activate` then `rasterize`: (color [3,H,W], depth [H,W] or None, opacity_map [H,W]) of `params` seen from `camera`
     — a Camera (its matrices are uploaded once per device and kept with it; write to a Camera's arrays and it must be a new
     object) or a tuple (view, proj, cam_pos, tan_fovx, tan_fovy) whose first three are device tensors, which may require
@@ -380,11 +384,17 @@ def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: 
     the call its `.radii` is the frame's radii (i32[N], a new tensor per frame) — what optim.GaussianAdam.step() takes. A
     FrameSlot also receives, in the backward, the frame's dL_dmean2D [N,2] — what densify.DensityStats.update() takes.
     opacity_grad=True: the opacity map is differentiable too (see `rasterize`). antialiased=True: the opacities are
-    compensated for the 0.3 dilation first (see `rasterize`); the view matrix must then not require a gradient."""
+    compensated for the 0.3 dilation first (see `rasterize`); the view matrix must then not require a gradient.
+    filter_3d: the 3D smoothing filter's values (filter3d.Filter3D.values: float32 [N] on the rasterizer's device, a constant),
+    or None for none. The activated scales and opacities then pass through filter3d.smooth before anything else sees them —
+    the rasterizer and, with antialiased=True, the 2D compensation, as in Mip-Splatting — and its backward takes the
+    gradients back to the raw parameters. Another length, dtype or device is a ValueError."""
     if semantics == "inria" and sh_degree >= 1:
         assert params.sh_layout == "coefficient_major", 'semantics="inria" reads shs as [N][16][3]: sh_layout="coefficient_major"'
     slot = radii_slot if radii_slot is not None else RadiiSlot()
     means3D, scales, rotations, opacities = params.activated(slot)
+    if filter_3d is not None:
+        scales, opacities = _filter3d.smooth(scales, opacities, filter_3d, radii_slot=slot)
     view, proj, cam_pos, tan_fovx, tan_fovy = _camera_tensors(camera, rast.device)
     return rasterize(rast, means3D, scales, rotations, opacities, params.shs, view, proj, cam_pos, (tan_fovx, tan_fovy),
                      semantics=semantics, sh_degree=sh_degree, scale_modifier=scale_modifier, depth=depth, radii_slot=slot,

@@ -7,8 +7,9 @@
  * so that the dilation keeps the splat's total weight. In gsr_forward the opacity decides nothing before the blend — radius,
  * rectangle, tiles, depth order and lists come from the dilated covariance alone, the opacity is copied into conic_opacity.w —
  * so an antialiased frame is gsr_forward handed o' = o * c, and its backward is gsr_backward, whose dL_dconic_opacity[:, 3] is
- * then dL/do', followed by gsr_antialias_backward. Not in here: a 3D smoothing filter, cov3D_precomp inputs, and the gradient
- * of c with respect to the camera — the view and projection matrices are READ, NOT DIFFERENTIATED.
+ * then dL/do', followed by gsr_antialias_backward. Mip-Splatting's 3D smoothing filter is a pass of its own in front of this one
+ * (gsrast_amd_filter3d.h), whose scales and opacities are then this call's inputs. Not in here: cov3D_precomp inputs, and the
+ * gradient of c with respect to the camera — the view and projection matrices are READ, NOT DIFFERENTIATED.
  *
  * The quantity, operation by operation. float32, no fused multiply-add, IEEE division and square root, unless said otherwise;
  * min / max are glm's: min(a, b) = (b < a) ? b : a, max(a, b) = (a < b) ? b : a; products of 3 x 3 matrices add their three
