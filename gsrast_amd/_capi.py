@@ -1,5 +1,6 @@
 """ctypes binding of include/gsrast_amd.h, include/gsrast_amd_init.h, include/gsrast_amd_opacity.h, include/gsrast_amd_mcmc.h,
-include/gsrast_amd_contrib.h, include/gsrast_amd_antialias.h and include/gsrast_amd_filter3d.h (the C ABI of libgsrast_amd.so).
+include/gsrast_amd_contrib.h, include/gsrast_amd_antialias.h, include/gsrast_amd_filter3d.h and include/gsrast_amd_absgrad.h (the C ABI
+of libgsrast_amd.so).
 
 There is no fallback: if the HIP library has not been built, importing the product path
 raises. Field order and types below mirror the header exactly.
@@ -369,6 +370,16 @@ FILTER3D_SIGNATURES = {
     "gsr_filter3d_backward": (C.c_int, [C.POINTER(Filter3dBackwardArgs)]),
 }
 
+# include/gsrast_amd_absgrad.h (AbsGS: the absolute screen-space gradient of a frame), in the same shape, with its own symbol test.
+class AbsgradArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("backward", C.POINTER(BackwardArgs)),
+                ("dL_dout_alpha", C.c_void_p), ("abs_dL_dmean2D", C.c_void_p), ("sums_f64", C.c_void_p), ("stage_ms", C.c_float)]
+
+
+ABSGRAD_SIGNATURES = {
+    "gsr_absgrad": (C.c_int, [C.POINTER(AbsgradArgs)]),
+}
+
 _lib = None
 
 
@@ -395,7 +406,7 @@ def lib() -> C.CDLL:
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(INIT_SIGNATURES.items()) + list(OPACITY_SIGNATURES.items())
                                   + list(MCMC_SIGNATURES.items()) + list(CONTRIB_SIGNATURES.items()) + list(ANTIALIAS_SIGNATURES.items())
-                                  + list(FILTER3D_SIGNATURES.items())):
+                                  + list(FILTER3D_SIGNATURES.items()) + list(ABSGRAD_SIGNATURES.items())):
             fn = getattr(L, name, None)
             if fn is None and _TAG:
                 continue                       # (a tagged A/B build of an older tree may lack the newest entry points)

@@ -46,11 +46,16 @@ class RadiiSlot:
 class FrameSlot(RadiiSlot):
     """A RadiiSlot that also receives, in the frame's backward, dL_dmean2D [N,2]: the gradient w.r.t. each Gaussian's
     pixel-space centre (no NDC factor; a new tensor per frame) — the statistic densify.DensityStats.update() accumulates.
-    The backward asks gsr_backward for one more array; the other gradients are the same bits as with a RadiiSlot."""
+    The backward asks gsr_backward for one more array; the other gradients are the same bits as with a RadiiSlot.
+    absgrad=True: the backward also calls SplatRasterizer.absgrad right behind gsr_backward, with the same three incoming
+    gradients, and leaves abs_dL_dmean2D [N,2] (AbsGS's sum of absolute per-pixel shares, a new tensor per frame) here — what
+    DensityStats.update(absgrad=True) takes. With the default nothing more is launched or allocated."""
 
-    def __init__(self):
+    def __init__(self, absgrad: bool = False):
         super().__init__()
+        self.absgrad = bool(absgrad)
         self.dL_dmean2D: "torch.Tensor | None" = None
+        self.abs_dL_dmean2D: "torch.Tensor | None" = None
 
 
 class _Activate(torch.autograd.Function):
@@ -213,6 +218,9 @@ class _Rasterize(torch.autograd.Function):
                             depth=opts["depth"] or None, camera=camera, into=into, sync=False, dL_dalpha=g_alpha)
         if frame_slot is not None:
             frame_slot.dL_dmean2D = res["dL_dmean2D"]
+            if frame_slot.absgrad:
+                frame_slot.abs_dL_dmean2D = rast.absgrad(g_color, dL_ddepth=g_depth if opts["depth"] else None, depth=opts["depth"] or None,
+                                                         dL_dalpha=g_alpha, receipt=ctx.receipt, semantics=opts["semantics"], sync=False)
         g = lambda k, on=True: res[k] if (on and k in res) else None
         cam_g = lambda k, name, shape: res[k].reshape(shape) if need[name] else None
         return (None, None, g("dL_dmeans3D"), g("dL_dscales", need["scales"]), g("dL_drotations"),
@@ -242,7 +250,8 @@ def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs,
     The backward asks gsr_backward (double sums: the gradients do not depend on the order of the tiles' atomics) for exactly
     the per-Gaussian outputs whose input requires a gradient, written into new tensors; when view, proj or cam_pos requires
     one, it runs with camera=True and returns the three camera gradients in the inputs' shapes. With a FrameSlot as radii_slot
-    it also asks for dL_dmean2D, into a new [N,2] tensor left in the slot. It raises RuntimeError
+    it also asks for dL_dmean2D, into a new [N,2] tensor left in the slot, and a FrameSlot(absgrad=True) also gets abs_dL_dmean2D
+    from one more pass (SplatRasterizer.absgrad). It raises RuntimeError
     before launching anything if `rast` drew again, or was rebound, after this call (see the module docstring).
 
     antialiased=True: upstream's `antialiasing`. The opacities pass through antialias.compensate first — o' = o * c with
@@ -382,7 +391,8 @@ def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: 
     gradients. `loss.backward()` fills params.*.grad (and the camera tensors' .grad). Gaussians the frame culled get zero
     gradients without their rows being read. radii_slot: a RadiiSlot of the caller's, used instead of the call's own; after
     the call its `.radii` is the frame's radii (i32[N], a new tensor per frame) — what optim.GaussianAdam.step() takes. A
-    FrameSlot also receives, in the backward, the frame's dL_dmean2D [N,2] — what densify.DensityStats.update() takes.
+    FrameSlot also receives, in the backward, the frame's dL_dmean2D [N,2] — what densify.DensityStats.update() takes — and,
+    as FrameSlot(absgrad=True), abs_dL_dmean2D [N,2], AbsGS's score, for DensityStats.update(absgrad=True).
     opacity_grad=True: the opacity map is differentiable too (see `rasterize`). antialiased=True: the opacities are
     compensated for the 0.3 dilation first (see `rasterize`); the view matrix must then not require a gradient.
     filter_3d: the 3D smoothing filter's values (filter3d.Filter3D.values: float32 [N] on the rasterizer's device, a constant),

@@ -56,11 +56,16 @@ class DensityStats:
     def num_gaussians(self) -> int:
         return int(self.grad_accum.shape[0])
 
-    def update(self, slot: FrameSlot, width: int, height: int) -> None:
+    def update(self, slot: FrameSlot, width: int, height: int, absgrad: bool = False) -> None:
         """Adds the frame `slot` carries (after its backward). One launch on the current stream, no synchronisation; a
-        Gaussian the frame culled keeps its three statistics and its gradient is not read."""
+        Gaussian the frame culled keeps its three statistics and its gradient is not read.
+        absgrad=True: AbsGS's score — slot.abs_dL_dmean2D (a FrameSlot(absgrad=True)) is accumulated in place of dL_dmean2D,
+        by the same kernel; ValueError if the slot holds none. grad_accum is then on another scale: see densify_and_prune."""
         n = self.num_gaussians
-        radii, grad = slot.radii, getattr(slot, "dL_dmean2D", None)
+        radii, grad = slot.radii, getattr(slot, "abs_dL_dmean2D" if absgrad else "dL_dmean2D", None)
+        if absgrad and grad is None:
+            raise ValueError("DensityStats.update(absgrad=True): the slot holds no abs_dL_dmean2D (a FrameSlot(absgrad=True) "
+                             "after render() and backward())")
         if radii is None or grad is None:
             raise ValueError("DensityStats.update: the slot holds no frame (a FrameSlot after render() and backward())")
         if (radii.dtype != torch.int32 or tuple(radii.shape) != (n,) or grad.dtype != torch.float32 or tuple(grad.shape) != (n, 2)
@@ -162,6 +167,10 @@ def densify_and_prune(params: GaussianParams, opt, stats: DensityStats, *, max_g
     the moments — only where there were any — follow their rows, zeros for clones and children. `stats` restarts from zeros
     at the new row count. One synchronisation (the counts). Returns (src_of i32[N_new]: the old row of every new row;
     (K, C, S, N_new): kept, clones, splits that survived, the new row count).
+
+    With statistics accumulated by DensityStats.update(absgrad=True) g is the mean of AbsGS's absolute score, which is never
+    below the signed norm and usually several times it: max_grad is then on another scale. gsplat suggests 0.0008 where 0.0002
+    serves the signed norm; that figure is gsplat's and has not been measured here.
 
     Raises ValueError before anything is launched or replaced: a parameter of `params` that `opt` does not hold; parameters
     or moments that are not float32, of the wrong shape, on another device, not contiguous from a 16-byte boundary; one

@@ -139,6 +139,7 @@ class SplatRasterizer:
         self.last_stage_ms: dict[str, float] = {}
         self.last_backward_ms: tuple = ()              # (render, chain) of the last backward(profile=True)
         self.last_camera_ms: "float | None" = None     # of the last camera_backward(profile=True)
+        self.last_absgrad_ms: "float | None" = None    # of the last absgrad(profile=True)
         self.rects: torch.Tensor | None = None
         self._bw = BackwardBuffers(self.device)
         # which colours a draw() composited (backward() reads the same ones): (that call's receipt serial, tensor or None)
@@ -533,6 +534,63 @@ class SplatRasterizer:
         if sync:
             torch.cuda.current_stream(dev).synchronize()
         return {k: arrays[k] for k in plan.result}
+
+    def absgrad(self, dL_dout: torch.Tensor, *, dL_ddepth: "torch.Tensor | None" = None, depth: "bool | str | None" = None,
+                dL_dalpha: "torch.Tensor | None" = None, receipt: "_capi.ForwardReceipt | None" = None, semantics: str = "gscuda",
+                tile_rows: "tuple[int, int] | None" = None, into: "torch.Tensor | None" = None, sync: bool = True,
+                profile: bool = False) -> torch.Tensor:
+        """The absolute screen-space gradient of the last draw() (AbsGS; gsr_absgrad of include/gsrast_amd_absgrad.h): [N,2],
+        per Gaussian and axis the sum over pixels of |each pixel's share of dL_dmean2D| — where backward()'s dL_dmean2D is the
+        absolute value of the sum at best. dL_dout, dL_ddepth, depth, dL_dalpha, receipt (a receipt is required: default this
+        object's last draw()), semantics and tile_rows as backward() takes them, and for the same frame: the result is that of
+        the loss backward() differentiates with the same arguments, its three terms joined per pixel before the absolute value
+        is taken. Pixel units, no NDC factor, as dL_dmean2D: densify.DensityStats.update(absgrad=True) takes it.
+        One more walk over the sorted lists (refused after draw(sorted_lists=False)); nothing of the forward state is written,
+        and backward() may run before or after it. The scratch (16 N bytes of doubles) is kept by this object, zero between
+        calls and dropped if a call fails. into: a float32 [N,2] tensor on this device, contiguous, written in full and
+        returned; else a new tensor. profile: last_absgrad_ms gets the pass's time."""
+        n, dev = self.num_gaussians, self.device
+        rcpt = self.last_receipt if receipt is None else receipt
+        assert rcpt is not None, "absgrad needs the receipt of a draw()"
+        assert semantics in ("gscuda", "inria"), semantics
+        if dL_dalpha is not None:
+            assert isinstance(dL_dalpha, torch.Tensor) and dL_dalpha.dtype == torch.float32, "dL_dalpha: a float32 tensor"
+            assert dL_dalpha.device == dev, ("dL_dalpha", dL_dalpha.device, dev)
+            assert tuple(dL_dalpha.shape) == (self.height, self.width), ("dL_dalpha", tuple(dL_dalpha.shape))
+        g = dL_dout.to(device=dev, dtype=torch.float32).contiguous()
+        assert g.shape == (3, self.height, self.width)
+        if into is not None:
+            assert into.dtype == torch.float32 and into.device == dev and into.is_contiguous() and tuple(into.shape) == (n, 2)
+        mode = None
+        if dL_ddepth is not None:
+            gd = dL_ddepth.to(device=dev, dtype=torch.float32).contiguous()
+            assert gd.shape == (self.height, self.width)
+            mode = backward_plan.depth_mode(depth, self.last_depth)
+        self._bw.fit(n)
+        b = self._backward_args(rcpt, self._colors_of(rcpt), semantics, 3)
+        b.dL_dout_color = g.data_ptr()
+        if dL_ddepth is not None:
+            b.dL_dout_depth = gd.data_ptr()
+        if tile_rows is not None:
+            b.tile_row_begin, b.tile_row_end = int(tile_rows[0]), int(tile_rows[1])
+        out = into if into is not None else torch.empty((n, 2), dtype=torch.float32, device=dev)
+        a = _capi.AbsgradArgs()
+        a.struct_size = C.sizeof(_capi.AbsgradArgs)
+        a.flags = (_capi.GSR_FLAG_PROFILE if profile else 0) | (_capi.GSR_FLAG_DEPTH_INVERSE if mode == "inverse" else 0)
+        a.backward = C.pointer(b)
+        ga = dL_dalpha.contiguous() if dL_dalpha is not None else None
+        a.dL_dout_alpha = ga.data_ptr() if ga is not None else None
+        a.abs_dL_dmean2D = out.data_ptr()
+        a.sums_f64 = self._bw.get("absgrad_sums_f64", n, 2, dtype=torch.float64, zero=True).data_ptr()
+        try:
+            _capi.call("gsr_absgrad", C.byref(a), device=dev)
+        except _capi.GsrError:
+            self._bw.scratch.pop("absgrad_sums_f64", None)     # (a call that failed half way may have left sums behind)
+            raise
+        self.last_absgrad_ms = float(a.stage_ms) if profile else None
+        if sync:
+            torch.cuda.current_stream(dev).synchronize()
+        return out
 
     def _colors_of(self, rcpt: "_capi.ForwardReceipt | None") -> "torch.Tensor | None":
         """The precomputed colours the draw() of `rcpt` composited, None where it took its geomState.rgb: they are recorded
