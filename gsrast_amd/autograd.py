@@ -49,7 +49,9 @@ class FrameSlot(RadiiSlot):
     The backward asks gsr_backward for one more array; the other gradients are the same bits as with a RadiiSlot.
     absgrad=True: the backward also calls SplatRasterizer.absgrad right behind gsr_backward, with the same three incoming
     gradients, and leaves abs_dL_dmean2D [N,2] (AbsGS's sum of absolute per-pixel shares, a new tensor per frame) here — what
-    DensityStats.update(absgrad=True) takes. With the default nothing more is launched or allocated."""
+    DensityStats.update(absgrad=True) takes. With the default nothing more is launched or allocated.
+    With rasterize / render(features=...) dL_dmean2D includes the feature map's term (it is the gradient of the whole loss);
+    abs_dL_dmean2D does not: it stays the score of the colour, depth and opacity terms."""
 
     def __init__(self, absgrad: bool = False):
         super().__init__()
@@ -145,7 +147,7 @@ STALE_MESSAGE = ("this rasterizer has drawn another frame, or was given another 
 
 class _Rasterize(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp):
+    def forward(ctx, rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, features=None):
         n, dev = int(means3D.shape[0]), rast.device
         means3D, scales, rotations = _f32c(means3D, (n, 4), "means3D"), _f32c(scales, (n, 4), "scales"), _f32c(rotations, (n, 4), "rotations")
         opacities, shs = _f32c(opacities, (n,), "opacities"), _f32c(shs, (n, 48), "shs")
@@ -161,31 +163,42 @@ class _Rasterize(torch.autograd.Function):
                   depth=depth, colors_precomp=colors_precomp if colors_precomp is not None else False, sorted_lists=True,
                   into=into, **opts["draw"])
         opacity_map = rast.opacity_map()                      # (1 - finalT: a new tensor)
+        feature_map = None
+        if features is not None:                              # (one more walk over the lists this draw() left; zero background)
+            if features.dtype != F32 or features.dim() != 2 or int(features.shape[0]) != n or features.device != dev:
+                raise ValueError(f"features: expected float32 [{n}, C] on {dev}, got {features.dtype} {tuple(features.shape)} on {features.device}")
+            features = features.contiguous()
+            feature_map = rast.render_features(features, sync=False)
         if opts["radii_slot"] is not None:
             opts["radii_slot"].radii = rast.map_geometry_state()["radii"].clone()
         ctx.rast, ctx.opts = rast, opts
         ctx.receipt, ctx.epoch = rast.last_receipt.copy(), rast._state_epoch
         ctx.view_shapes = (view.shape, proj.shape, cam_pos.shape)
         ctx.has_colors = colors_precomp is not None
-        ctx.save_for_backward(means3D, scales, rotations, opacities, shs)      # (a write to one of them before backward() is reported)
+        ctx.has_features = features is not None
+        if features is None:
+            ctx.save_for_backward(means3D, scales, rotations, opacities, shs)      # (a write to one of them before backward() is reported)
+        else:
+            ctx.save_for_backward(means3D, scales, rotations, opacities, shs, features)
         if not opts["opacity_grad"]:
             ctx.mark_non_differentiable(opacity_map)
-        else:
+        if opts["opacity_grad"] or features is not None:
             ctx.set_materialize_grads(False)                  # (a map the loss does not use arrives as None, not as zeros to run through)
-        return into["out_color"], into.get("out_depth"), opacity_map
+        return into["out_color"], into.get("out_depth"), opacity_map, feature_map
 
     @staticmethod
-    def backward(ctx, g_color, g_depth, g_opacity_map):
+    def backward(ctx, g_color, g_depth, g_opacity_map, g_feature_map=None):
         rast, opts = ctx.rast, ctx.opts
         if rast._state_epoch != ctx.epoch:
             raise RuntimeError(STALE_MESSAGE)
-        ctx.saved_tensors                                     # noqa: B018 (raises if one was modified in place)
-        need = dict(zip(("means3D", "scales", "rotations", "opacities", "shs", "view", "proj", "cam_pos", "colors_precomp"),
+        saved = ctx.saved_tensors                             # (raises if one was modified in place)
+        need = dict(zip(("means3D", "scales", "rotations", "opacities", "shs", "view", "proj", "cam_pos", "colors_precomp", "features"),
                         ctx.needs_input_grad[2:]))
         n, dev = rast.num_gaussians, rast.device
         g_alpha = g_opacity_map if opts["opacity_grad"] else None
-        if g_color is None and g_depth is None and g_alpha is None:
-            return (None,) * 11
+        feature_term = (saved[5], g_feature_map) if (ctx.has_features and g_feature_map is not None) else None
+        if g_color is None and g_depth is None and g_alpha is None and feature_term is None:
+            return (None,) * 12
         if g_color is None:
             g_color = torch.zeros((3, rast.height, rast.width), dtype=F32, device=dev)
         new = lambda *shape: torch.empty(shape, dtype=F32, device=dev)
@@ -209,13 +222,17 @@ class _Rasterize(torch.autograd.Function):
         if camera:
             into["camera"] = new(35)
         if not into:
-            return (None,) * 11
+            # nothing but the features requires a gradient: the frozen-geometry pass, no chain
+            d_feat = (rast.features_backward(*feature_term, receipt=ctx.receipt, sync=False)
+                      if (feature_term is not None and need["features"]) else None)
+            return (None,) * 11 + (d_feat,)
         frame_slot = opts["radii_slot"] if isinstance(opts["radii_slot"], FrameSlot) else None
         if frame_slot is not None:
             into["dL_dmean2D"] = new(n, 2)
         res = rast.backward(g_color, semantics=opts["semantics"], sh_degree=opts["sh_degree"], scale_modifier=opts["scale_modifier"],
                             receipt=ctx.receipt, wide_sums=True, dL_ddepth=g_depth if opts["depth"] else None,
-                            depth=opts["depth"] or None, camera=camera, into=into, sync=False, dL_dalpha=g_alpha)
+                            depth=opts["depth"] or None, camera=camera, into=into, sync=False, dL_dalpha=g_alpha,
+                            features=feature_term)
         if frame_slot is not None:
             frame_slot.dL_dmean2D = res["dL_dmean2D"]
             if frame_slot.absgrad:
@@ -226,13 +243,13 @@ class _Rasterize(torch.autograd.Function):
         return (None, None, g("dL_dmeans3D"), g("dL_dscales", need["scales"]), g("dL_drotations"),
                 res["dL_dconic_opacity"][:, 3] if need["opacities"] else None, g("dL_dshs", need["shs"]),
                 cam_g("dL_dview_matrix", "view", ctx.view_shapes[0]), cam_g("dL_dproj_matrix", "proj", ctx.view_shapes[1]),
-                cam_g("dL_dcam_pos", "cam_pos", ctx.view_shapes[2]), g("dL_dcolors"))
+                cam_g("dL_dcam_pos", "cam_pos", ctx.view_shapes[2]), g("dL_dcolors"), g("dL_dfeatures", need["features"]))
 
 
 def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, tan_fov, *,
               semantics: str = "gscuda", sh_degree: int = 3, scale_modifier: float = 1.0, depth: "bool | str" = False,
               colors_precomp: "torch.Tensor | None" = None, radii_slot: "RadiiSlot | None" = None, opacity_grad: bool = False,
-              antialiased: bool = False, **draw_options):
+              antialiased: bool = False, features: "torch.Tensor | None" = None, **draw_options):
     """One differentiable frame: SplatRasterizer.draw forward, .backward / .camera_backward backward.
 
     Tensors in the library's layouts, float32 on rast.device: means3D / scales / rotations [N,4], opacities [N], shs [N,48]
@@ -259,7 +276,15 @@ def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs,
     rasterizer's width and height — and the frame is the ordinary frame of o': the geometry chunk, the depth channel, the
     opacity map and gsr_contribution all see o'. Its backward adds c's gradients to the mean, the scales and the rotation.
     No gradient to the camera through c: a view that requires a gradient is a ValueError. (Mip-Splatting's 3D filter is
-    `render`'s filter_3d, or filter3d.smooth on the scales and opacities handed in here.)"""
+    `render`'s filter_3d, or filter3d.smooth on the scales and opacities handed in here.)
+
+    features: float32 [N,C] on rast.device (1 <= C <= 256), which may require a gradient. The call then returns a 4-tuple,
+    (color, depth, opacity_map, feature_map [C,H,W]): feature_map = sum_i features[i] alpha_i T_i with this frame's own alpha, T
+    and decisions (SplatRasterizer.render_features), composited over a ZERO background — add (1 - opacity_map) * bg yourself,
+    with opacity_grad=True if that term should reach the geometry. Its incoming gradient enters the same backward call as
+    colour, depth and opacity (SplatRasterizer.backward(features=...)): the camera gradients, FrameSlot.dL_dmean2D,
+    antialiased and the 3D filter all see the feature term. FrameSlot(absgrad=True)'s abs_dL_dmean2D does NOT include it.
+    Without `features` the 3-tuple and everything about the call stay exactly as they were."""
     assert set(draw_options) <= set(_DRAW_OPTIONS), sorted(draw_options)
     assert depth in (False, True, "inverse"), depth
     opts = {"tan_fov": (float(tan_fov[0]), float(tan_fov[1])), "semantics": semantics, "sh_degree": int(sh_degree),
@@ -268,7 +293,9 @@ def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs,
     if antialiased:
         opacities = _antialias.compensate(means3D, scales, rotations, opacities, view, opts["tan_fov"], rast.width, rast.height,
                                           semantics=semantics, scale_modifier=opts["scale_modifier"], proj=proj, radii_slot=radii_slot)
-    return _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp)
+    if features is None:
+        return _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, None)[:3]
+    return _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, features)
 
 
 def _rest_to_coefficient_major(sh: np.ndarray) -> np.ndarray:
@@ -384,7 +411,8 @@ def _camera_tensors(camera, dev):
 
 def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: str = "gscuda", sh_degree: int = 3,
            scale_modifier: float = 1.0, depth: "bool | str" = False, radii_slot: "RadiiSlot | None" = None,
-           opacity_grad: bool = False, antialiased: bool = False, filter_3d: "torch.Tensor | None" = None, **draw_options):
+           opacity_grad: bool = False, antialiased: bool = False, filter_3d: "torch.Tensor | None" = None,
+           features: "torch.Tensor | None" = None, **draw_options):
     """`activate` then `rasterize`: (color [3,H,W], depth [H,W] or None, opacity_map [H,W]) of `params` seen from `camera`
     — a Camera (its matrices are uploaded once per device and kept with it; write to a Camera's arrays and it must be a new
     object) or a tuple (view, proj, cam_pos, tan_fovx, tan_fovy) whose first three are device tensors, which may require
@@ -398,7 +426,9 @@ def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: 
     filter_3d: the 3D smoothing filter's values (filter3d.Filter3D.values: float32 [N] on the rasterizer's device, a constant),
     or None for none. The activated scales and opacities then pass through filter3d.smooth before anything else sees them —
     the rasterizer and, with antialiased=True, the 2D compensation, as in Mip-Splatting — and its backward takes the
-    gradients back to the raw parameters. Another length, dtype or device is a ValueError."""
+    gradients back to the raw parameters. Another length, dtype or device is a ValueError.
+    features: float32 [N,C] on the rasterizer's device (a Parameter of the caller's, say): the result is then the 4-tuple
+    (color, depth, opacity_map, feature_map [C,H,W]) of `rasterize`, the feature map over a zero background."""
     if semantics == "inria" and sh_degree >= 1:
         assert params.sh_layout == "coefficient_major", 'semantics="inria" reads shs as [N][16][3]: sh_layout="coefficient_major"'
     slot = radii_slot if radii_slot is not None else RadiiSlot()
@@ -408,4 +438,4 @@ def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: 
     view, proj, cam_pos, tan_fovx, tan_fovy = _camera_tensors(camera, rast.device)
     return rasterize(rast, means3D, scales, rotations, opacities, params.shs, view, proj, cam_pos, (tan_fovx, tan_fovy),
                      semantics=semantics, sh_degree=sh_degree, scale_modifier=scale_modifier, depth=depth, radii_slot=slot,
-                     opacity_grad=opacity_grad, antialiased=antialiased, **draw_options)
+                     opacity_grad=opacity_grad, antialiased=antialiased, features=features, **draw_options)

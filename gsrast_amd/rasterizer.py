@@ -140,6 +140,7 @@ class SplatRasterizer:
         self.last_backward_ms: tuple = ()              # (render, chain) of the last backward(profile=True)
         self.last_camera_ms: "float | None" = None     # of the last camera_backward(profile=True)
         self.last_absgrad_ms: "float | None" = None    # of the last absgrad(profile=True)
+        self.last_features_ms: "float | None" = None   # of the last render_features / features_backward / backward(features=...) with profile=True
         self.rects: torch.Tensor | None = None
         self._bw = BackwardBuffers(self.device)
         # which colours a draw() composited (backward() reads the same ones): (that call's receipt serial, tensor or None)
@@ -444,7 +445,7 @@ class SplatRasterizer:
                  sh_degree: int = 3, receipt: "_capi.ForwardReceipt | None | bool" = None, wide_sums: bool = True,
                  outputs: "tuple[str, ...] | None" = None, dL_ddepth: "torch.Tensor | None" = None,
                  depth: "bool | str | None" = None, camera: bool = False, into: "dict | None" = None,
-                 sync: bool = True, dL_dalpha: "torch.Tensor | None" = None) -> dict:
+                 sync: bool = True, dL_dalpha: "torch.Tensor | None" = None, features: "tuple | None" = None) -> dict:
         """Gradients of sum(dL_dout * out_color) of the LAST draw() through gsr_backward; `semantics` / `sh_degree`
         must be those of that draw(). receipt: the gsr_forward_receipt of the draw() this is the backward of (default:
         this object's last draw(); any host thread may call); False = none, the reference's contract only (sorted lists
@@ -476,9 +477,18 @@ class SplatRasterizer:
         three as views of into["camera"]): memory no later call of this object writes. None of this object's output buffers
         is allocated for such a call; what the call needs beside them (dL_ddepths, the camera pass's inputs) is scratch
         of this object. dL_dshs under semantics="gscuda" must come zero-filled: that chain writes floats 0..15 of each row.
-        sync=False: returns without waiting for the stream."""
+        sync=False: returns without waiting for the stream.
+        features (needs wide_sums and a receipt): (F [N,C], dL_dfeature_map [C,H,W][, background [C]]) — the loss gains
+        sum(dL_dfeature_map * render_features(F, background=...)). gsr_features_backward runs first, on the same stream, and adds
+        the feature term's geometry sums into this object's sums_f64 scratch; gsr_backward / gsr_backward_alpha then chains the
+        total, so every output (the camera's included) holds the feature term, and the result also holds dL_dfeatures [N,C], a
+        new tensor. On an error both scratches are dropped. Without `features` the call is what it was."""
         n, dev = self.num_gaussians, self.device
         rcpt = self.last_receipt if receipt is None else (None if receipt is False else receipt)
+        if features is not None:                 # (checked before the first copy or launch of this call)
+            assert wide_sums, "features= needs wide_sums: the feature term reaches the chain through the sums_f64 scratch"
+            assert rcpt is not None, "features= needs the receipt of a draw()"
+            assert isinstance(features, (tuple, list)) and len(features) in (2, 3), "features=(F, dL_dfeature_map[, background])"
         col = self._colors_of(rcpt)
         plan = backward_plan.plan_backward(semantics, with_cov3D, wide_sums, None if outputs is None else tuple(outputs),
                                            None if into is None else tuple(into), dL_ddepth is not None, camera, col is not None)
@@ -515,7 +525,16 @@ class SplatRasterizer:
             a.scale_modifier = scale_modifier
         if tile_rows is not None:
             a.tile_row_begin, a.tile_row_end = int(tile_rows[0]), int(tile_rows[1])
+        feature_call = None
+        if features is not None:
+            feature_call, feature_keep = self._features_call(rcpt, features[0], features[2] if len(features) > 2 else None,
+                                                             dL_dout=features[1], profile=profile)
         try:
+            if feature_call is not None:        # its geometry sums go where gsr_backward's go: that call chains the total
+                feature_call.geometry_sums_f64 = a.sums_f64
+                if tile_rows is not None:
+                    feature_call.tile_row_begin, feature_call.tile_row_end = int(tile_rows[0]), int(tile_rows[1])
+                _capi.call("gsr_features_backward", C.byref(feature_call), device=dev)
             if dL_dalpha is None:
                 _capi.call("gsr_backward", C.byref(a), device=dev)
             else:
@@ -525,15 +544,119 @@ class SplatRasterizer:
             if wide_sums:                        # (a call that failed half way may have left sums behind: the next starts from zeroed ones)
                 self._bw.scratch.pop("sums_f64", None)
                 self._bw.scratch.pop("depth_sums_f64", None)
+            self._bw.scratch.pop("feature_sums_f64", None)
             raise
         self.last_backward_ms = (float(a.stage_ms[0]), float(a.stage_ms[1])) if profile else ()
+        if feature_call is not None:
+            self.last_features_ms = float(feature_call.stage_ms) if profile else None
+            arrays["dL_dfeatures"] = feature_keep[-1]
         if camera:
             arrays.update(self.camera_backward({k: arrays[k] for k in plan.camera_inputs}, semantics=semantics,
                                                sh_degree=sh_degree, shs_colour="dL_dcolors" in plan.camera_inputs, depth=mode,
                                                profile=profile, sync=False, into=into["camera"] if plan.camera_into else None))
         if sync:
             torch.cuda.current_stream(dev).synchronize()
-        return {k: arrays[k] for k in plan.result}
+        return {k: arrays[k] for k in tuple(plan.result) + (("dL_dfeatures",) if feature_call is not None else ())}
+
+    # -- N-channel feature maps (include/gsrast_amd_features.h) -------------------------------
+    def _features_call(self, rcpt: _capi.ForwardReceipt, features: torch.Tensor, background, *, out: "torch.Tensor | None" = None,
+                       dL_dout: "torch.Tensor | None" = None, into: "torch.Tensor | None" = None,
+                       tile_rows: "tuple[int, int] | None" = None, profile: bool = False):
+        """(gsr_features_args, the tensors it points at) for the frame of `rcpt`: the forward call's with `out`, the backward
+        call's with dL_dout — the last tensor of the list is then dL_dfeatures (`into`, or a new one), and the double scratch
+        is this object's (created zero, left zero by the library)."""
+        n, dev = self.num_gaussians, self.device
+        assert isinstance(features, torch.Tensor) and features.dtype == torch.float32 and features.device == dev, "features: a float32 tensor on this device"
+        assert features.dim() == 2 and features.shape[0] == n, ("features", tuple(features.shape), n)
+        c = int(features.shape[1])
+        f = features.detach().contiguous()
+        keep = [f]
+        gst, ist, bst = _capi.GeometryState(), _capi.ImageState(), _capi.BinningState()
+        self.lib.gsr_geometry_from_chunk(self.geom.base(), n, C.byref(gst))
+        self.lib.gsr_image_from_chunk(self.image.base(), self.width * self.height, C.byref(ist))
+        self.lib.gsr_binning_from_chunk(self.binning.base(), int(rcpt.num_rendered), C.byref(bst))
+        a = _capi.FeaturesArgs()
+        a.struct_size = C.sizeof(_capi.FeaturesArgs)
+        a.flags = _capi.GSR_FLAG_PROFILE if profile else 0
+        a.num_gaussians, a.width, a.height, a.channels = n, self.width, self.height, c
+        a.means2D, a.conic_opacity = gst.means2D, gst.conic_opacity
+        a.ranges, a.n_contrib, a.final_t = ist.ranges, ist.n_contrib, ist.accum_alpha
+        a.point_list = bst.values
+        a.receipt = rcpt
+        a.features = f.data_ptr()
+        if background is not None:
+            bg = _dev(background, dev).reshape(-1)
+            assert bg.numel() == c, ("background", tuple(bg.shape), c)
+            keep.append(bg)
+            a.background = bg.data_ptr()
+        if tile_rows is None:                    # (the band the draw() itself had: the calls take no other)
+            tile_rows = (int(rcpt.tile_row_begin), int(rcpt.tile_row_end))
+        a.tile_row_begin, a.tile_row_end = int(tile_rows[0]), int(tile_rows[1])
+        a.stream = _capi.stream(dev)
+        if out is not None:
+            a.out = out.data_ptr()
+            keep.append(out)
+        if dL_dout is not None:
+            g = dL_dout.to(device=dev, dtype=torch.float32).contiguous()
+            assert tuple(g.shape) == (c, self.height, self.width), ("dL_dfeature_map", tuple(g.shape))
+            if into is not None:
+                assert into.dtype == torch.float32 and into.device == dev and into.is_contiguous() and tuple(into.shape) == (n, c)
+            res = into if into is not None else torch.empty((n, c), dtype=torch.float32, device=dev)
+            self._bw.fit(n)
+            scratch = self._bw.scratch.get("feature_sums_f64")
+            if scratch is None or scratch.numel() < n * c:       # (all zero between calls: a larger C takes a new one)
+                scratch = self._bw.scratch["feature_sums_f64"] = torch.zeros(n * c, dtype=torch.float64, device=dev)
+            a.dL_dout, a.dL_dfeatures, a.feature_sums_f64 = g.data_ptr(), res.data_ptr(), scratch.data_ptr()
+            keep += [g, res]
+        return a, keep
+
+    def render_features(self, features: torch.Tensor, *, background=None, receipt: "_capi.ForwardReceipt | None" = None,
+                        tile_rows: "tuple[int, int] | None" = None, into: "torch.Tensor | None" = None, profile: bool = False,
+                        sync: bool = True) -> torch.Tensor:
+        """[C,H,W]: sum_i features[i] alpha_i T_i per pixel of the last draw() (gsr_features_forward), with that call's own
+        alpha, T and decisions — call it after a draw() and before the next one, as ContributionStats.update is used.
+        features: float32 [N,C] on this device, 1 <= C <= 256. background: C floats composited behind (final_t * background),
+        or None for none. With the frame's colours and background the result is out_color bit for bit. receipt: default this
+        object's last draw(). tile_rows: the band to write, which must be that of the draw() (the default: the receipt's own rows);
+        other rows are left alone. into: a float32 [C,H,W] tensor on this device, contiguous, written and returned; else a new
+        tensor, zeros outside the band (all zeros for an empty band).
+        One more walk over the sorted lists (refused after draw(sorted_lists=False)). profile: last_features_ms gets the time."""
+        rcpt = self.last_receipt if receipt is None else receipt
+        assert rcpt is not None, "render_features needs the receipt of a draw()"
+        assert isinstance(features, torch.Tensor) and features.dim() == 2, "features: [N,C]"
+        shape = (int(features.shape[1]), self.height, self.width)
+        if into is not None:
+            assert into.dtype == torch.float32 and into.device == self.device and into.is_contiguous() and tuple(into.shape) == shape
+        # (a call writes the rows of its band only — tile_rows, else the receipt's own band: anything but the whole frame starts from zeros)
+        whole = tile_rows is None and (int(rcpt.tile_row_begin), int(rcpt.tile_row_end)) == (0, (self.height + 15) // 16)
+        out = into if into is not None else (torch.empty if whole else torch.zeros)(shape, dtype=torch.float32, device=self.device)
+        a, _keep = self._features_call(rcpt, features, background, out=out, tile_rows=tile_rows, profile=profile)
+        _capi.call("gsr_features_forward", C.byref(a), device=self.device)
+        self.last_features_ms = float(a.stage_ms) if profile else None
+        if sync:
+            torch.cuda.current_stream(self.device).synchronize()
+        return out
+
+    def features_backward(self, features: torch.Tensor, dL_dout: torch.Tensor, *, background=None,
+                          receipt: "_capi.ForwardReceipt | None" = None, tile_rows: "tuple[int, int] | None" = None,
+                          into: "torch.Tensor | None" = None, profile: bool = False, sync: bool = True) -> torch.Tensor:
+        """dL_dfeatures [N,C] of sum(dL_dout * render_features(features)) for the last draw() (gsr_features_backward with no
+        geometry sums: the frozen-geometry case — nothing else is computed and no scratch shared with backward() is touched;
+        for the geometry's gradients too, pass features= to backward()). dL_dout: [C,H,W]. `background` does not enter this
+        gradient and is accepted for symmetry. The scratch (8 N C bytes of doubles) is kept by this object, zero between calls
+        and dropped if a call fails. into: a float32 [N,C] tensor on this device, contiguous, written in full and returned."""
+        rcpt = self.last_receipt if receipt is None else receipt
+        assert rcpt is not None, "features_backward needs the receipt of a draw()"
+        a, keep = self._features_call(rcpt, features, background, dL_dout=dL_dout, into=into, tile_rows=tile_rows, profile=profile)
+        try:
+            _capi.call("gsr_features_backward", C.byref(a), device=self.device)
+        except _capi.GsrError:
+            self._bw.scratch.pop("feature_sums_f64", None)     # (a call that failed half way may have left sums behind)
+            raise
+        self.last_features_ms = float(a.stage_ms) if profile else None
+        if sync:
+            torch.cuda.current_stream(self.device).synchronize()
+        return keep[-1]
 
     def absgrad(self, dL_dout: torch.Tensor, *, dL_ddepth: "torch.Tensor | None" = None, depth: "bool | str | None" = None,
                 dL_dalpha: "torch.Tensor | None" = None, receipt: "_capi.ForwardReceipt | None" = None, semantics: str = "gscuda",

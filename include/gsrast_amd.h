@@ -463,7 +463,19 @@ typedef struct gsr_backward_args {
                                       Gaussian (the four arrays above) are accumulated in double — a splat that fills the screen
                                       collects terms of either sign from 8 160 tiles, and in float their order of arrival shows
                                       in the fourth digit of its gradients, differently every run — and rounded to float once;
-                                      the float arrays need not be cleared by anybody then */
+                                      the float arrays need not be cleared by anybody then.
+                                      SEEDED SUMS: instead of zeros the rows of Gaussians with radii > 0 may hold, on entry, sums
+                                      in this layout that gsr_features_backward (gsrast_amd_features.h: geometry_sums_f64) of the
+                                      SAME forward call and tile rows left there. They are added to what the render backward sums
+                                      (every output and the chain see the total), and everything is left zero on return; a zero
+                                      scratch behaves exactly as before. Every path only ever ADDS to the array before the
+                                      per-Gaussian kernel reads, rounds and zeroes it: the render backward's direct double
+                                      atomics, and flush_block_acc_kernel's where the block lists feed it. With an empty band of
+                                      tile rows neither runs and the per-Gaussian kernel alone reads and zeroes the rows. With
+                                      num_rendered == 0 the call returns before that kernel and neither reads nor zeroes the
+                                      array — gsr_features_backward of such a receipt adds nothing, so there is nothing to
+                                      lose. Rows with radii <= 0 are never read: a seed there would stay (no list names such
+                                      a Gaussian, so gsr_features_backward never writes one) */
     /* chain down to the inputs (all optional; without sums_f64 they need dL_dcov3D) */
     const float* proj_matrix;      /* inputs of the forward call */
     const float* scales;
