@@ -27,6 +27,7 @@
 #include "../../include/gsrast_amd_opacity.h"
 #include "blend_core.hpp"
 #include "blockbin.hpp"
+#include "wave_reduce.hpp"
 
 namespace gsr {
 namespace {
@@ -69,34 +70,8 @@ struct RenderBackwardParams {
 __device__ __forceinline__ float wave_sum12(float a0, float a1, float a2, float a3, float a4, float a5, float a6, float a7, float a8,
                                             float a9, float a10, float a11) {
     const int lane = threadIdx.x & (kWave - 1);
-    auto swap32 = [](float& x, float& y) {
-        auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-        x = __uint_as_float(r[0]); y = __uint_as_float(r[1]);
-    };
-    auto swap16 = [](float& x, float& y) {
-        auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-        x = __uint_as_float(r[0]); y = __uint_as_float(r[1]);
-    };
-#define GSR_DPP(v, ctrl) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xf, 0xf, false))
-    swap32(a0, a1); float p = a0 + a1;           // rows 0, 1: value 0 (lanes l and l + 32 added); rows 2, 3: value 1
-    swap32(a2, a3); float q = a2 + a3;
-    swap32(a4, a5); float r = a4 + a5;
-    swap32(a6, a7); float t = a6 + a7;
-    swap16(p, q); const float t0 = p + q;        // rows: value 0, 2, 1, 3, each added over the four 16-lane groups
-    swap16(r, t); const float t1 = r + t;        // rows: value 4, 6, 5, 7
-    const bool upper = (lane & 8) != 0;
-    float u = (upper ? t1 : t0) + GSR_DPP(upper ? t0 : t1, 0x128);      // row_ror:8: lanes 0-7 of a row now carry t0, lanes 8-15 t1
-    u += GSR_DPP(u, 0xB1);                       // quad_perm [1,0,3,2]
-    u += GSR_DPP(u, 0x4E);                       // quad_perm [2,3,0,1]
-    u += GSR_DPP(u, 0x141);                      // row_half_mirror
-    swap32(a8, a9); float pp = a8 + a9;          // rows 0, 1: value 8; rows 2, 3: value 9
-    swap32(a10, a11); float qq = a10 + a11;      // rows 0, 1: value 10; rows 2, 3: value 11
-    swap16(pp, qq); float w = pp + qq;           // rows: value 8, 10, 9, 11
-    w += GSR_DPP(w, 0x128);                      // row_ror:8
-    w += GSR_DPP(w, 0xB1);
-    w += GSR_DPP(w, 0x4E);
-    w += GSR_DPP(w, 0x141);                      // every lane of a row: the row's total
-#undef GSR_DPP
+    const float u = wave_sum8(a0, a1, a2, a3, a4, a5, a6, a7, lane);      // (wave_reduce.hpp)
+    const float w = wave_sum4(a8, a9, a10, a11);                           // every lane of a row: the row's total
     return (lane & 7) == 4 ? w : u;
 }
 
