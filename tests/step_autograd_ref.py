@@ -23,7 +23,18 @@ The decisions inside a pixel (alpha < 1/255, power > 0, the 0.99 clamp, the cut-
 in its own arithmetic, without gradient. A pixel on which one of them lies within a relative 1e-5 of its threshold, or
 whose last contributor differs from nContrib, is left out of the loss (pixels_to_drop).
 
-forward(..., cut=NAME) detaches exactly one coupling (CUTS): the blindness guards of the tests."""
+forward(..., cut=NAME) detaches exactly one coupling (CUTS): the blindness guards of the tests.
+
+The options of autograd.render beyond colour and depth, all off by default (tests/step_frames.py's FULL_CASES use them;
+tests/test_step_full_cpu.py pins them): the 3D smoothing filter between the activations and everything else (filter_3d, a
+constant; tests/filter3d_ref.smoothing64), the opacity compensation of antialiased=True formed from this forward's own cov2D
+nodes, a feature map of leaf["features"] over a zero background, and the accumulated opacity 1 - T as a map. Their float32
+decisions join the structure (with_decisions):
+  identity  bool[N]    the smoothing leaves the row as it is (f * f > 0 fails in float32: filter3d_ref.forward_f32)
+  flows     bool[N]    c = sqrt(d0 / d1) is computed and differentiated; floored, d1_bad bool[N]: the rows that take a constant
+                       instead (the square root of the floor; 1), as antialias_ref.compensation_f32 decides them
+No Gaussian is left out for them: rows_near_a_threshold reports the visible rows on which one lies within MARGIN of its
+threshold or differs from its float64 twin, and the tests assert that there are none."""
 from __future__ import annotations
 
 import numpy as np
@@ -31,7 +42,14 @@ import torch
 
 F64, F32 = torch.float64, torch.float32
 RAW = ("xyz", "opacity_logit", "log_scale", "rotation", "shs")
-CUTS = ("background", "jacobian_mean", "view_direction", "depth_mean", "clamp_to_tz", "modifier", "quat_norm", "cov2D_view")
+CUTS = ("background", "jacobian_mean", "view_direction", "depth_mean", "clamp_to_tz", "modifier", "quat_norm", "cov2D_view",
+        # the filter: ds'/ds taken as 1; do'/do taken as 1 (the coefficient not applied to the opacity's gradient); the
+        # coefficient's own dependence on the scales dropped
+        "filter_scale", "filter_opacity", "filter_coef",
+        # the compensation: c a constant; c differentiated along the unsmoothed scales' path (ds'/ds = 1 inside c only)
+        "compensation", "compensation_scales",
+        # the feature map's geometry (only dL/dF flows); the opacity map
+        "feature_geometry", "opacity_map")
 
 SH_C0 = 0.28209479177387814
 SH_C1 = 0.4886025119029199
@@ -43,12 +61,15 @@ _f = lambda x: float(np.float32(x))
 ALPHA_MIN = float(np.float32(1.0) / np.float32(255.0))
 ALPHA_MAX = _f(0.99)
 MARGIN = 1e-5
+FLOOR_R = _f(0.000025)                                       # the floor of d0 / d1 under the compensation's square root ...
+C_FLOORED = float(np.sqrt(np.float32(0.000025)))           # ... and a floored row's c: the float32 square root of it
 
 # The GPU bound of gradient array k of a case of tests/step_frames.py, as a share of the reference array's largest entry:
 # max(2e-4, 2 e32[k]), e32 = what float32 arithmetic alone does to the array on that frame (this restatement in float32
 # against itself in float64, same structure, same dropped pixels). 2e-4 is the RTOL of tests/test_gpu_backward*.py.
 # tests/test_step_autograd_cpu.py measures e32 and checks this table against it. Entries: (case, array) -> bound, for the
-# arrays whose 2 e32 exceeds the floor — none does (e32 is at most 3.5e-6): every array of every case is at the floor.
+# arrays whose 2 e32 exceeds the floor — none does (e32 is at most 3.5e-6 on CASES and 5.1e-6 on FULL_CASES, which
+# tests/test_step_full_cpu.py measures in the same way): every array of every case is at the floor.
 FLOOR = 2e-4
 BOUNDS = {}
 
@@ -89,15 +110,39 @@ def structure_of(means3D, view, tan_fovx, tan_fovy, width, height, radii, ranges
             "clx": clx, "cly": cly, "sx": sx, "sy": sy}
 
 
+def with_decisions(structure, masks=None, identity=None):
+    """structure plus the float32 decisions of the compensation (masks: antialias_ref.compensation_f32's result on the arrays
+    the compensation reads) and of the smoothing (identity: filter3d_ref.forward_f32's). The compensation's clamp decisions
+    must be the ones the structure already holds for the visible Gaussians: one t, one clamp, read by the conic and by c."""
+    out = dict(structure)
+    vis = structure["vis"]
+    if masks is not None:
+        assert not (masks["culled"] & vis).any()
+        for a, b in ((masks["hi_x"] | masks["lo_x"], structure["clx"]), (masks["hi_y"] | masks["lo_y"], structure["cly"]),
+                     (masks["hi_x"], structure["clx"] & (structure["sx"] > 0)), (masks["hi_y"], structure["cly"] & (structure["sy"] > 0))):
+            assert (np.asarray(a)[vis] == np.asarray(b)[vis]).all()
+        out.update(flows=np.asarray(masks["flows"], bool), floored=np.asarray(masks["floored"], bool),
+                   d1_bad=np.asarray(masks["d1_bad"], bool))
+        assert ((out["flows"] ^ out["floored"] ^ out["d1_bad"]) & ~(out["flows"] & out["floored"] & out["d1_bad"]))[vis].all()
+    if identity is not None:
+        out["identity"] = np.asarray(identity, bool)
+    return out
+
+
 # ---- the differentiable forward ----------------------------------------------------------------------------------------------
-def leaves(raw, cam, dtype=F64, colors=False):
-    """The leaf tensors forward() is differentiated by: the raw parameters (and `colors` for the colors_precomp case) and the
-    three camera tensors, from their float32 values."""
+def leaves(raw, cam, dtype=F64, colors=False, features=None, constant=()):
+    """The leaf tensors forward() is differentiated by: the raw parameters (and `colors` for the colors_precomp case,
+    `features` [N,C] for the feature map) and the three camera tensors, from their float32 values. constant: names of
+    the camera tensors that are no leaves (the view matrix under antialiased=True)."""
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dtype).requires_grad_(True)
     out = {k: t(raw[k]) for k in RAW}
     if colors:
         out["colors"] = t(raw["colors"])
+    if features is not None:
+        out["features"] = t(features)
     out.update(view=t(cam.view), proj=t(cam.proj), cam_pos=t(cam.cam_pos))
+    for k in constant:
+        out[k] = out[k].detach()
     return out
 
 
@@ -136,15 +181,30 @@ def _rotation(q, profile):
 
 
 def forward(leaf, structure, tan_fovx, tan_fovy, width, height, *, background, profile="gscuda", sh_degree=0,
-            scale_modifier=1.0, depth=False, cut=None):
+            scale_modifier=1.0, depth=False, cut=None, filter_3d=None, antialiased=False, opacity=False, modifier_first=False):
     """(color [3,H,W], depth [H,W] or None, aux). leaf: dict of tensors xyz [N,3], opacity_logit [N], log_scale [N,3],
     rotation [N,4], shs [N,48], view [16], proj [16], cam_pos [3] and optionally colors [N,3] (composited as given, no SH).
     aux: the activated tensors means3D [N,3], scales [N,3], rotations [N,4], opacities [N] (graph nodes: differentiate by them
     for the gradients gsr_backward returns), finalT [H,W], last [H,W] (this forward's last contributor) and near [H,W]
     (a decision of the pixel within MARGIN of its threshold), visible (the indices of the visible Gaussians), per_gaussian
     (graph nodes over the visible Gaussians: mean2D [n,2], cov2D [n,3] = (a, b, c) dilated, colors [n,3], depths [n] or None —
-    what the blend reads, for the per-Gaussian sums of the render backward) and cov3D [n,6]."""
+    what the blend reads, for the per-Gaussian sums of the render backward) and cov3D [n,6].
+
+    filter_3d [N] (float32 values, a constant): the activated (scales, opacities) become filter3d_ref.smoothing64's, and
+    everything downstream reads those — the modifier multiplies the SMOOTHED scale. aux["scales"] / ["opacities"] stay the
+    activated nodes; the smoothed ones are aux["scales_smoothed"] / ["opacities_smoothed"]. modifier_first=True is the WRONG
+    order (the smoothing of the modified scale), kept for the test that shows the image tells the two apart.
+    antialiased: the blend's opacity is o c, c = sqrt(max(0.000025, d0 / d1)) with d0 the determinant of this forward's cov
+    before the dilation and d1 the one after it — the nodes the conic is made of. aux["compensation"] [n]; per_gaussian
+    gains "opacities" [n], the opacity the blend reads.
+    leaf["features"] [N,C]: aux["feature_map"] [C,H,W] = sum F_i alpha_i T_i over a zero background. opacity=True:
+    aux["opacity_map"] [H,W] = 1 - T. Both are graph nodes. aux["rows"]: float64 numpy over the visible Gaussians of what
+    the row decisions are taken on (rx, ry = t.x / t.z, t.y / t.z; r = d0 / d1 and d1 when antialiased). aux["blended"]
+    bool[n]: some pixel composites the Gaussian."""
     assert cut is None or cut in CUTS, cut
+    assert filter_3d is not None or (not modifier_first and cut not in ("filter_scale", "filter_opacity", "filter_coef"))
+    assert cut != "compensation_scales" or (antialiased and filter_3d is not None)
+    assert cut != "compensation" or antialiased
     assert profile in ("gscuda", "inria") and depth in (False, True, "inverse")
     inria = profile == "inria"
     dt = leaf["xyz"].dtype
@@ -158,13 +218,29 @@ def forward(leaf, structure, tan_fovx, tan_fovy, width, height, *, background, p
     aux = {"means3D": means3D, "scales": scales, "rotations": rotations, "opacities": opacities}
     idx = torch.from_numpy(np.nonzero(structure["vis"])[0])
     n = idx.numel()
-    m, s, q, o = means3D[idx], scales[idx], rotations[idx], opacities[idx]
+    s_all, o_all = scales, opacities
+    if filter_3d is not None:
+        from filter3d_ref import smoothing64
+        ident = torch.from_numpy(np.asarray(structure["identity"], bool))
+        s_in = scale_modifier * scales if modifier_first else scales
+        s_all, o_all = smoothing64(s_in, opacities, cst(np.asarray(filter_3d, np.float32)), ident)
+        if cut == "filter_scale":
+            s_all = s_in + (s_all - s_in).detach()
+        elif cut in ("filter_opacity", "filter_coef"):
+            coef = torch.where(ident, torch.ones_like(opacities), o_all / opacities)
+            o_all = (opacities.detach() * coef + (opacities - opacities.detach()) if cut == "filter_opacity"
+                     else opacities * coef.detach())
+        aux.update(scales_smoothed=s_all, opacities_smoothed=o_all)
+    m, s, q, o = means3D[idx], s_all[idx], rotations[idx], o_all[idx]
     # -- cov3D = R diag(mod s)^2 R^T
     if not inria:
         qn = torch.sqrt((q * q).sum(1, keepdim=True))
         q = q / (qn.detach() if cut == "quat_norm" else qn)
     R = _rotation(q, profile)
-    ms = s + (s * (scale_modifier - 1.0)).detach() if cut == "modifier" else scale_modifier * s
+    if modifier_first:
+        ms = s
+    else:
+        ms = s + (s * (scale_modifier - 1.0)).detach() if cut == "modifier" else scale_modifier * s
     M = R * ms[:, None, :]
     Sigma = M @ M.transpose(1, 2)
     # -- t = V (x, y, z, 1)
@@ -190,6 +266,24 @@ def forward(leaf, structure, tan_fovx, tan_fovy, width, height, *, background, p
     ca, cb, cc = cov2D[:, 0], cov2D[:, 1], cov2D[:, 2]
     det = ca * cc - cb * cb
     A, B, C = cc / det, -cb / det, ca / det
+    rows = {"rx": (t[:, 0] / t[:, 2]).detach().to(F64).numpy(), "ry": (t[:, 1] / t[:, 2]).detach().to(F64).numpy()}
+    # -- the compensation of the 0.3 dilation, from the nodes above
+    comp = None
+    if antialiased:
+        cv, d1 = cov, det
+        if cut == "compensation_scales":                       # (the same values along another path: ds'/ds = 1 inside c)
+            s_c = scales[idx] + (s - scales[idx]).detach()
+            Mc = R * (scale_modifier * s_c)[:, None, :]
+            cv = P @ (Mc @ Mc.transpose(1, 2)) @ P.transpose(1, 2)
+            d1 = (cv[:, 0, 0] + _f(0.3)) * (cv[:, 1, 1] + _f(0.3)) - cv[:, 0, 1] * cv[:, 0, 1]
+        ratio = (cv[:, 0, 0] * cv[:, 1, 1] - cv[:, 0, 1] * cv[:, 0, 1]) / d1
+        flows = torch.from_numpy(structure["flows"])[idx]
+        const = torch.where(torch.from_numpy(structure["floored"])[idx], torch.full_like(ratio, C_FLOORED), torch.ones_like(ratio))
+        comp = torch.where(flows, torch.sqrt(torch.where(flows, ratio, torch.ones_like(ratio))), const.detach())
+        if cut == "compensation":
+            comp = comp.detach()
+        o = o * comp
+        rows.update(r=ratio.detach().to(F64).numpy(), d1=d1.detach().to(F64).numpy())
     # -- the pixel centre
     Pm = leaf["proj"].reshape(4, 4).T
     h = m @ Pm[:, :3].T + Pm[:, 3]                            # (the activated mean's w is 1 under either profile)
@@ -229,9 +323,13 @@ def forward(leaf, structure, tan_fovx, tan_fovy, width, height, *, background, p
     bg = cst(background)
     color = torch.zeros((3, height, width), dtype=dt)
     dmap = torch.zeros((height, width), dtype=dt) if depth else None
+    feat = leaf["features"][idx] if "features" in leaf else None
+    fmap = torch.zeros((feat.shape[1], height, width), dtype=dt) if feat is not None else None
+    omap = torch.zeros((height, width), dtype=dt) if opacity else None
     finalT = torch.ones((height, width), dtype=dt)
     last = torch.zeros((height, width), dtype=torch.int64)
     near = torch.zeros((height, width), dtype=torch.bool)
+    blended = torch.zeros(n, dtype=torch.bool)
     for tyi in range(gy):
         for txi in range(gx):
             r0, r1 = (int(v) for v in structure["ranges"][tyi * gx + txi])
@@ -261,6 +359,8 @@ def forward(leaf, structure, tan_fovx, tan_fovy, width, height, *, background, p
                 nr = seen & ((power.abs() <= MARGIN) | close(a_raw, ALPHA_MIN)
                              | (~skip & (close(a_raw, ALPHA_MAX) | close(test, cutoff))))
                 lst = torch.where(on, order + 1, torch.zeros_like(order)).max(0).values if L else none
+            if L:
+                blended[ids] |= on.any(1)
             a = torch.where(on, alpha, torch.zeros_like(alpha))
             Tx = torch.cat([torch.ones((1, npx), dtype=dt), torch.cumprod(1.0 - a, 0)[:-1]], 0) if L else a
             wgt = a * Tx
@@ -270,14 +370,45 @@ def forward(leaf, structure, tan_fovx, tan_fovy, width, height, *, background, p
             color[:, ya:yb, xa:xb] = ((wgt.T @ rgb[ids]).T + bg[:, None] * Tb[None, :]).reshape(3, *shape)
             if depth:
                 dmap[ya:yb, xa:xb] = (wgt * dval[ids][:, None]).sum(0).reshape(shape)
+            if feat is not None:
+                wgt_f = wgt.detach() if cut == "feature_geometry" else wgt
+                fmap[:, ya:yb, xa:xb] = (wgt_f.T @ feat[ids]).T.reshape(-1, *shape)
+            if opacity:
+                omap[ya:yb, xa:xb] = (1.0 - (Tf.detach() if cut == "opacity_map" else Tf)).reshape(shape)
             finalT[ya:yb, xa:xb] = Tf.detach().reshape(shape)
             last[ya:yb, xa:xb] = lst.reshape(shape)
             near[ya:yb, xa:xb] = (nr.any(0) if L else torch.zeros(npx, dtype=torch.bool)).reshape(shape)
     aux.update(finalT=finalT.numpy(), last=last.numpy(), near=near.numpy(), visible=idx.numpy(),
                per_gaussian={"mean2D": mean2D, "cov2D": cov2D, "colors": rgb, "depths": dval},
+               feature_map=fmap, opacity_map=omap, compensation=comp, rows=rows, blended=blended.numpy(),
                cov3D=torch.stack([Sigma[:, 0, 0], Sigma[:, 0, 1], Sigma[:, 0, 2], Sigma[:, 1, 1], Sigma[:, 1, 2],
                                   Sigma[:, 2, 2]], 1).detach())
+    if antialiased:
+        aux["per_gaussian"]["opacities"] = o
     return color, dmap, aux
+
+
+def rows_near_a_threshold(aux, structure, tan_fovx, tan_fovy, filter_3d=None, antialiased=False):
+    """(near, differ): bool over aux["visible"] — a row decision of the compensation or of the smoothing within a relative
+    MARGIN of its threshold in float64, or taken otherwise in float64 than the float32 decision in `structure`. The
+    decisions: the two clamps, and with antialiased r = d0 / d1 against the floor and d1 (zero or not finite); with
+    filter_3d, f * f > 0. aux: of the uncut float64 forward()."""
+    vis, rows = aux["visible"], aux["rows"]
+    near, differ = np.zeros(vis.size, bool), np.zeros(vis.size, bool)
+    close = lambda v, thr: np.abs(v - thr) <= MARGIN * thr
+    for k, mask, tan in (("rx", "clx", tan_fovx), ("ry", "cly", tan_fovy)):
+        lim = float(np.float32(1.3) * np.float32(tan))
+        near |= close(np.abs(rows[k]), lim)
+        differ |= (np.abs(rows[k]) > lim) != structure[mask][vis]
+    if antialiased:
+        bad = ~np.isfinite(rows["d1"]) | (rows["d1"] == 0)
+        near |= ~bad & (close(rows["r"], FLOOR_R) | (np.abs(rows["d1"]) <= MARGIN))
+        differ |= (bad != structure["d1_bad"][vis]) | (~bad & (~(rows["r"] > FLOOR_R) != structure["floored"][vis]))
+    if filter_3d is not None:
+        f = np.asarray(filter_3d, np.float32).astype(np.float64)[vis]
+        differ |= ~(f * f > 0.0) != structure["identity"][vis]
+        near |= (f != 0) & (f * f <= float(np.finfo(np.float32).tiny) * (1.0 + MARGIN))
+    return near, differ
 
 
 def pixels_to_drop(aux, structure):
@@ -286,9 +417,11 @@ def pixels_to_drop(aux, structure):
     return aux["near"] | (aux["last"] != structure["nContrib"])
 
 
-def gradients(leaf, structure, cam, w, wd, drop, dtype=F64, **forward_options):
+def gradients(leaf, structure, cam, w, wd, drop, dtype=F64, wf=None, wa=None, **forward_options):
     """One step of the reference: forward(leaf, structure, <cam's tangents and size>, **forward_options), loss =
-    (w . color).sum() + (wd . depth).sum() with the dropped pixels' weights zero, and autograd. Returns (grads, color, depth,
+    (w . color).sum() + (wd . depth).sum() [+ (wf . feature_map).sum() + (wa . opacity_map).sum(): wf [C,H,W] with
+    leaf["features"], wa [H,W] with opacity=True; afterwards aux["feature_map"] / ["opacity_map"] are float64 numpy] with the
+    dropped pixels' weights zero, and autograd. A member of `leaf` that requires no gradient is a constant and has no entry. Returns (grads, color, depth,
     aux) — grads: float64 numpy, keyed by the leaves' names, by "means3D", "scales", "rotations", "opacities" (the gradients
     w.r.t. the activated arrays) and by "per_gaussian.mean2D" etc. (w.r.t. aux["per_gaussian"], rows in the order of
     aux["visible"]); zeros where the loss does not depend on the tensor."""
@@ -297,8 +430,13 @@ def gradients(leaf, structure, cam, w, wd, drop, dtype=F64, **forward_options):
     keep = torch.from_numpy(~drop)
     wt, wdt = torch.from_numpy(w).to(dtype) * keep, torch.from_numpy(wd).to(dtype) * keep
     loss = (wt * color).sum() + ((wdt * dmap).sum() if depth else 0.0)
-    names = list(leaf) + ["means3D", "scales", "rotations", "opacities"]
-    tensors = [leaf[k] for k in leaf] + [aux[k] for k in names[len(leaf):]]
+    if wf is not None:
+        loss = loss + (torch.from_numpy(wf).to(dtype) * keep * aux["feature_map"]).sum()
+    if wa is not None:
+        loss = loss + (torch.from_numpy(wa).to(dtype) * keep * aux["opacity_map"]).sum()
+    names = [k for k in leaf if leaf[k].requires_grad]
+    tensors = [leaf[k] for k in names] + [aux[k] for k in ("means3D", "scales", "rotations", "opacities")]
+    names = names + ["means3D", "scales", "rotations", "opacities"]
     for k, t in aux["per_gaussian"].items():
         if t is not None and t.requires_grad:
             names.append("per_gaussian." + k)
@@ -306,4 +444,7 @@ def gradients(leaf, structure, cam, w, wd, drop, dtype=F64, **forward_options):
     got = torch.autograd.grad(loss, tensors, allow_unused=True)
     grads = {k: (g.detach().to(F64).numpy() if g is not None else np.zeros(tuple(t.shape)))
              for k, g, t in zip(names, got, tensors)}
+    for k in ("feature_map", "opacity_map"):
+        if aux[k] is not None:
+            aux[k] = aux[k].detach().to(F64).numpy()
     return grads, color.detach().to(F64).numpy(), (dmap.detach().to(F64).numpy() if depth else None), aux

@@ -1,5 +1,8 @@
 """The frames of the training-step tests (tests/test_step_autograd_cpu.py, tests/test_gpu_step_autograd.py): the cases, the
-scene in raw parameters, the camera, the loss weights, and the reference step of a case (tests/step_autograd_ref.py)."""
+scene in raw parameters, the camera, the loss weights, and the reference step of a case (tests/step_autograd_ref.py). And,
+in a second table (FULL_CASES, full_*), the frames of tests/test_step_full_cpu.py and tests/test_gpu_step_full.py: the same
+pose and size with the 3D filter, the opacity compensation, a feature map and the opacity map, on a scene derived from
+raw_scene without altering it."""
 from __future__ import annotations
 
 import functools
@@ -86,6 +89,153 @@ def raw_scene(profile, seed=None):
             raw["shs"][r, r % 3] = -2.5
     raw["colors"] = rng.uniform(0.0, 1.0, (N, 3)).astype(np.float32)          # (the colours of the colors_precomp case)
     return raw
+
+
+# ---- the frames with the filter, the compensation, the feature map and the opacity map (tests/test_step_full_cpu.py,
+# tests/test_gpu_step_full.py). name -> the options of the case; `constant`: the camera tensors that are no leaves (the library
+# refuses a view matrix that requires a gradient under antialiased=True); colour=False: the colour's weight is all zeros
+def _full(profile, deg, depth, mod=1.0, kx=1.0, filt=False, antialiased=False, channels=0, opacity=False, colour=True):
+    return dict(profile=profile, sh_degree=deg, depth=depth, scale_modifier=mod, kx=kx, filter=filt, antialiased=antialiased,
+                channels=channels, opacity=opacity, colour=colour, constant=("view",) if antialiased else ())
+
+
+FULL_CASES = {
+    "full-inria": _full("inria", 3, True, filt=True, antialiased=True, channels=5, opacity=True),
+    "full-gscuda-m2": _full("gscuda", 0, "inverse", mod=2.0, filt=True, antialiased=True, channels=3, opacity=True),
+    "filter-features-kx": _full("inria", 2, "inverse", kx=1.7, filt=True, channels=5, opacity=True),
+    "antialias-alone": _full("gscuda", 0, True, antialiased=True),
+    "filter-alone": _full("inria", 1, True, filt=True),
+    "features-alone": _full("gscuda", 0, False, channels=1, colour=False),
+}
+# The scene's sizes, in world units (a pixel is about 0.15 at the scene's depth). They are chosen so that the Gaussians whose
+# gradients are the largest of the frame are the ones on which the filter and the compensation both matter — splats of about a
+# pixel with a filter of their own size: a bound is a share of an array's LARGEST entry, and a cut that only moves the gradients
+# of small faint splats beside large opaque ones is not seen (tests/test_step_full_cpu.py, the cuts; raw_scene's own sizes show
+# the cut of the smoothed scales inside c by one bound, these by more than a hundred).
+FILTER_SCALE = 1.7            # what the training cameras' filter is scaled by: about 0.1, two thirds of a pixel
+LARGE_BAND = (0.35, 0.5)      # every other ordinary splat: two to three pixels, hardly compensated ...
+LARGE_OPACITY = 0.05          # ... and its opacity multiplied by this, so that it does not set the largest entries
+SMALL_BAND = (0.05, 0.12)     # the others: below a pixel, c and the filter's coefficient well below 0.9
+STACK_TOP, STACK_SHRINK = 0.08, 0.4     # the two stacks: their first two splats' scale, and the factor on the other five
+WIDE_OPACITY = 0.04           # the factor on the opacity of the wide ones (scales of 2 to 8)
+IDENTITY_FROM = 7             # rows 7, 17, ... have filter value 0: only two of them lie behind the camera
+
+
+def full_camera_of(case):
+    from helpers import posed_camera
+    return posed_camera(W, H, kx=FULL_CASES[case]["kx"], **P1)
+
+
+@functools.lru_cache(maxsize=None)
+def full_scene(case):
+    """raw_scene(profile), copied, with its ordinary splats (not the stacks, the ones behind the camera or the wide ones)
+    brought to the frame's resolution: every other one doubled and clipped into LARGE_BAND, the others clipped into SMALL_BAND
+    — but every seventh of those left as it is, far below a pixel. The stacks shrunk to a pixel's size (STACK_TOP,
+    STACK_SHRINK), the large and the wide ones fainter (LARGE_OPACITY, WIDE_OPACITY). Under a scale_modifier k every scale is divided by k: the rasterizer sees the same sizes again, and the
+    filter, which the modifier multiplies too, is made for them (filter_values). Plus "features" [N,5], standard normal (a
+    case of C channels reads the first C columns)."""
+    c = FULL_CASES[case]
+    raw = {k: v.copy() for k, v in raw_scene(c["profile"]).items()}
+    special = np.zeros(N, bool)
+    for a, b in ((10, 17), (80, 87), (20, 32), (100, 112), (140, 148)):
+        special[a:b] = True
+    rows = np.nonzero(~special)[0]
+    large, small = rows[::2], np.setdiff1d(rows[1::2], rows[1::2][::7])
+    ln = lambda v: np.float32(np.log(v))
+    raw["log_scale"][large] = np.clip(raw["log_scale"][large] + ln(2.0), ln(LARGE_BAND[0]), ln(LARGE_BAND[1]))
+    raw["log_scale"][small] = np.clip(raw["log_scale"][small], ln(SMALL_BAND[0]), ln(SMALL_BAND[1]))
+    raw["log_scale"][[10, 11, 80, 81]] = ln(STACK_TOP)
+    for a in (12, 82):
+        raw["log_scale"][a:a + 5] += ln(STACK_SHRINK)
+    raw["log_scale"] -= ln(c["scale_modifier"])
+    for rows_, factor in ((np.arange(140, 148), WIDE_OPACITY), (large, LARGE_OPACITY)):
+        o = 1.0 / (1.0 + np.exp(-raw["opacity_logit"][rows_].astype(np.float64))) * factor
+        raw["opacity_logit"][rows_] = np.log(o / (1.0 - o)).astype(np.float32)
+    raw["features"] = np.random.default_rng(23).normal(size=(N, 5)).astype(np.float32)
+    return raw
+
+
+@functools.lru_cache(maxsize=None)
+def filter_values(case):
+    """The scene's filter as tests/test_gpu_filter3d.py makes it: observe and finalize (the float32 restatement) of five
+    training cameras at this frame's size, scaled by FILTER_SCALE (over the case's scale_modifier, as the scene's scales
+    are), every tenth value zero — from row IDENTITY_FROM on, so that few of the IDENTITY rows are among the ones raw_scene
+    puts behind the camera (float32 [N]). None for a case without the filter."""
+    import filter3d_ref
+    from gsrast_amd import filter3d
+    if not FULL_CASES[case]["filter"]:
+        return None
+    rec, max_focal = filter3d.camera_records(filter3d_ref.orbit_cameras(5, width=W, height=H, radius=5.0, seed=6, arc=1.0))
+    v = filter3d_ref.finalize_f32(filter3d_ref.observe_f32(full_scene(case)["xyz"], rec), max_focal)
+    v = (v * np.float32(FILTER_SCALE / FULL_CASES[case]["scale_modifier"])).astype(np.float32)
+    v[IDENTITY_FROM::10] = 0.0
+    v.setflags(write=False)
+    return v
+
+
+def full_weights(case, seed=29):
+    """(w [3,H,W], wd [H,W], wf [C,H,W] or None, wa [H,W] or None), float32: weights() for colour and depth (the colour's all
+    zeros where the case says so), white noise on the feature map, a smooth field of one sign on the opacity map."""
+    c = FULL_CASES[case]
+    w, wd = weights()
+    rng = np.random.default_rng(seed)
+    wf = rng.normal(size=(5, H, W)).astype(np.float32)[:c["channels"]] if c["channels"] else None
+    wa = (0.5 + 0.2 * rng.normal(size=(H, W))).astype(np.float32) if c["opacity"] else None
+    return (w if c["colour"] else np.zeros_like(w)), wd, wf, wa
+
+
+def full_row_arrays(case, scales, opacities, means3D, rotations, cam, smoothed=None):
+    """The float32 arrays the rasterizer is handed and the row decisions on the way, from the float32 ACTIVATED arrays (the
+    restatement's on the CPU, the device's own on the GPU): filter3d_ref.forward_f32, then antialias_ref.compensation_f32.
+    smoothed: (scales' [N,4], opacities' [N]) where the caller has the smoothed arrays themselves (the device's): the
+    compensation's decisions are then taken on those. Returns dict: scales [N,4], opacities [N] (what gsr_forward reads),
+    identity (or None), masks (or None), smoothed (forward_f32's dict or None)."""
+    import antialias_ref
+    import filter3d_ref
+    c = FULL_CASES[case]
+    out = dict(scales=np.asarray(scales, np.float32), opacities=np.asarray(opacities, np.float32), identity=None, masks=None, smoothed=None)
+    if c["filter"]:
+        sm = filter3d_ref.forward_f32(out["scales"], out["opacities"], filter_values(case))
+        out.update(scales=sm["scales_out"], opacities=sm["opacities_out"], identity=sm["identity"], smoothed=sm)
+        if smoothed is not None:
+            out.update(scales=np.asarray(smoothed[0], np.float32), opacities=np.asarray(smoothed[1], np.float32))
+    if c["antialiased"]:
+        m = antialias_ref.compensation_f32(means3D, out["scales"], rotations, out["opacities"], cam.view, cam.proj, cam.tan_fovx,
+                                           cam.tan_fovy, W, H, c["profile"], c["scale_modifier"])
+        out.update(opacities=m["o_out"], masks=m)
+    return out
+
+
+def full_structure_of(case, cam, rows, radii, ranges, values, n_contrib, clamped=None):
+    """The structure of a FULL_CASES frame: structure_of plus the row decisions of full_row_arrays' result `rows`."""
+    return R.with_decisions(structure_of(full_scene(case), cam, radii, ranges, values, n_contrib, clamped),
+                            rows["masks"], rows["identity"])
+
+
+def full_forward_options(case, cut=None, **more):
+    c = FULL_CASES[case]
+    return dict(background=BG, profile=c["profile"], sh_degree=c["sh_degree"], scale_modifier=c["scale_modifier"], depth=c["depth"],
+                cut=cut, filter_3d=filter_values(case), antialiased=c["antialiased"],
+                opacity=c["opacity"], **more)
+
+
+def full_leaves(case, dtype=R.F64):
+    c = FULL_CASES[case]
+    raw = full_scene(case)
+    return R.leaves(raw, full_camera_of(case), dtype=dtype, features=raw["features"][:, :c["channels"]] if c["channels"] else None,
+                    constant=c["constant"])
+
+
+def full_reference_step(case, structure, cut=None, dtype=R.F64, drop=None):
+    """(grads, color, depth, aux, drop) of a FULL_CASES step on `structure`, as reference_step gives them for CASES."""
+    cam = full_camera_of(case)
+    w, wd, wf, wa = full_weights(case)
+    if drop is None:
+        none = np.zeros((H, W), bool)
+        aux = R.gradients(full_leaves(case), structure, cam, w, wd, none, wf=wf, wa=wa, **full_forward_options(case))[3]
+        drop = R.pixels_to_drop(aux, structure)
+    return R.gradients(full_leaves(case, dtype), structure, cam, w, wd, drop, dtype=dtype, wf=wf, wa=wa,
+                       **full_forward_options(case, cut)) + (drop,)
 
 
 def weights(seed=17):
