@@ -1,6 +1,6 @@
 """ctypes binding of include/gsrast_amd.h, include/gsrast_amd_init.h, include/gsrast_amd_opacity.h, include/gsrast_amd_mcmc.h,
-include/gsrast_amd_contrib.h, include/gsrast_amd_antialias.h, include/gsrast_amd_filter3d.h, include/gsrast_amd_absgrad.h and
-include/gsrast_amd_features.h (the C ABI of libgsrast_amd.so).
+include/gsrast_amd_contrib.h, include/gsrast_amd_antialias.h, include/gsrast_amd_filter3d.h, include/gsrast_amd_absgrad.h,
+include/gsrast_amd_features.h and include/gsrast_amd_distortion.h (the C ABI of libgsrast_amd.so).
 
 There is no fallback: if the HIP library has not been built, importing the product path
 raises. Field order and types below mirror the header exactly.
@@ -403,6 +403,24 @@ FEATURES_SIGNATURES = {
     "gsr_features_backward": (C.c_int, [C.POINTER(FeaturesArgs)]),
 }
 
+# include/gsrast_amd_distortion.h (the depth distortion map of a drawn frame, forward and backward), in the same shape, with its own symbol test.
+class DistortionArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32),
+                ("num_gaussians", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("power", C.c_int32),
+                ("means2D", C.c_void_p), ("conic_opacity", C.c_void_p), ("ranges", C.c_void_p), ("n_contrib", C.c_void_p),
+                ("final_t", C.c_void_p), ("point_list", C.c_void_p), ("receipt", ForwardReceipt),
+                ("values", C.c_void_p), ("out", C.c_void_p), ("moments", C.c_void_p),
+                ("dL_dout", C.c_void_p), ("dL_dvalues", C.c_void_p), ("value_sums_f64", C.c_void_p),
+                ("geometry_sums_f64", C.c_void_p),
+                ("tile_row_begin", C.c_int32), ("tile_row_end", C.c_int32), ("stream", C.c_void_p), ("stage_ms", C.c_float)]
+
+
+DISTORTION_SIGNATURES = {
+    "gsr_distortion_temp_bytes": (C.c_size_t, [C.c_int32]),
+    "gsr_distortion_forward": (C.c_int, [C.POINTER(DistortionArgs)]),
+    "gsr_distortion_backward": (C.c_int, [C.POINTER(DistortionArgs)]),
+}
+
 _lib = None
 
 
@@ -430,7 +448,7 @@ def lib() -> C.CDLL:
         for name, (res, args) in (list(SIGNATURES.items()) + list(INIT_SIGNATURES.items()) + list(OPACITY_SIGNATURES.items())
                                   + list(MCMC_SIGNATURES.items()) + list(CONTRIB_SIGNATURES.items()) + list(ANTIALIAS_SIGNATURES.items())
                                   + list(FILTER3D_SIGNATURES.items()) + list(ABSGRAD_SIGNATURES.items())
-                                  + list(FEATURES_SIGNATURES.items())):
+                                  + list(FEATURES_SIGNATURES.items()) + list(DISTORTION_SIGNATURES.items())):
             fn = getattr(L, name, None)
             if fn is None and _TAG:
                 continue                       # (a tagged A/B build of an older tree may lack the newest entry points)

@@ -51,7 +51,8 @@ class FrameSlot(RadiiSlot):
     gradients, and leaves abs_dL_dmean2D [N,2] (AbsGS's sum of absolute per-pixel shares, a new tensor per frame) here — what
     DensityStats.update(absgrad=True) takes. With the default nothing more is launched or allocated.
     With rasterize / render(features=...) dL_dmean2D includes the feature map's term (it is the gradient of the whole loss);
-    abs_dL_dmean2D does not: it stays the score of the colour, depth and opacity terms."""
+    abs_dL_dmean2D does not: it stays the score of the colour, depth and opacity terms. The same holds for the distortion
+    map's term of rasterize / render(distortion=...)."""
 
     def __init__(self, absgrad: bool = False):
         super().__init__()
@@ -147,7 +148,7 @@ STALE_MESSAGE = ("this rasterizer has drawn another frame, or was given another 
 
 class _Rasterize(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, features=None):
+    def forward(ctx, rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, features=None, distortion=None):
         n, dev = int(means3D.shape[0]), rast.device
         means3D, scales, rotations = _f32c(means3D, (n, 4), "means3D"), _f32c(scales, (n, 4), "scales"), _f32c(rotations, (n, 4), "rotations")
         opacities, shs = _f32c(opacities, (n,), "opacities"), _f32c(shs, (n, 48), "shs")
@@ -169,36 +170,43 @@ class _Rasterize(torch.autograd.Function):
                 raise ValueError(f"features: expected float32 [{n}, C] on {dev}, got {features.dtype} {tuple(features.shape)} on {features.device}")
             features = features.contiguous()
             feature_map = rast.render_features(features, sync=False)
+        distortion_map = None
+        if distortion is not None:                            # (likewise: gsr_distortion_forward; the moments go with this graph)
+            if distortion.dtype != F32 or tuple(distortion.shape) != (n,) or distortion.device != dev:
+                raise ValueError(f"distortion: expected float32 [{n}] on {dev}, got {distortion.dtype} {tuple(distortion.shape)} on {distortion.device}")
+            distortion = distortion.contiguous()
+            distortion_map = rast.render_distortion(distortion, power=opts["distortion_power"], sync=False)
+            ctx.distortion_moments = rast._distortion_moments[2]
         if opts["radii_slot"] is not None:
             opts["radii_slot"].radii = rast.map_geometry_state()["radii"].clone()
         ctx.rast, ctx.opts = rast, opts
         ctx.receipt, ctx.epoch = rast.last_receipt.copy(), rast._state_epoch
         ctx.view_shapes = (view.shape, proj.shape, cam_pos.shape)
         ctx.has_colors = colors_precomp is not None
-        ctx.has_features = features is not None
-        if features is None:
-            ctx.save_for_backward(means3D, scales, rotations, opacities, shs)      # (a write to one of them before backward() is reported)
-        else:
-            ctx.save_for_backward(means3D, scales, rotations, opacities, shs, features)
+        ctx.has_features, ctx.has_distortion = features is not None, distortion is not None
+        # (a write to one of them before backward() is reported)
+        ctx.save_for_backward(means3D, scales, rotations, opacities, shs, *(t for t in (features, distortion) if t is not None))
         if not opts["opacity_grad"]:
             ctx.mark_non_differentiable(opacity_map)
-        if opts["opacity_grad"] or features is not None:
+        if opts["opacity_grad"] or features is not None or distortion is not None:
             ctx.set_materialize_grads(False)                  # (a map the loss does not use arrives as None, not as zeros to run through)
-        return into["out_color"], into.get("out_depth"), opacity_map, feature_map
+        return into["out_color"], into.get("out_depth"), opacity_map, feature_map, distortion_map
 
     @staticmethod
-    def backward(ctx, g_color, g_depth, g_opacity_map, g_feature_map=None):
+    def backward(ctx, g_color, g_depth, g_opacity_map, g_feature_map=None, g_distortion_map=None):
         rast, opts = ctx.rast, ctx.opts
         if rast._state_epoch != ctx.epoch:
             raise RuntimeError(STALE_MESSAGE)
         saved = ctx.saved_tensors                             # (raises if one was modified in place)
-        need = dict(zip(("means3D", "scales", "rotations", "opacities", "shs", "view", "proj", "cam_pos", "colors_precomp", "features"),
+        need = dict(zip(("means3D", "scales", "rotations", "opacities", "shs", "view", "proj", "cam_pos", "colors_precomp", "features", "distortion"),
                         ctx.needs_input_grad[2:]))
         n, dev = rast.num_gaussians, rast.device
         g_alpha = g_opacity_map if opts["opacity_grad"] else None
         feature_term = (saved[5], g_feature_map) if (ctx.has_features and g_feature_map is not None) else None
-        if g_color is None and g_depth is None and g_alpha is None and feature_term is None:
-            return (None,) * 12
+        distortion_term = ((saved[6 if ctx.has_features else 5], g_distortion_map, opts["distortion_power"], ctx.distortion_moments)
+                           if (ctx.has_distortion and g_distortion_map is not None) else None)
+        if g_color is None and g_depth is None and g_alpha is None and feature_term is None and distortion_term is None:
+            return (None,) * 13
         if g_color is None:
             g_color = torch.zeros((3, rast.height, rast.width), dtype=F32, device=dev)
         new = lambda *shape: torch.empty(shape, dtype=F32, device=dev)
@@ -225,14 +233,17 @@ class _Rasterize(torch.autograd.Function):
             # nothing but the features requires a gradient: the frozen-geometry pass, no chain
             d_feat = (rast.features_backward(*feature_term, receipt=ctx.receipt, sync=False)
                       if (feature_term is not None and need["features"]) else None)
-            return (None,) * 11 + (d_feat,)
+            d_val = (rast.distortion_backward(distortion_term[0], distortion_term[1], power=distortion_term[2], moments=distortion_term[3],
+                                              receipt=ctx.receipt, sync=False)
+                     if (distortion_term is not None and need["distortion"]) else None)
+            return (None,) * 11 + (d_feat, d_val)
         frame_slot = opts["radii_slot"] if isinstance(opts["radii_slot"], FrameSlot) else None
         if frame_slot is not None:
             into["dL_dmean2D"] = new(n, 2)
         res = rast.backward(g_color, semantics=opts["semantics"], sh_degree=opts["sh_degree"], scale_modifier=opts["scale_modifier"],
                             receipt=ctx.receipt, wide_sums=True, dL_ddepth=g_depth if opts["depth"] else None,
                             depth=opts["depth"] or None, camera=camera, into=into, sync=False, dL_dalpha=g_alpha,
-                            features=feature_term)
+                            features=feature_term, distortion=distortion_term)
         if frame_slot is not None:
             frame_slot.dL_dmean2D = res["dL_dmean2D"]
             if frame_slot.absgrad:
@@ -243,13 +254,15 @@ class _Rasterize(torch.autograd.Function):
         return (None, None, g("dL_dmeans3D"), g("dL_dscales", need["scales"]), g("dL_drotations"),
                 res["dL_dconic_opacity"][:, 3] if need["opacities"] else None, g("dL_dshs", need["shs"]),
                 cam_g("dL_dview_matrix", "view", ctx.view_shapes[0]), cam_g("dL_dproj_matrix", "proj", ctx.view_shapes[1]),
-                cam_g("dL_dcam_pos", "cam_pos", ctx.view_shapes[2]), g("dL_dcolors"), g("dL_dfeatures", need["features"]))
+                cam_g("dL_dcam_pos", "cam_pos", ctx.view_shapes[2]), g("dL_dcolors"), g("dL_dfeatures", need["features"]),
+                g("dL_dvalues", need["distortion"]))
 
 
 def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, tan_fov, *,
               semantics: str = "gscuda", sh_degree: int = 3, scale_modifier: float = 1.0, depth: "bool | str" = False,
               colors_precomp: "torch.Tensor | None" = None, radii_slot: "RadiiSlot | None" = None, opacity_grad: bool = False,
-              antialiased: bool = False, features: "torch.Tensor | None" = None, **draw_options):
+              antialiased: bool = False, features: "torch.Tensor | None" = None, distortion: "torch.Tensor | str | None" = None,
+              distortion_power: int = 2, **draw_options):
     """One differentiable frame: SplatRasterizer.draw forward, .backward / .camera_backward backward.
 
     Tensors in the library's layouts, float32 on rast.device: means3D / scales / rotations [N,4], opacities [N], shs [N,48]
@@ -284,18 +297,36 @@ def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs,
     with opacity_grad=True if that term should reach the geometry. Its incoming gradient enters the same backward call as
     colour, depth and opacity (SplatRasterizer.backward(features=...)): the camera gradients, FrameSlot.dL_dmean2D,
     antialiased and the 3D filter all see the feature term. FrameSlot(absgrad=True)'s abs_dL_dmean2D does NOT include it.
-    Without `features` the 3-tuple and everything about the call stay exactly as they were."""
+    Without `features` the 3-tuple and everything about the call stay exactly as they were.
+
+    distortion: a float32 [N] tensor on rast.device, one scalar m per Gaussian, which may require a gradient — or "depth": the
+    view-space z of means3D, formed here with torch operations from means3D and view, so that its gradient flows back through
+    torch to both. The distortion map [H,W] = sum_i sum_j w_i w_j |m_i - m_j|^distortion_power, w = alpha T of this frame
+    (SplatRasterizer.render_distortion; the loss of Mip-NeRF 360 as 2DGS uses it; power 1 is signed in list order, which is the
+    absolute form for the view depth), is then appended as the LAST element of the returned tuple: (color, depth, opacity_map[,
+    feature_map], distortion_map). Its incoming gradient enters the same backward call as the other terms
+    (SplatRasterizer.backward(distortion=...)), so the camera gradients, FrameSlot.dL_dmean2D, antialiased and the 3D filter
+    all see it. FrameSlot(absgrad=True)'s abs_dL_dmean2D does NOT include it. Without `distortion` every return value and every
+    launch stay as they were."""
     assert set(draw_options) <= set(_DRAW_OPTIONS), sorted(draw_options)
     assert depth in (False, True, "inverse"), depth
     opts = {"tan_fov": (float(tan_fov[0]), float(tan_fov[1])), "semantics": semantics, "sh_degree": int(sh_degree),
             "scale_modifier": float(scale_modifier), "depth": depth, "radii_slot": radii_slot, "draw": dict(draw_options),
-            "opacity_grad": bool(opacity_grad)}
+            "opacity_grad": bool(opacity_grad), "distortion_power": int(distortion_power)}
+    assert distortion_power in (1, 2), ("distortion_power", distortion_power)
     if antialiased:
         opacities = _antialias.compensate(means3D, scales, rotations, opacities, view, opts["tan_fov"], rast.width, rast.height,
                                           semantics=semantics, scale_modifier=opts["scale_modifier"], proj=proj, radii_slot=radii_slot)
-    if features is None:
-        return _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, None)[:3]
-    return _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, features)
+    if distortion is None:
+        if features is None:
+            return _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, None, None)[:3]
+        return _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, features, None)[:4]
+    if isinstance(distortion, str):
+        assert distortion == "depth", distortion
+        v = view.reshape(-1)                                  # (column-major: row 2 of the view matrix is elements 2, 6, 10, 14)
+        distortion = (means3D[:, 0] * v[2] + means3D[:, 1] * v[6]) + (means3D[:, 2] * v[10] + v[14])
+    out = _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, features, distortion)
+    return out[:3] + ((out[3],) if features is not None else ()) + (out[4],)
 
 
 def _rest_to_coefficient_major(sh: np.ndarray) -> np.ndarray:
@@ -412,7 +443,8 @@ def _camera_tensors(camera, dev):
 def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: str = "gscuda", sh_degree: int = 3,
            scale_modifier: float = 1.0, depth: "bool | str" = False, radii_slot: "RadiiSlot | None" = None,
            opacity_grad: bool = False, antialiased: bool = False, filter_3d: "torch.Tensor | None" = None,
-           features: "torch.Tensor | None" = None, **draw_options):
+           features: "torch.Tensor | None" = None, distortion: "torch.Tensor | str | None" = None, distortion_power: int = 2,
+           **draw_options):
     """`activate` then `rasterize`: (color [3,H,W], depth [H,W] or None, opacity_map [H,W]) of `params` seen from `camera`
     — a Camera (its matrices are uploaded once per device and kept with it; write to a Camera's arrays and it must be a new
     object) or a tuple (view, proj, cam_pos, tan_fovx, tan_fovy) whose first three are device tensors, which may require
@@ -428,7 +460,9 @@ def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: 
     the rasterizer and, with antialiased=True, the 2D compensation, as in Mip-Splatting — and its backward takes the
     gradients back to the raw parameters. Another length, dtype or device is a ValueError.
     features: float32 [N,C] on the rasterizer's device (a Parameter of the caller's, say): the result is then the 4-tuple
-    (color, depth, opacity_map, feature_map [C,H,W]) of `rasterize`, the feature map over a zero background."""
+    (color, depth, opacity_map, feature_map [C,H,W]) of `rasterize`, the feature map over a zero background.
+    distortion, distortion_power: a float32 [N] tensor or "depth" (the view-space z): the distortion map [H,W] of `rasterize` is
+    appended as the last element of the result."""
     if semantics == "inria" and sh_degree >= 1:
         assert params.sh_layout == "coefficient_major", 'semantics="inria" reads shs as [N][16][3]: sh_layout="coefficient_major"'
     slot = radii_slot if radii_slot is not None else RadiiSlot()
@@ -438,4 +472,5 @@ def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: 
     view, proj, cam_pos, tan_fovx, tan_fovy = _camera_tensors(camera, rast.device)
     return rasterize(rast, means3D, scales, rotations, opacities, params.shs, view, proj, cam_pos, (tan_fovx, tan_fovy),
                      semantics=semantics, sh_degree=sh_degree, scale_modifier=scale_modifier, depth=depth, radii_slot=slot,
-                     opacity_grad=opacity_grad, antialiased=antialiased, features=features, **draw_options)
+                     opacity_grad=opacity_grad, antialiased=antialiased, features=features, distortion=distortion,
+                     distortion_power=distortion_power, **draw_options)

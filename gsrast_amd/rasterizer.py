@@ -141,6 +141,9 @@ class SplatRasterizer:
         self.last_camera_ms: "float | None" = None     # of the last camera_backward(profile=True)
         self.last_absgrad_ms: "float | None" = None    # of the last absgrad(profile=True)
         self.last_features_ms: "float | None" = None   # of the last render_features / features_backward / backward(features=...) with profile=True
+        self.last_distortion_ms: "float | None" = None # of the last render_distortion / distortion_backward / backward(distortion=...) with profile=True
+        # the moments of the last render_distortion: (that frame's receipt serial, the power, [3,H,W]) — what its backward reads
+        self._distortion_moments: "tuple[int | None, int, torch.Tensor | None]" = (None, 0, None)
         self.rects: torch.Tensor | None = None
         self._bw = BackwardBuffers(self.device)
         # which colours a draw() composited (backward() reads the same ones): (that call's receipt serial, tensor or None)
@@ -445,7 +448,8 @@ class SplatRasterizer:
                  sh_degree: int = 3, receipt: "_capi.ForwardReceipt | None | bool" = None, wide_sums: bool = True,
                  outputs: "tuple[str, ...] | None" = None, dL_ddepth: "torch.Tensor | None" = None,
                  depth: "bool | str | None" = None, camera: bool = False, into: "dict | None" = None,
-                 sync: bool = True, dL_dalpha: "torch.Tensor | None" = None, features: "tuple | None" = None) -> dict:
+                 sync: bool = True, dL_dalpha: "torch.Tensor | None" = None, features: "tuple | None" = None,
+                 distortion: "tuple | None" = None) -> dict:
         """Gradients of sum(dL_dout * out_color) of the LAST draw() through gsr_backward; `semantics` / `sh_degree`
         must be those of that draw(). receipt: the gsr_forward_receipt of the draw() this is the backward of (default:
         this object's last draw(); any host thread may call); False = none, the reference's contract only (sorted lists
@@ -482,9 +486,21 @@ class SplatRasterizer:
         sum(dL_dfeature_map * render_features(F, background=...)). gsr_features_backward runs first, on the same stream, and adds
         the feature term's geometry sums into this object's sums_f64 scratch; gsr_backward / gsr_backward_alpha then chains the
         total, so every output (the camera's included) holds the feature term, and the result also holds dL_dfeatures [N,C], a
-        new tensor. On an error both scratches are dropped. Without `features` the call is what it was."""
+        new tensor. On an error both scratches are dropped. Without `features` the call is what it was.
+        distortion (needs wide_sums and a receipt): (values [N], dL_ddistortion_map [H,W][, power = 2[, moments]]) — the loss gains
+        sum(dL_ddistortion_map * render_distortion(values, power=power)); the moments are those that call kept (or the [3,H,W]
+        tensor given), refused when they are of another frame or power. gsr_distortion_backward runs in front of gsr_backward,
+        after the feature pass if both are given, and adds its geometry sums into the same sums_f64 scratch, so every output holds
+        the term; the result also holds dL_dvalues [N], a new tensor. Without `distortion` the call is what it was."""
         n, dev = self.num_gaussians, self.device
         rcpt = self.last_receipt if receipt is None else (None if receipt is False else receipt)
+        if distortion is not None:               # (checked before the first copy or launch of this call)
+            assert wide_sums, "distortion= needs wide_sums: the distortion term reaches the chain through the sums_f64 scratch"
+            assert rcpt is not None, "distortion= needs the receipt of a draw()"
+            assert isinstance(distortion, (tuple, list)) and len(distortion) in (2, 3, 4), "distortion=(values, dL_ddistortion_map[, power[, moments]])"
+            distortion_power = int(distortion[2]) if len(distortion) > 2 else 2
+            assert distortion_power in (1, 2), ("power", distortion_power)
+            distortion_moments = self._distortion_moments_of(rcpt, distortion_power, distortion[3] if len(distortion) > 3 else None)
         if features is not None:                 # (checked before the first copy or launch of this call)
             assert wide_sums, "features= needs wide_sums: the feature term reaches the chain through the sums_f64 scratch"
             assert rcpt is not None, "features= needs the receipt of a draw()"
@@ -529,12 +545,19 @@ class SplatRasterizer:
         if features is not None:
             feature_call, feature_keep = self._features_call(rcpt, features[0], features[2] if len(features) > 2 else None,
                                                              dL_dout=features[1], profile=profile)
+        distortion_call = None
+        if distortion is not None:
+            distortion_call, distortion_keep = self._distortion_call(rcpt, distortion[0], distortion_power, distortion_moments,
+                                                                     dL_dout=distortion[1], tile_rows=tile_rows, profile=profile)
         try:
             if feature_call is not None:        # its geometry sums go where gsr_backward's go: that call chains the total
                 feature_call.geometry_sums_f64 = a.sums_f64
                 if tile_rows is not None:
                     feature_call.tile_row_begin, feature_call.tile_row_end = int(tile_rows[0]), int(tile_rows[1])
                 _capi.call("gsr_features_backward", C.byref(feature_call), device=dev)
+            if distortion_call is not None:     # (likewise; both passes may seed the same sums)
+                distortion_call.geometry_sums_f64 = a.sums_f64
+                _capi.call("gsr_distortion_backward", C.byref(distortion_call), device=dev)
             if dL_dalpha is None:
                 _capi.call("gsr_backward", C.byref(a), device=dev)
             else:
@@ -545,18 +568,23 @@ class SplatRasterizer:
                 self._bw.scratch.pop("sums_f64", None)
                 self._bw.scratch.pop("depth_sums_f64", None)
             self._bw.scratch.pop("feature_sums_f64", None)
+            self._bw.scratch.pop("distortion_sums_f64", None)
             raise
         self.last_backward_ms = (float(a.stage_ms[0]), float(a.stage_ms[1])) if profile else ()
         if feature_call is not None:
             self.last_features_ms = float(feature_call.stage_ms) if profile else None
             arrays["dL_dfeatures"] = feature_keep[-1]
+        if distortion_call is not None:
+            self.last_distortion_ms = float(distortion_call.stage_ms) if profile else None
+            arrays["dL_dvalues"] = distortion_keep[-1]
         if camera:
             arrays.update(self.camera_backward({k: arrays[k] for k in plan.camera_inputs}, semantics=semantics,
                                                sh_degree=sh_degree, shs_colour="dL_dcolors" in plan.camera_inputs, depth=mode,
                                                profile=profile, sync=False, into=into["camera"] if plan.camera_into else None))
         if sync:
             torch.cuda.current_stream(dev).synchronize()
-        return {k: arrays[k] for k in tuple(plan.result) + (("dL_dfeatures",) if feature_call is not None else ())}
+        return {k: arrays[k] for k in tuple(plan.result) + (("dL_dfeatures",) if feature_call is not None else ())
+                + (("dL_dvalues",) if distortion_call is not None else ())}
 
     # -- N-channel feature maps (include/gsrast_amd_features.h) -------------------------------
     def _features_call(self, rcpt: _capi.ForwardReceipt, features: torch.Tensor, background, *, out: "torch.Tensor | None" = None,
@@ -654,6 +682,120 @@ class SplatRasterizer:
             self._bw.scratch.pop("feature_sums_f64", None)     # (a call that failed half way may have left sums behind)
             raise
         self.last_features_ms = float(a.stage_ms) if profile else None
+        if sync:
+            torch.cuda.current_stream(self.device).synchronize()
+        return keep[-1]
+
+    # -- the depth distortion map (include/gsrast_amd_distortion.h) ---------------------------
+    def _distortion_moments_of(self, rcpt: _capi.ForwardReceipt, power: int, moments: "torch.Tensor | None") -> torch.Tensor:
+        """The [3,H,W] moments a backward call reads: `moments`, or those the last render_distortion of this frame and power left."""
+        if moments is None:
+            serial, kept_power, kept = self._distortion_moments
+            assert kept is not None and serial == int(rcpt.serial) and kept_power == power, (
+                "distortion: the moments kept by this rasterizer are stale — they are those of render_distortion for another "
+                "frame or power (or there are none): call render_distortion(values, power=...) for this draw() first")
+            moments = kept
+        assert moments.dtype == torch.float32 and moments.device == self.device and moments.is_contiguous(), "moments"
+        assert tuple(moments.shape) == (3, self.height, self.width), ("moments", tuple(moments.shape))
+        return moments
+
+    def _distortion_call(self, rcpt: _capi.ForwardReceipt, values: torch.Tensor, power: int, moments: torch.Tensor, *,
+                         out: "torch.Tensor | None" = None, dL_dout: "torch.Tensor | None" = None,
+                         into: "torch.Tensor | None" = None, tile_rows: "tuple[int, int] | None" = None, profile: bool = False):
+        """(gsr_distortion_args, the tensors it points at) for the frame of `rcpt`: the forward call's with `out`, the backward
+        call's with dL_dout — the last tensor of the list is then dL_dvalues (`into`, or a new one), and the double scratch is
+        this object's (created zero, left zero by the library)."""
+        n, dev = self.num_gaussians, self.device
+        assert isinstance(values, torch.Tensor) and values.dtype == torch.float32 and values.device == dev, "values: a float32 tensor on this device"
+        assert values.dim() == 1 and values.shape[0] == n, ("values", tuple(values.shape), n)
+        v = values.detach().contiguous()
+        keep = [v, moments]
+        gst, ist, bst = _capi.GeometryState(), _capi.ImageState(), _capi.BinningState()
+        self.lib.gsr_geometry_from_chunk(self.geom.base(), n, C.byref(gst))
+        self.lib.gsr_image_from_chunk(self.image.base(), self.width * self.height, C.byref(ist))
+        self.lib.gsr_binning_from_chunk(self.binning.base(), int(rcpt.num_rendered), C.byref(bst))
+        a = _capi.DistortionArgs()
+        a.struct_size = C.sizeof(_capi.DistortionArgs)
+        a.flags = _capi.GSR_FLAG_PROFILE if profile else 0
+        a.num_gaussians, a.width, a.height, a.power = n, self.width, self.height, int(power)
+        a.means2D, a.conic_opacity = gst.means2D, gst.conic_opacity
+        a.ranges, a.n_contrib, a.final_t = ist.ranges, ist.n_contrib, ist.accum_alpha
+        a.point_list = bst.values
+        a.receipt = rcpt
+        a.values, a.moments = v.data_ptr(), moments.data_ptr()
+        if tile_rows is None:                    # (the band the draw() itself had: the calls take no other)
+            tile_rows = (int(rcpt.tile_row_begin), int(rcpt.tile_row_end))
+        a.tile_row_begin, a.tile_row_end = int(tile_rows[0]), int(tile_rows[1])
+        a.stream = _capi.stream(dev)
+        if out is not None:
+            a.out = out.data_ptr()
+            keep.append(out)
+        if dL_dout is not None:
+            g = dL_dout.to(device=dev, dtype=torch.float32).contiguous()
+            assert tuple(g.shape) == (self.height, self.width), ("dL_ddistortion_map", tuple(g.shape))
+            if into is not None:
+                assert into.dtype == torch.float32 and into.device == dev and into.is_contiguous() and tuple(into.shape) == (n,)
+            res = into if into is not None else torch.empty((n,), dtype=torch.float32, device=dev)
+            self._bw.fit(n)
+            scratch = self._bw.scratch.get("distortion_sums_f64")
+            if scratch is None or scratch.numel() < n:           # (all zero between calls)
+                scratch = self._bw.scratch["distortion_sums_f64"] = torch.zeros(n, dtype=torch.float64, device=dev)
+            a.dL_dout, a.dL_dvalues, a.value_sums_f64 = g.data_ptr(), res.data_ptr(), scratch.data_ptr()
+            keep += [g, res]
+        return a, keep
+
+    def render_distortion(self, values: torch.Tensor, *, power: int = 2, receipt: "_capi.ForwardReceipt | None" = None,
+                          tile_rows: "tuple[int, int] | None" = None, into: "torch.Tensor | None" = None, profile: bool = False,
+                          sync: bool = True) -> torch.Tensor:
+        """[H,W]: the distortion map sum_i sum_j w_i w_j |m_i - m_j|^power of the last draw() (gsr_distortion_forward), w = alpha T
+        with that call's own alpha, T and decisions — call it after a draw() and before the next one. values: float32 [N] on this
+        device, one scalar m per Gaussian (view depth, inverse depth, ...). power: 2, or 1 — signed in list order, which is the
+        absolute form wherever the values do not decrease along the lists (the frame's view depth). receipt: default this
+        object's last draw(). tile_rows: the band to write, which must be that of the draw(); other rows are left alone. into: a
+        float32 [H,W] tensor on this device, contiguous, written and returned; else a new tensor, zeros outside the band.
+        The per-pixel moments [3,H,W] the gradient needs are kept by this object (a new tensor per call), keyed to the receipt's
+        serial and the power: distortion_backward / backward(distortion=...) of another frame or power are refused.
+        One more walk over the sorted lists (refused after draw(sorted_lists=False)). profile: last_distortion_ms gets the time."""
+        rcpt = self.last_receipt if receipt is None else receipt
+        assert rcpt is not None, "render_distortion needs the receipt of a draw()"
+        assert power in (1, 2), ("power", power)
+        shape = (self.height, self.width)
+        if into is not None:
+            assert into.dtype == torch.float32 and into.device == self.device and into.is_contiguous() and tuple(into.shape) == shape
+        whole = tile_rows is None and (int(rcpt.tile_row_begin), int(rcpt.tile_row_end)) == (0, (self.height + 15) // 16)
+        new = torch.empty if whole else torch.zeros
+        out = into if into is not None else new(shape, dtype=torch.float32, device=self.device)
+        moments = new((3,) + shape, dtype=torch.float32, device=self.device)
+        a, _keep = self._distortion_call(rcpt, values, power, moments, out=out, tile_rows=tile_rows, profile=profile)
+        self._distortion_moments = (None, 0, None)
+        _capi.call("gsr_distortion_forward", C.byref(a), device=self.device)
+        self._distortion_moments = (int(rcpt.serial), int(power), moments)
+        self.last_distortion_ms = float(a.stage_ms) if profile else None
+        if sync:
+            torch.cuda.current_stream(self.device).synchronize()
+        return out
+
+    def distortion_backward(self, values: torch.Tensor, dL_dmap: torch.Tensor, *, power: int = 2,
+                            receipt: "_capi.ForwardReceipt | None" = None, tile_rows: "tuple[int, int] | None" = None,
+                            into: "torch.Tensor | None" = None, moments: "torch.Tensor | None" = None, profile: bool = False,
+                            sync: bool = True) -> torch.Tensor:
+        """dL_dvalues [N] of sum(dL_dmap * render_distortion(values, power=power)) for the last draw() (gsr_distortion_backward
+        with no geometry sums: the frozen-geometry case — nothing else is computed and no scratch shared with backward() is
+        touched; for the geometry's gradients too, pass distortion= to backward()). dL_dmap: [H,W]. moments: the [3,H,W] tensor
+        of that render_distortion call (default: the one this object kept, refused when it is of another frame or power).
+        The scratch (8 N bytes of doubles) is kept by this object, zero between calls and dropped if a call fails. into: a
+        float32 [N] tensor on this device, contiguous, written in full and returned."""
+        rcpt = self.last_receipt if receipt is None else receipt
+        assert rcpt is not None, "distortion_backward needs the receipt of a draw()"
+        assert power in (1, 2), ("power", power)
+        a, keep = self._distortion_call(rcpt, values, power, self._distortion_moments_of(rcpt, power, moments), dL_dout=dL_dmap,
+                                        into=into, tile_rows=tile_rows, profile=profile)
+        try:
+            _capi.call("gsr_distortion_backward", C.byref(a), device=self.device)
+        except _capi.GsrError:
+            self._bw.scratch.pop("distortion_sums_f64", None)   # (a call that failed half way may have left sums behind)
+            raise
+        self.last_distortion_ms = float(a.stage_ms) if profile else None
         if sync:
             torch.cuda.current_stream(self.device).synchronize()
         return keep[-1]

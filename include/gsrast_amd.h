@@ -465,8 +465,10 @@ typedef struct gsr_backward_args {
                                       in the fourth digit of its gradients, differently every run — and rounded to float once;
                                       the float arrays need not be cleared by anybody then.
                                       SEEDED SUMS: instead of zeros the rows of Gaussians with radii > 0 may hold, on entry, sums
-                                      in this layout that gsr_features_backward (gsrast_amd_features.h: geometry_sums_f64) of the
-                                      SAME forward call and tile rows left there. They are added to what the render backward sums
+                                      in this layout that gsr_features_backward (gsrast_amd_features.h: geometry_sums_f64) or
+                                      gsr_distortion_backward (gsrast_amd_distortion.h: geometry_sums_f64) of the SAME forward call
+                                      and tile rows left there; both may seed the same array before one gsr_backward. They are
+                                      added to what the render backward sums
                                       (every output and the chain see the total), and everything is left zero on return; a zero
                                       scratch behaves exactly as before. Every path only ever ADDS to the array before the
                                       per-Gaussian kernel reads, rounds and zeroes it: the render backward's direct double
