@@ -1,6 +1,6 @@
 """ctypes binding of include/gsrast_amd.h, include/gsrast_amd_init.h, include/gsrast_amd_opacity.h, include/gsrast_amd_mcmc.h,
 include/gsrast_amd_contrib.h, include/gsrast_amd_antialias.h, include/gsrast_amd_filter3d.h, include/gsrast_amd_absgrad.h,
-include/gsrast_amd_features.h and include/gsrast_amd_distortion.h (the C ABI of libgsrast_amd.so).
+include/gsrast_amd_features.h, include/gsrast_amd_distortion.h and include/gsrast_amd_normals.h (the C ABI of libgsrast_amd.so).
 
 There is no fallback: if the HIP library has not been built, importing the product path
 raises. Field order and types below mirror the header exactly.
@@ -421,6 +421,37 @@ DISTORTION_SIGNATURES = {
     "gsr_distortion_backward": (C.c_int, [C.POINTER(DistortionArgs)]),
 }
 
+# include/gsrast_amd_normals.h (the per-Gaussian normal and the normal of a depth surface, forward and backward), in the same shape, with its own symbol test.
+_GAUSSIAN_NORMALS_COMMON = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("num_gaussians", C.c_int32),
+                            ("means3D", C.c_void_p), ("scales", C.c_void_p), ("rotations", C.c_void_p), ("view_matrix", C.c_void_p)]
+_DEPTH_NORMALS_COMMON = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32),
+                         ("tan_fovx", C.c_float), ("tan_fovy", C.c_float), ("depth", C.c_void_p)]
+
+
+class GaussianNormalsArgs(C.Structure):
+    _fields_ = _GAUSSIAN_NORMALS_COMMON + [("normals", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class GaussianNormalsBackwardArgs(C.Structure):
+    _fields_ = _GAUSSIAN_NORMALS_COMMON + [("dL_dnormals", C.c_void_p), ("radii", C.c_void_p), ("dL_drotations", C.c_void_p),
+                                           ("stream", C.c_void_p)]
+
+
+class DepthNormalsArgs(C.Structure):
+    _fields_ = _DEPTH_NORMALS_COMMON + [("normals", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class DepthNormalsBackwardArgs(C.Structure):
+    _fields_ = _DEPTH_NORMALS_COMMON + [("dL_dnormals", C.c_void_p), ("dL_ddepth", C.c_void_p), ("stream", C.c_void_p)]
+
+
+NORMALS_SIGNATURES = {
+    "gsr_gaussian_normals_forward": (C.c_int, [C.POINTER(GaussianNormalsArgs)]),
+    "gsr_gaussian_normals_backward": (C.c_int, [C.POINTER(GaussianNormalsBackwardArgs)]),
+    "gsr_depth_normals_forward": (C.c_int, [C.POINTER(DepthNormalsArgs)]),
+    "gsr_depth_normals_backward": (C.c_int, [C.POINTER(DepthNormalsBackwardArgs)]),
+}
+
 _lib = None
 
 
@@ -448,7 +479,8 @@ def lib() -> C.CDLL:
         for name, (res, args) in (list(SIGNATURES.items()) + list(INIT_SIGNATURES.items()) + list(OPACITY_SIGNATURES.items())
                                   + list(MCMC_SIGNATURES.items()) + list(CONTRIB_SIGNATURES.items()) + list(ANTIALIAS_SIGNATURES.items())
                                   + list(FILTER3D_SIGNATURES.items()) + list(ABSGRAD_SIGNATURES.items())
-                                  + list(FEATURES_SIGNATURES.items()) + list(DISTORTION_SIGNATURES.items())):
+                                  + list(FEATURES_SIGNATURES.items()) + list(DISTORTION_SIGNATURES.items())
+                                  + list(NORMALS_SIGNATURES.items())):
             fn = getattr(L, name, None)
             if fn is None and _TAG:
                 continue                       # (a tagged A/B build of an older tree may lack the newest entry points)

@@ -3,6 +3,7 @@
   activate   raw parameters -> the arrays gsr_forward takes (gsr_activate_params / _backward, csrc/activations.hip)
   (filter3d.smooth   scales, opacities -> the 3D-filtered ones, between the two with filter_3d=values: gsrast_amd/filter3d.py)
   (antialias.compensate   opacities -> opacities * c, between the two with antialiased=True: gsrast_amd/antialias.py)
+  (normals.gaussian_normals   scales, rotations -> three more feature channels, with normals=True: gsrast_amd/normals.py)
   rasterize  SplatRasterizer.draw / backward / camera_backward as one differentiable function
   GaussianParams, render   the two joined for a trainer: `render(params, rast, cam)` then `loss.backward()`
 
@@ -21,6 +22,7 @@ import torch
 from . import _capi
 from . import antialias as _antialias
 from . import filter3d as _filter3d
+from . import normals as _normals
 from . import ply as _ply
 from .camera import Camera
 from .rasterizer import SplatRasterizer
@@ -262,7 +264,7 @@ def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs,
               semantics: str = "gscuda", sh_degree: int = 3, scale_modifier: float = 1.0, depth: "bool | str" = False,
               colors_precomp: "torch.Tensor | None" = None, radii_slot: "RadiiSlot | None" = None, opacity_grad: bool = False,
               antialiased: bool = False, features: "torch.Tensor | None" = None, distortion: "torch.Tensor | str | None" = None,
-              distortion_power: int = 2, **draw_options):
+              distortion_power: int = 2, normals: bool = False, **draw_options):
     """One differentiable frame: SplatRasterizer.draw forward, .backward / .camera_backward backward.
 
     Tensors in the library's layouts, float32 on rast.device: means3D / scales / rotations [N,4], opacities [N], shs [N,48]
@@ -307,7 +309,17 @@ def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs,
     feature_map], distortion_map). Its incoming gradient enters the same backward call as the other terms
     (SplatRasterizer.backward(distortion=...)), so the camera gradients, FrameSlot.dL_dmean2D, antialiased and the 3D filter
     all see it. FrameSlot(absgrad=True)'s abs_dL_dmean2D does NOT include it. Without `distortion` every return value and every
-    launch stay as they were."""
+    launch stay as they were.
+
+    normals=True: the per-Gaussian normals of normals.gaussian_normals — formed from the scales and rotations handed in here, for
+    the same semantics, view tensor and radii slot — travel as three more channels of the ONE feature pass, behind the caller's
+    `features` if any (C + 3 > 256 is a ValueError), and come back split off as normal_map [3,H,W], the alpha-blended view-space
+    normals over a zero background: (color, depth, opacity_map[, feature_map], normal_map[, distortion_map]). Its incoming
+    gradient enters the same backward call as the other terms and reaches every parameter the blend weights depend on and the
+    camera through them; through the normals themselves it reaches the rotations only — not the scales, the means or the camera: a
+    view that requires a gradient is a ValueError. With normals.depth_normals of depth / opacity_map it forms 2DGS's
+    normal-consistency loss (normals.normal_consistency). Without `normals` every return value and every launch stay as they
+    were."""
     assert set(draw_options) <= set(_DRAW_OPTIONS), sorted(draw_options)
     assert depth in (False, True, "inverse"), depth
     opts = {"tan_fov": (float(tan_fov[0]), float(tan_fov[1])), "semantics": semantics, "sh_degree": int(sh_degree),
@@ -317,16 +329,44 @@ def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs,
     if antialiased:
         opacities = _antialias.compensate(means3D, scales, rotations, opacities, view, opts["tan_fov"], rast.width, rast.height,
                                           semantics=semantics, scale_modifier=opts["scale_modifier"], proj=proj, radii_slot=radii_slot)
+    if normals:
+        return _with_normals(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, features, distortion)
     if distortion is None:
         if features is None:
             return _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, None, None)[:3]
         return _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, features, None)[:4]
+    distortion = _distortion_values(distortion, means3D, view)
+    out = _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, features, distortion)
+    return out[:3] + ((out[3],) if features is not None else ()) + (out[4],)
+
+
+def _distortion_values(distortion, means3D, view):
+    """rasterize's `distortion` as a tensor: "depth" is the view-space z of means3D, formed with torch operations."""
     if isinstance(distortion, str):
         assert distortion == "depth", distortion
         v = view.reshape(-1)                                  # (column-major: row 2 of the view matrix is elements 2, 6, 10, 14)
         distortion = (means3D[:, 0] * v[2] + means3D[:, 1] * v[6]) + (means3D[:, 2] * v[10] + v[14])
-    out = _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, features, distortion)
-    return out[:3] + ((out[3],) if features is not None else ()) + (out[4],)
+    return distortion
+
+
+def _with_normals(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, features, distortion):
+    """rasterize(normals=True): the Gaussian normals as the last three channels of the one feature pass, split off again."""
+    n, dev = int(means3D.shape[0]), rast.device
+    c = 0
+    if features is not None:
+        if features.dtype != F32 or features.dim() != 2 or int(features.shape[0]) != n or features.device != dev:
+            raise ValueError(f"features: expected float32 [{n}, C] on {dev}, got {features.dtype} {tuple(features.shape)} on {features.device}")
+        c = int(features.shape[1])
+        if c + 3 > _capi.GSR_FEATURES_MAX_CHANNELS:
+            raise ValueError(f"features: {c} channels and the three of normals=True are more than the feature pass's "
+                             f"{_capi.GSR_FEATURES_MAX_CHANNELS}")
+    per_gaussian = _normals.gaussian_normals(means3D, scales, rotations, view, semantics=opts["semantics"], radii_slot=opts["radii_slot"])
+    channels = per_gaussian if features is None else torch.cat([features, per_gaussian], 1)
+    if distortion is not None:
+        distortion = _distortion_values(distortion, means3D, view)
+    out = _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, channels, distortion)
+    return (out[:3] + ((out[3][:c],) if features is not None else ()) + (out[3][c:],)
+            + ((out[4],) if distortion is not None else ()))
 
 
 def _rest_to_coefficient_major(sh: np.ndarray) -> np.ndarray:
@@ -444,7 +484,7 @@ def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: 
            scale_modifier: float = 1.0, depth: "bool | str" = False, radii_slot: "RadiiSlot | None" = None,
            opacity_grad: bool = False, antialiased: bool = False, filter_3d: "torch.Tensor | None" = None,
            features: "torch.Tensor | None" = None, distortion: "torch.Tensor | str | None" = None, distortion_power: int = 2,
-           **draw_options):
+           normals: bool = False, **draw_options):
     """`activate` then `rasterize`: (color [3,H,W], depth [H,W] or None, opacity_map [H,W]) of `params` seen from `camera`
     — a Camera (its matrices are uploaded once per device and kept with it; write to a Camera's arrays and it must be a new
     object) or a tuple (view, proj, cam_pos, tan_fovx, tan_fovy) whose first three are device tensors, which may require
@@ -462,7 +502,10 @@ def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: 
     features: float32 [N,C] on the rasterizer's device (a Parameter of the caller's, say): the result is then the 4-tuple
     (color, depth, opacity_map, feature_map [C,H,W]) of `rasterize`, the feature map over a zero background.
     distortion, distortion_power: a float32 [N] tensor or "depth" (the view-space z): the distortion map [H,W] of `rasterize` is
-    appended as the last element of the result."""
+    appended as the last element of the result.
+    normals=True: the normal map [3,H,W] of `rasterize` — the per-Gaussian normals of the activated (and, with filter_3d, smoothed:
+    the filter adds the same amount to every squared scale, so the shortest axis stays the shortest) scales and rotations — follows
+    the feature map, before the distortion map; the view matrix must then not require a gradient."""
     if semantics == "inria" and sh_degree >= 1:
         assert params.sh_layout == "coefficient_major", 'semantics="inria" reads shs as [N][16][3]: sh_layout="coefficient_major"'
     slot = radii_slot if radii_slot is not None else RadiiSlot()
@@ -473,4 +516,4 @@ def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: 
     return rasterize(rast, means3D, scales, rotations, opacities, params.shs, view, proj, cam_pos, (tan_fovx, tan_fovy),
                      semantics=semantics, sh_degree=sh_degree, scale_modifier=scale_modifier, depth=depth, radii_slot=slot,
                      opacity_grad=opacity_grad, antialiased=antialiased, features=features, distortion=distortion,
-                     distortion_power=distortion_power, **draw_options)
+                     distortion_power=distortion_power, normals=normals, **draw_options)
