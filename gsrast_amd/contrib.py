@@ -99,12 +99,11 @@ class ContributionStats:
 def contribution_args(rast, rcpt: "_capi.ForwardReceipt", semantics: str, outputs: dict) -> "_capi.ContributionArgs":
     """gsr_contribution_args for the forward call of `rcpt` on `rast`, on torch's current stream: that call's chunks mapped
     as backward() maps them. outputs: {name of WHAT: device address}; the others stay NULL."""
-    b = rast._backward_args(rcpt, None, semantics, 0)
     a = _capi.ContributionArgs()
     a.struct_size = C.sizeof(_capi.ContributionArgs)
     a.flags = _capi.GSR_FLAG_SEMANTICS_INRIA if semantics == "inria" else 0
     a.num_gaussians, a.width, a.height = rast.num_gaussians, rast.width, rast.height
-    a.means2D, a.conic_opacity, a.ranges, a.n_contrib, a.point_list = b.means2D, b.conic_opacity, b.ranges, b.n_contrib, b.point_list
+    rast._map_frame(a, int(rcpt.num_rendered))
     a.receipt = rcpt
     for w, ptr in outputs.items():
         assert w in WHAT, w

@@ -6,21 +6,18 @@
 //     the pixel's first blended record (d = m - m0), and D = sum w e with e the record's distance to everything in front of it.
 //     It leaves out = 2 D and the three planes m0, M1, M2 the backward reads.
 //   - distortion_backward_kernel is the back walk: with the pixel's totals every record's d out / d w (c) and d out / d m come
-//     from what the pixel read once; dL_dalpha = g (Tn c - S inv) with S the suffix sum of c w, and from there (GEO) the render
-//     backward's own lines, added into slots 0..5 and 9..11 of the double sums a gsr_backward of the same frame then reads.
+//     from what the pixel read once; dL_dalpha = g (Tn c - S inv) with S the suffix sum of c w, and from there (GEO) the walk's
+//     GeometrySums: the render backward's own lines, added into the double sums a gsr_backward of the same frame then reads.
 //     Without GEO neither c nor S is formed.
-// A record's value sum rides in the seventh input of the wave_sum8 that carries the six geometry sums: two reductions a record,
-// as in features.hip.
+// A record's value sum rides in the seventh input of the wave_sum8 that carries the six geometry sums (GeometrySums::file's
+// `extra`): two reductions a record, as in features.hip.
 #include <hip/hip_runtime.h>
-#include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 #include "list_walk.hpp"
 #include "../../include/gsrast_amd_distortion.h"
 
 namespace gsr {
 namespace {
-
-constexpr uint32_t kGeoFloats = 12;      // the layout of gsr_backward_args.sums_f64 (backward.hip: kAccFloats)
 
 struct DistortionParams {
     WalkFrame frame;
@@ -100,14 +97,7 @@ __global__ __launch_bounds__(kWave) void distortion_backward_kernel(const Distor
     if (tile < 0) return;
     const size_t plane = (size_t)p.frame.dims.width * (size_t)p.frame.dims.height;
 
-    // Which of a record's sums this lane files: wave_sum8 leaves value kSumOfRow[r] in lane 8 r; wave_sum4 value kSumOfRow4[r]
-    // in every lane of row r (lane 16 r + 4 files it). Of the eight, values 0..5 are the geometry's slots 0..5 (the render
-    // backward's, backward.hip), value 6 is the record's value sum and value 7 is unused; the four are slots 9..11 and one unused.
-    constexpr int kSumOfRow[8] = {0, 4, 2, 6, 1, 5, 3, 7};
-    constexpr int kSumOfRow4[4] = {9, 11, 10, 12};
-    constexpr int kValueSum = 6;
-    const int my8 = (lane & 7) == 0 ? kSumOfRow[lane >> 3] : -1;
-    const int my_geo = (lane & 7) == 0 ? (my8 < 6 ? my8 : -1) : ((lane & 15) == 4 && kSumOfRow4[lane >> 4] < 12 ? kSumOfRow4[lane >> 4] : -1);
+    [[maybe_unused]] const bool files_value = sum8_of_lane(lane) == GeometrySums::kExtra;      // (GEO: the record's value sum rides there)
 
     BackLanes s;
     float g[4] = {}, m0[4] = {}, M1n[4] = {};
@@ -115,7 +105,7 @@ __global__ __launch_bounds__(kWave) void distortion_backward_kernel(const Distor
     [[maybe_unused]] float An[4], Tf[4], Tb[4], Ms[4], S[4];
     // the record in hand: its value and this lane's sums over its four pixels
     float m = 0.0f, a_v = 0.0f;
-    [[maybe_unused]] float a_mx, a_my, a_A, a_B, a_C, a_op, a_m00, a_m01, a_m11;
+    [[maybe_unused]] GeometrySums geo(lane);
     back_walk<true>(
         p.frame, tile, tx, ty, lane, s, st,
         /* seed */ [&](const int k, const size_t pid) {
@@ -136,7 +126,7 @@ __global__ __launch_bounds__(kWave) void distortion_backward_kernel(const Distor
         /* begin */ [&](const int j) {
             m = s_value[j];
             a_v = 0.0f;
-            if constexpr (GEO) a_mx = a_my = a_A = a_B = a_C = a_op = a_m00 = a_m01 = a_m11 = 0.0f;
+            if constexpr (GEO) geo.clear();
         },
         /* on_pixel */ [&](const int k, const BackPixel& px) {
             const float d = m - m0[k];
@@ -158,32 +148,16 @@ __global__ __launch_bounds__(kWave) void distortion_backward_kernel(const Distor
             }
             a_v = __builtin_fmaf(px.w * g[k], dv, a_v);
             if constexpr (GEO) {
-                // from here to the sums: render_backward_kernel's lines (backward.hip), as features_backward_kernel has them
-                const float dx = px.dx, dy = px.dy;
                 const float dL_dalpha = g[k] * __builtin_fmaf(px.Tn, c, -(S[k] * px.inv));
                 S[k] = __builtin_fmaf(c, px.w, S[k]);
-                const bool live = px.live();
-                const float gop = live ? px.G * dL_dalpha : 0.0f;
-                const float dpow = live ? px.raw * dL_dalpha : 0.0f;
-                a_op += gop;
-                a_A = __builtin_fmaf(-0.5f * dx * dx, dpow, a_A);
-                a_B = __builtin_fmaf(-(dx * dy), dpow, a_B);
-                a_C = __builtin_fmaf(-0.5f * dy * dy, dpow, a_C);
-                const float ux = px.ux(), uy = px.uy();
-                a_mx = __builtin_fmaf(-ux, dpow, a_mx);
-                a_my = __builtin_fmaf(-uy, dpow, a_my);
-                const float hux = 0.5f * dpow * ux, huy = 0.5f * dpow * uy;      // (the masked factor first: 0 x finite)
-                a_m00 = __builtin_fmaf(hux, ux, a_m00); a_m01 = __builtin_fmaf(hux, uy, a_m01); a_m11 = __builtin_fmaf(huy, uy, a_m11);
+                geo.add(px, dL_dalpha);
             }
         },
         /* file */ [&](const int j) {
             const size_t id = st.id[j];
             if constexpr (GEO) {
-                const float t8 = wave_sum8(a_mx, a_my, a_A, a_B, a_C, a_op, a_v, 0.0f, lane);
-                const float t4 = wave_sum4(a_m00, a_m01, a_m11, 0.0f);
-                if (my8 == kValueSum && t8 != 0.0f) unsafeAtomicAdd(p.value_sums + id, (double)t8);
-                const float total = (lane & 7) == 4 ? t4 : t8;
-                if (my_geo >= 0 && total != 0.0f) unsafeAtomicAdd(p.geometry_sums + kGeoFloats * id + (uint32_t)my_geo, (double)total);
+                const float total = geo.file(p.geometry_sums, id, lane, a_v);
+                if (files_value && total != 0.0f) unsafeAtomicAdd(p.value_sums + id, (double)total);
             } else {
                 const float total = wave_sum2(a_v, 0.0f);            // (lane 31 holds the total of the first)
                 if (lane == 31 && total != 0.0f) unsafeAtomicAdd(p.value_sums + id, (double)total);
@@ -191,24 +165,19 @@ __global__ __launch_bounds__(kWave) void distortion_backward_kernel(const Distor
         });
 }
 
-// What both calls check, in the header's order; *nothing: no record to walk (R == 0 or an empty band).
+// What both calls check beside walk_pass_check; *nothing: no record to walk (R == 0 or an empty band).
 int distortion_check(gsr_distortion_args* a, bool backward, FrameDims* d, bool* nothing) {
-    if (!a || a->struct_size != sizeof(gsr_distortion_args)) return GSR_ERR_INVALID_ARG;
-    a->stage_ms = 0.0f;
-    if (a->num_gaussians <= 0 || a->width <= 0 || a->height <= 0) return GSR_ERR_INVALID_ARG;
+    GSR_TRY(walk_pass_check(a, d, nothing));
     if (a->power != 1 && a->power != 2) return GSR_ERR_INVALID_ARG;
-    if (!a->means2D || !a->conic_opacity || !a->ranges || !a->n_contrib || !a->final_t || !a->values) return GSR_ERR_INVALID_ARG;
-    if (!a->moments) return GSR_ERR_INVALID_ARG;
+    if (!a->values || !a->moments) return GSR_ERR_INVALID_ARG;
     if (backward ? (!a->dL_dout || !a->dL_dvalues || !a->value_sums_f64) : !a->out) return GSR_ERR_INVALID_ARG;
-    if (misaligned(a->means2D, 8) || misaligned(a->conic_opacity, 16) || misaligned(a->ranges, 8)) return GSR_ERR_INVALID_ARG;
     if (backward && (misaligned(a->value_sums_f64, 8) || misaligned(a->geometry_sums_f64, 8))) return GSR_ERR_INVALID_ARG;
-    return walk_check(a->receipt, a->num_gaussians, a->width, a->height, a->tile_row_begin, a->tile_row_end, false, a->point_list, d, nothing);
+    return GSR_OK;
 }
 
-DistortionParams distortion_params(const gsr_distortion_args* a, const FrameDims& d) {
+DistortionParams distortion_params(const gsr_distortion_args* a, const WalkFrame& frame) {
     DistortionParams p;
-    p.frame = walk_frame(a->ranges, a->point_list, a->means2D, a->conic_opacity, a->n_contrib, a->final_t, d, a->num_gaussians,
-                         a->receipt.num_rendered);
+    p.frame = frame;
     p.values = a->values;
     p.out = a->out;
     p.moments = a->moments;
@@ -222,47 +191,32 @@ int distortion_forward_impl(gsr_distortion_args* a) {
     FrameDims d;
     bool nothing = false;
     GSR_TRY(distortion_check(a, false, &d, &nothing));
-    const long long blocks = patch_workgroups(d.grid_x, d.row_end - d.row_begin);
-    if (exceeds_grid(blocks)) return GSR_ERR_TOO_LARGE;
-    // ---- nothing is refused from here on ----
-    hipStream_t stream = static_cast<hipStream_t>(a->stream);
-    StageTimer timer;
-    GSR_TRY(timer.begin((a->flags & GSR_FLAG_PROFILE) != 0, stream));
-    if (d.row_begin != d.row_end) {          // (R == 0: every tile of the band is a tile without a list)
-        const DistortionParams p = distortion_params(a, d);
-        const dim3 grid((unsigned)blocks);
+    return walk_pass_call(a, d, nothing, nullptr, [&](const WalkFrame& frame, unsigned blocks, hipStream_t stream) {
+        const DistortionParams p = distortion_params(a, frame);
+        const dim3 grid(blocks);
         if (a->power == 2) hipLaunchKernelGGL(distortion_forward_kernel<2>, grid, dim3(kWave), 0, stream, p);
         else hipLaunchKernelGGL(distortion_forward_kernel<1>, grid, dim3(kWave), 0, stream, p);
         GSR_LAUNCH_CHECK("distortion_forward_kernel");
-    }
-    return timer.end(stream, &a->stage_ms);
+        return GSR_OK;
+    });
 }
 
 int distortion_backward_impl(gsr_distortion_args* a) {
     FrameDims d;
     bool nothing = false;
     GSR_TRY(distortion_check(a, true, &d, &nothing));
-    const long long blocks = patch_workgroups(d.grid_x, d.row_end - d.row_begin);
-    const size_t count = (size_t)a->num_gaussians;
-    if (exceeds_grid(blocks) || exceeds_grid(finish_sums_workgroups(count))) return GSR_ERR_TOO_LARGE;
-    // ---- nothing is refused from here on ----
-    hipStream_t stream = static_cast<hipStream_t>(a->stream);
-    StageTimer timer;
-    GSR_TRY(timer.begin((a->flags & GSR_FLAG_PROFILE) != 0, stream));
-    if (!nothing) {
-        DistortionParams p = distortion_params(a, d);
-        // (the tiles that were slow in the forward blend are the slow ones here: they go first, as they did there)
-        p.frame.tile_order = tile_order_of_call(a->receipt, d.row_begin, d.row_end);
+    const WalkSums sums = {(size_t)a->num_gaussians, a->value_sums_f64, a->dL_dvalues};
+    return walk_pass_call(a, d, nothing, &sums, [&](const WalkFrame& frame, unsigned blocks, hipStream_t stream) {
+        const DistortionParams p = distortion_params(a, frame);
         const bool square = a->power == 2, geo = a->geometry_sums_f64 != nullptr;
-        const dim3 grid((unsigned)blocks);
+        const dim3 grid(blocks);
         if (square && geo) hipLaunchKernelGGL((distortion_backward_kernel<2, true>), grid, dim3(kWave), 0, stream, p);
         else if (square) hipLaunchKernelGGL((distortion_backward_kernel<2, false>), grid, dim3(kWave), 0, stream, p);
         else if (geo) hipLaunchKernelGGL((distortion_backward_kernel<1, true>), grid, dim3(kWave), 0, stream, p);
         else hipLaunchKernelGGL((distortion_backward_kernel<1, false>), grid, dim3(kWave), 0, stream, p);
         GSR_LAUNCH_CHECK("distortion_backward_kernel");
-    }
-    GSR_TRY(launch_finish_sums<1>(count, a->value_sums_f64, a->dL_dvalues, stream));
-    return timer.end(stream, &a->stage_ms);
+        return GSR_OK;
+    });
 }
 
 }  // namespace

@@ -5,15 +5,13 @@
 //   - features_forward_kernel is the replay: what a blended (record, pixel) adds is composite_record's acc = fmaf(f, alpha T, acc)
 //     per channel, and a pixel leaves as tile_lanes_write forms it, acc + final_t bg. With the frame's colours and background
 //     that is out_color bit for bit.
-//   - features_backward_kernel is the back walk, and from dL_dalpha on (GEO) the render backward's own lines (backward.hip) — the
-//     clamp rule raw > 0.99, dpow, gop, u = K d, the pixel-by-pixel cov2D sums — added into slots 0..5 and 9..11 of the double
-//     sums a gsr_backward of the same frame then reads (slots 6..8, the colour's, are not touched). Without GEO neither cg nor
-//     the suffix sum S is formed: w g is all a frozen geometry needs.
+//   - features_backward_kernel is the back walk, and from dL_dalpha on (GEO) the walk's GeometrySums: the render backward's own
+//     lines, added into the double sums a gsr_backward of the same frame then reads. Without GEO neither cg nor the suffix
+//     sum S is formed: w g is all a frozen geometry needs.
 // A record's K feature sums are reduced eight at a time by the fold-and-pack of backward.hip's wave_sum12 (three lane swaps
 // pack eight values into one register, four DPP steps finish: 8 sums for the price of about 2 separate ones) and leave as ONE
 // double atomic instruction per eight channels, eight lanes on 64 contiguous bytes of feature_sums_f64.
 #include <hip/hip_runtime.h>
-#include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 #include "list_walk.hpp"
 #include "../../include/gsrast_amd_features.h"
@@ -28,7 +26,6 @@ constexpr int kChunkNarrow = GSR_FEATURES_CHUNK_NARROW, kChunkWide = GSR_FEATURE
 static_assert(kChunkNarrow % 8 == 0 && kChunkNarrow >= 8 && kChunkWide % 8 == 0 && kChunkWide >= kChunkNarrow && kChunkWide <= 32,
               "the reduction packs eight sums per register");
 inline int chunk_of(int channels) { return channels <= kChunkNarrow ? kChunkNarrow : kChunkWide; }
-constexpr uint32_t kGeoFloats = 12;      // the layout of gsr_backward_args.sums_f64 (backward.hip: kAccFloats)
 
 struct FeatureParams {
     WalkFrame frame;
@@ -136,14 +133,7 @@ __global__ __launch_bounds__(kWave) void features_backward_kernel(const FeatureP
     const size_t plane = (size_t)p.frame.dims.width * (size_t)p.frame.dims.height;
     const uint32_t c0 = blockIdx.y * (uint32_t)K, nc = min((uint32_t)K, p.channels - c0);
 
-    // Which of a record's sums this lane files: wave_sum8 leaves value kSumOfRow[r] in lane 8 r; wave_sum4 value kSumOfRow4[r]
-    // in every lane of row r (lane 16 r + 4 files it) — the geometry's slots are the render backward's (backward.hip).
-    constexpr int kSumOfRow[8] = {0, 4, 2, 6, 1, 5, 3, 7};
-    constexpr int kSumOfRow4[4] = {9, 11, 10, 12};
-    const int my_feat = (lane & 7) == 0 ? kSumOfRow[lane >> 3] : -1;
-    // (geometry: values 0..5 of the eight are slots 0..5, values 6 and 7 are unused; the four are slots 9..11 and one unused)
-    const int my_geo = (lane & 7) == 0 ? (kSumOfRow[lane >> 3] < 6 ? kSumOfRow[lane >> 3] : -1)
-                                       : ((lane & 15) == 4 && kSumOfRow4[lane >> 4] < 12 ? kSumOfRow4[lane >> 4] : -1);
+    const int my_feat = sum8_of_lane(lane);        // which of a reduction's eight channel sums this lane files
 
     BackLanes s;
     float g[4][K] = {};
@@ -151,7 +141,7 @@ __global__ __launch_bounds__(kWave) void features_backward_kernel(const FeatureP
     // the record in hand: its features (GEO) and this lane's sums over its four pixels
     float a_f[K];
     [[maybe_unused]] float feat[K];
-    [[maybe_unused]] float a_mx, a_my, a_A, a_B, a_C, a_op, a_m00, a_m01, a_m11;
+    [[maybe_unused]] GeometrySums geo(lane);
     back_walk<true>(
         p.frame, tile, tx, ty, lane, s, st,
         /* seed */ [&](const int k, const size_t pid) {
@@ -183,7 +173,7 @@ __global__ __launch_bounds__(kWave) void features_backward_kernel(const FeatureP
             for (int c = 0; c < K; ++c) a_f[c] = 0.0f;
             if constexpr (GEO) {
                 load_feature_row<K>(feat, &s_feat[j * K]);
-                a_mx = a_my = a_A = a_B = a_C = a_op = a_m00 = a_m01 = a_m11 = 0.0f;
+                geo.clear();
             }
         },
         /* on_pixel */ [&](const int k, const BackPixel& px) {
@@ -193,22 +183,9 @@ __global__ __launch_bounds__(kWave) void features_backward_kernel(const FeatureP
                 float cg = feat[K - 1] * g[k][K - 1];
 #pragma unroll
                 for (int c = K - 2; c >= 0; --c) cg = __builtin_fmaf(feat[c], g[k][c], cg);
-                // from here to the sums: render_backward_kernel's lines (backward.hip)
-                const float dx = px.dx, dy = px.dy;
                 const float dL_dalpha = __builtin_fmaf(px.Tn, cg, -(S[k] * px.inv));
                 S[k] = __builtin_fmaf(cg, px.w, S[k]);
-                const bool live = px.live();
-                const float gop = live ? px.G * dL_dalpha : 0.0f;
-                const float dpow = live ? px.raw * dL_dalpha : 0.0f;
-                a_op += gop;
-                a_A = __builtin_fmaf(-0.5f * dx * dx, dpow, a_A);
-                a_B = __builtin_fmaf(-(dx * dy), dpow, a_B);
-                a_C = __builtin_fmaf(-0.5f * dy * dy, dpow, a_C);
-                const float ux = px.ux(), uy = px.uy();
-                a_mx = __builtin_fmaf(-ux, dpow, a_mx);
-                a_my = __builtin_fmaf(-uy, dpow, a_my);
-                const float hux = 0.5f * dpow * ux, huy = 0.5f * dpow * uy;      // (the masked factor first: 0 x finite)
-                a_m00 = __builtin_fmaf(hux, ux, a_m00); a_m01 = __builtin_fmaf(hux, uy, a_m01); a_m11 = __builtin_fmaf(huy, uy, a_m11);
+                geo.add(px, dL_dalpha);
             }
         },
         /* file */ [&](const int j) {
@@ -220,32 +197,23 @@ __global__ __launch_bounds__(kWave) void features_backward_kernel(const FeatureP
                 if (my_feat >= 0 && (uint32_t)(c + my_feat) < nc && total != 0.0f)
                     unsafeAtomicAdd(p.feature_sums + id * (size_t)p.channels + c0 + (uint32_t)(c + my_feat), (double)total);
             }
-            if constexpr (GEO) {
-                const float t8 = wave_sum8(a_mx, a_my, a_A, a_B, a_C, a_op, 0.0f, 0.0f, lane);
-                const float t4 = wave_sum4(a_m00, a_m01, a_m11, 0.0f);
-                const float total = (lane & 7) == 4 ? t4 : t8;
-                if (my_geo >= 0 && total != 0.0f) unsafeAtomicAdd(p.geometry_sums + kGeoFloats * id + (uint32_t)my_geo, (double)total);
-            }
+            if constexpr (GEO) geo.file(p.geometry_sums, id, lane, 0.0f);
         });
 }
 
-// What both calls check, in the header's order; *nothing: no record to walk (R == 0 or an empty band).
+// What both calls check beside walk_pass_check; *nothing: no record to walk (R == 0 or an empty band).
 int features_check(gsr_features_args* a, bool backward, FrameDims* d, bool* nothing) {
-    if (!a || a->struct_size != sizeof(gsr_features_args)) return GSR_ERR_INVALID_ARG;
-    a->stage_ms = 0.0f;
-    if (a->num_gaussians <= 0 || a->width <= 0 || a->height <= 0) return GSR_ERR_INVALID_ARG;
+    GSR_TRY(walk_pass_check(a, d, nothing));
     if (a->channels < 1 || a->channels > GSR_FEATURES_MAX_CHANNELS) return GSR_ERR_INVALID_ARG;
-    if (!a->means2D || !a->conic_opacity || !a->ranges || !a->n_contrib || !a->final_t || !a->features) return GSR_ERR_INVALID_ARG;
+    if (!a->features) return GSR_ERR_INVALID_ARG;
     if (backward ? (!a->dL_dout || !a->dL_dfeatures || !a->feature_sums_f64) : !a->out) return GSR_ERR_INVALID_ARG;
-    if (misaligned(a->means2D, 8) || misaligned(a->conic_opacity, 16) || misaligned(a->ranges, 8)) return GSR_ERR_INVALID_ARG;
     if (backward && (misaligned(a->feature_sums_f64, 8) || misaligned(a->geometry_sums_f64, 8))) return GSR_ERR_INVALID_ARG;
-    return walk_check(a->receipt, a->num_gaussians, a->width, a->height, a->tile_row_begin, a->tile_row_end, false, a->point_list, d, nothing);
+    return GSR_OK;
 }
 
-FeatureParams feature_params(const gsr_features_args* a, const FrameDims& d) {
+FeatureParams feature_params(const gsr_features_args* a, const WalkFrame& frame) {
     FeatureParams p;
-    p.frame = walk_frame(a->ranges, a->point_list, a->means2D, a->conic_opacity, a->n_contrib, a->final_t, d, a->num_gaussians,
-                         a->receipt.num_rendered);
+    p.frame = frame;
     p.features = a->features;
     p.background = a->background;
     p.out = a->out;
@@ -260,49 +228,34 @@ int features_forward_impl(gsr_features_args* a) {
     FrameDims d;
     bool nothing = false;
     GSR_TRY(features_check(a, false, &d, &nothing));
-    const long long blocks = patch_workgroups(d.grid_x, d.row_end - d.row_begin);
-    if (exceeds_grid(blocks)) return GSR_ERR_TOO_LARGE;
-    // ---- nothing is refused from here on ----
-    hipStream_t stream = static_cast<hipStream_t>(a->stream);
-    StageTimer timer;
-    GSR_TRY(timer.begin((a->flags & GSR_FLAG_PROFILE) != 0, stream));
-    if (d.row_begin != d.row_end) {          // (R == 0: every tile of the band is a tile without a list)
-        const FeatureParams p = feature_params(a, d);
+    return walk_pass_call(a, d, nothing, nullptr, [&](const WalkFrame& frame, unsigned blocks, hipStream_t stream) {
+        const FeatureParams p = feature_params(a, frame);
         const int k = chunk_of(a->channels);
-        const dim3 grid((unsigned)blocks, (unsigned)((a->channels + k - 1) / k));
+        const dim3 grid(blocks, (unsigned)((a->channels + k - 1) / k));
         if (k == kChunkNarrow) hipLaunchKernelGGL(features_forward_kernel<kChunkNarrow>, grid, dim3(kWave), 0, stream, p);
         else hipLaunchKernelGGL(features_forward_kernel<kChunkWide>, grid, dim3(kWave), 0, stream, p);
         GSR_LAUNCH_CHECK("features_forward_kernel");
-    }
-    return timer.end(stream, &a->stage_ms);
+        return GSR_OK;
+    });
 }
 
 int features_backward_impl(gsr_features_args* a) {
     FrameDims d;
     bool nothing = false;
     GSR_TRY(features_check(a, true, &d, &nothing));
-    const long long blocks = patch_workgroups(d.grid_x, d.row_end - d.row_begin);
-    const size_t count = (size_t)a->num_gaussians * (size_t)a->channels;
-    if (exceeds_grid(blocks) || exceeds_grid(finish_sums_workgroups(count))) return GSR_ERR_TOO_LARGE;
-    // ---- nothing is refused from here on ----
-    hipStream_t stream = static_cast<hipStream_t>(a->stream);
-    StageTimer timer;
-    GSR_TRY(timer.begin((a->flags & GSR_FLAG_PROFILE) != 0, stream));
-    if (!nothing) {
-        FeatureParams p = feature_params(a, d);
-        // (the tiles that were slow in the forward blend are the slow ones here: they go first, as they did there)
-        p.frame.tile_order = tile_order_of_call(a->receipt, d.row_begin, d.row_end);
+    const WalkSums sums = {(size_t)a->num_gaussians * (size_t)a->channels, a->feature_sums_f64, a->dL_dfeatures};
+    return walk_pass_call(a, d, nothing, &sums, [&](const WalkFrame& frame, unsigned blocks, hipStream_t stream) {
+        const FeatureParams p = feature_params(a, frame);
         const int k = chunk_of(a->channels);
         const bool narrow = k == kChunkNarrow, geo = a->geometry_sums_f64 != nullptr;
-        const dim3 grid((unsigned)blocks, (unsigned)((a->channels + k - 1) / k));
+        const dim3 grid(blocks, (unsigned)((a->channels + k - 1) / k));
         if (narrow && geo) hipLaunchKernelGGL((features_backward_kernel<kChunkNarrow, true>), grid, dim3(kWave), 0, stream, p);
         else if (narrow) hipLaunchKernelGGL((features_backward_kernel<kChunkNarrow, false>), grid, dim3(kWave), 0, stream, p);
         else if (geo) hipLaunchKernelGGL((features_backward_kernel<kChunkWide, true>), grid, dim3(kWave), 0, stream, p);
         else hipLaunchKernelGGL((features_backward_kernel<kChunkWide, false>), grid, dim3(kWave), 0, stream, p);
         GSR_LAUNCH_CHECK("features_backward_kernel");
-    }
-    GSR_TRY(launch_finish_sums<1>(count, a->feature_sums_f64, a->dL_dfeatures, stream));
-    return timer.end(stream, &a->stage_ms);
+        return GSR_OK;
+    });
 }
 
 }  // namespace

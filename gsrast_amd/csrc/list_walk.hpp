@@ -1,7 +1,10 @@
-// The two walks over a tile's SORTED list that the passes behind a forward call share (contrib.hip, absgrad.hip, features.hip),
-// each written once as __device__ __forceinline__ templates that take the pass's part as callables — every callable is inlined
-// into the unrolled loops, so the pixel index k stays a compile-time index into the per-pixel register arrays — and, at the
-// end, the host side those calls share. Common to both walks: one wavefront per 16 x 16 tile, four pixels per lane
+// The two walks over a tile's SORTED list that the passes behind a forward call share, each written once as __device__
+// __forceinline__ templates that take the pass's part as callables — every callable is inlined into the unrolled loops, so the
+// pixel index k stays a compile-time index into the per-pixel register arrays — and, at the end, the host side those calls
+// share. Who takes what: the replay contrib.hip, features.hip and distortion.hip (forward); the back walk absgrad.hip,
+// features.hip and distortion.hip (backward), the last two with GeometrySums behind it where the geometry moves; the host
+// side's walk_check, walk_frame and StageTimer all four, finish_sums the three backward calls, and walk_pass_check /
+// walk_pass_call features.hip and distortion.hip, whose argument structs name the frame's fields alike. Common to both walks: one wavefront per 16 x 16 tile, four pixels per lane
 // (x = lane & 15, y = (lane >> 4) + 4 k), tiles dealt to the XCDs in patches (blend_core.hpp: tile_of_workgroup), batches of 64
 // list entries with ids two batches ahead and records one batch ahead, a batch compacted by record_misses_tile, one lane per
 // record, into wave-private LDS (no barrier: its writes and reads are ordered inside the wave). A list entry is bounded by the
@@ -18,9 +21,10 @@
 //   - the BACK WALK (back to front) with render_backward_kernel (backward.hip): every pixel starts at its own last contributor
 //     with T = final_t; the record's floor -ln(255 o) - 1e-3 skips strips it is too faint for before the exponential; power in
 //     the forward's operation order, exp_ref, alpha >= 1/255: the forward's set; T_i = T_{i+1} rcp(1 - alpha); raw > 0.99 zeroes
-//     a pixel's share of the geometry but not the walk; u = K d by two multiply-adds.
+//     a pixel's share of the geometry but not the walk; u = K d by two multiply-adds; GeometrySums: its lines from dL_dalpha on.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 #include "blend_core.hpp"           // (and, through gsr_common.hpp, frame_policy.hpp: tile_band)
 #include "blockbin.hpp"             // (lists_of_receipt, tile_order_of_call)
@@ -229,6 +233,56 @@ struct BackPixel {
     __device__ __forceinline__ float uy() const { return __builtin_fmaf(co.y, dx, co.z * dy); }
 };
 
+// Which of wave_sum8's eight totals this lane is left with (wave_reduce.hpp: lane 8 r holds value kSumOfRow[r]); -1: none.
+__device__ __forceinline__ int sum8_of_lane(int lane) {
+    constexpr int kSumOfRow[8] = {0, 4, 2, 6, 1, 5, 3, 7};
+    return (lane & 7) == 0 ? kSumOfRow[lane >> 3] : -1;
+}
+
+// The geometry tail of a back walk whose pass forms a dL_dalpha per (record, pixel): render_backward_kernel's lines (backward.hip)
+// from there on — the clamp rule raw > 0.99, dpow, gop, u = K d, the pixel-by-pixel cov2D sums — and the filing of a record's
+// nine sums into slots 0..5 and 9..11 of the double sums a gsr_backward of the same frame then reads (gsr_backward_args.sums_f64;
+// slots 6..8, the colour's, are not touched). This lane's sums over its four pixels of the record in hand.
+struct GeometrySums {
+    static constexpr uint32_t kFloats = 12;      // the layout of gsr_backward_args.sums_f64 (backward.hip: kAccFloats)
+    float mx, my, A, B, C, op, m00, m01, m11;
+    __device__ __forceinline__ void clear() { mx = my = A = B = C = op = m00 = m01 = m11 = 0.0f; }
+    __device__ __forceinline__ void add(const BackPixel& px, const float dL_dalpha) {
+        const float dx = px.dx, dy = px.dy;
+        const bool live = px.live();
+        const float gop = live ? px.G * dL_dalpha : 0.0f;
+        const float dpow = live ? px.raw * dL_dalpha : 0.0f;
+        op += gop;
+        A = __builtin_fmaf(-0.5f * dx * dx, dpow, A);
+        B = __builtin_fmaf(-(dx * dy), dpow, B);
+        C = __builtin_fmaf(-0.5f * dy * dy, dpow, C);
+        const float ux = px.ux(), uy = px.uy();
+        mx = __builtin_fmaf(-ux, dpow, mx);
+        my = __builtin_fmaf(-uy, dpow, my);
+        const float hux = 0.5f * dpow * ux, huy = 0.5f * dpow * uy;      // (the masked factor first: 0 x finite)
+        m00 = __builtin_fmaf(hux, ux, m00); m01 = __builtin_fmaf(hux, uy, m01); m11 = __builtin_fmaf(huy, uy, m11);
+    }
+    // Two reductions a record, one atomic per filing lane. The lane map and the reductions are one decision: of wave_sum8's
+    // eight, values 0..5 are slots 0..5, value kExtra is `extra` — a sum of the pass's own that rides along; what is returned is
+    // its total in the lane where sum8_of_lane is kExtra — and value 7 is unused; wave_sum4 leaves value kSumOfRow4[r] in
+    // every lane of row r (lane 16 r + 4 files it): slots 9..11 and one unused. (slot is formed once, ahead of the walk, where
+    // the passes formed it themselves: inside file() features_backward_kernel<8, true> lost a wave per SIMD to registers)
+    static constexpr int kExtra = 6;
+    int slot;                                    // the slot this lane files, -1: none
+    __device__ __forceinline__ explicit GeometrySums(const int lane) {
+        constexpr int kSumOfRow4[4] = {9, 11, 10, 12};
+        const int of8 = sum8_of_lane(lane);
+        slot = (lane & 7) == 0 ? (of8 < kExtra ? of8 : -1) : ((lane & 15) == 4 && kSumOfRow4[lane >> 4] < 12 ? kSumOfRow4[lane >> 4] : -1);
+    }
+    __device__ __forceinline__ float file(double* geometry_sums, const size_t id, const int lane, const float extra) const {
+        const float t8 = wave_sum8(mx, my, A, B, C, op, extra, 0.0f, lane);
+        const float t4 = wave_sum4(m00, m01, m11, 0.0f);
+        const float total = (lane & 7) == 4 ? t4 : t8;
+        if (slot >= 0 && total != 0.0f) unsafeAtomicAdd(geometry_sums + kFloats * id + (uint32_t)slot, (double)total);
+        return t8;
+    }
+};
+
 // The whole walk of one tile. The pass's callables, all inlined:
 //   seed(k, pid)           for a pixel slot inside the image: loads the pass's own per-pixel inputs (g), zero for the others;
 //   start()                once, s.last and s.T set and a record to walk: what the pass forms of them (S);
@@ -388,6 +442,23 @@ inline WalkFrame walk_frame(const uint32_t* ranges, const uint32_t* point_list, 
     return f;
 }
 
+// For the passes whose argument struct (Args: gsr_features_args, gsr_distortion_args) names the frame's fields alike — what both
+// of a pass's calls check of them, in the header's order, the pass's own fields left to the pass; and the frame of such a struct.
+template <typename Args>
+inline int walk_pass_check(Args* a, FrameDims* d, bool* nothing) {
+    if (!a || a->struct_size != sizeof(Args)) return GSR_ERR_INVALID_ARG;
+    a->stage_ms = 0.0f;
+    if (a->num_gaussians <= 0 || a->width <= 0 || a->height <= 0) return GSR_ERR_INVALID_ARG;
+    if (!a->means2D || !a->conic_opacity || !a->ranges || !a->n_contrib || !a->final_t) return GSR_ERR_INVALID_ARG;
+    if (misaligned(a->means2D, 8) || misaligned(a->conic_opacity, 16) || misaligned(a->ranges, 8)) return GSR_ERR_INVALID_ARG;
+    return walk_check(a->receipt, a->num_gaussians, a->width, a->height, a->tile_row_begin, a->tile_row_end, false, a->point_list, d, nothing);
+}
+template <typename Args>
+inline WalkFrame walk_frame(const Args* a, const FrameDims& d) {
+    return walk_frame(a->ranges, a->point_list, a->means2D, a->conic_opacity, a->n_contrib, a->final_t, d, a->num_gaussians,
+                      a->receipt.num_rendered);
+}
+
 struct StageTimer {               // GSR_FLAG_PROFILE: the call's kernels between two events
     CallEvents<2> events;
     bool on = false;
@@ -434,6 +505,34 @@ inline int launch_finish_sums(size_t count, double* sums, float* out, hipStream_
     hipLaunchKernelGGL(finish_sums_kernel<V>, dim3((unsigned)finish_sums_workgroups(count)), dim3(256), 0, stream, count, sums, out);
     GSR_LAUNCH_CHECK("finish_sums_kernel");
     return GSR_OK;
+}
+
+// The call of such a pass once walk_pass_check has passed: launch(frame, workgroups, stream) is the pass's own kernel launch.
+// The caller says which call it is. Forward (backward == nullptr): the kernel runs whenever the band has a row, at R == 0 too —
+// every tile is then a tile without a list, and background and zeros get written. Backward: `backward` names the double sums
+// the kernel adds into and the output they are rounded to; the kernel runs only where there is a record to walk, in the forward
+// blend's tile order (the tiles that were slow there are the slow ones here: they go first, as they did there), and the sums
+// are finished either way: the output is written in full.
+struct WalkSums {
+    size_t count;
+    double* sums;
+    float* out;
+};
+template <typename Args, typename Launch>
+inline int walk_pass_call(Args* a, const FrameDims& d, bool nothing, const WalkSums* backward, Launch launch) {
+    const long long blocks = patch_workgroups(d.grid_x, d.row_end - d.row_begin);
+    if (exceeds_grid(blocks) || (backward && exceeds_grid(finish_sums_workgroups(backward->count)))) return GSR_ERR_TOO_LARGE;
+    // ---- nothing is refused from here on ----
+    hipStream_t stream = static_cast<hipStream_t>(a->stream);
+    StageTimer timer;
+    GSR_TRY(timer.begin((a->flags & GSR_FLAG_PROFILE) != 0, stream));
+    if (backward ? !nothing : d.row_begin != d.row_end) {
+        WalkFrame frame = walk_frame(a, d);
+        if (backward) frame.tile_order = tile_order_of_call(a->receipt, d.row_begin, d.row_end);
+        GSR_TRY(launch(frame, (unsigned)blocks, stream));
+    }
+    if (backward) GSR_TRY(launch_finish_sums<1>(backward->count, backward->sums, backward->out, stream));
+    return timer.end(stream, &a->stage_ms);
 }
 }  // namespace
 

@@ -84,11 +84,19 @@ class BackwardBuffers:
             self.sets.clear()
             self.scratch.clear()
 
-    def get(self, name: str, *shape, dtype=torch.float32, zero=False) -> torch.Tensor:
+    def get(self, name: str, *shape, dtype=torch.float32) -> torch.Tensor:
         """scratch[name], created with `shape` on first use."""
         if name not in self.scratch:
-            self.scratch[name] = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=self.device)
+            self.scratch[name] = torch.empty(shape, dtype=dtype, device=self.device)
         return self.scratch[name]
+
+    def sums(self, name: str, *shape) -> torch.Tensor:
+        """scratch[name] as the double sums of a pass: created zero, left zero by the library and never cleared here; a call
+        that needs more of them than the one kept (a larger C) takes a new one. The caller drops it if its call fails."""
+        t = self.scratch.get(name)
+        if t is None or t.numel() < int(np.prod(shape)):
+            t = self.scratch[name] = torch.zeros(shape, dtype=torch.float64, device=self.device)
+        return t
 
     def take(self, plan: backward_plan.BackwardPlan, semantics: str, with_cov3D: bool, into: "dict | None") -> dict:
         """{name: tensor} of every array `plan` gives a pointer, each from the source the plan names."""
@@ -294,10 +302,7 @@ class SplatRasterizer:
         if into is not None:
             assert set(into) <= {"out_color", "out_depth"}, sorted(into)
             for k, shape in (("out_color", (3, self.height, self.width)), ("out_depth", (self.height, self.width))):
-                t = into.get(k)
-                if t is not None:
-                    assert t.dtype == torch.float32 and t.device == self.device and t.is_contiguous(), k
-                    assert tuple(t.shape) == shape, (k, tuple(t.shape))
+                self._check_into(into.get(k), shape, k)
             out_color = into.get("out_color", out_color)
             out_depth = into.get("out_depth")
         a = self._forward_args(self.means3D, out_color)
@@ -413,29 +418,96 @@ class SplatRasterizer:
         return {"depth": v(st.depth, P, torch.float32).view(self.height, self.width),
                 "outColor": v(st.out_color, 3 * P, torch.float32).view(3, self.height, self.width)}
 
+    # -- what the passes over a drawn frame share ---------------------------------------------
+    def _map_frame(self, a, num_rendered: int) -> _capi.GeometryState:
+        """Points the frame fields of the args struct `a` — those it has of means2D, conic_opacity, ranges, n_contrib, final_t
+        and point_list — at what a forward call of `num_rendered` list entries left in the three chunks. Returns the geometry
+        state, for the caller that takes more of it."""
+        gst, ist, bst = _capi.GeometryState(), _capi.ImageState(), _capi.BinningState()
+        self.lib.gsr_geometry_from_chunk(self.geom.base(), self.num_gaussians, C.byref(gst))
+        self.lib.gsr_image_from_chunk(self.image.base(), self.width * self.height, C.byref(ist))
+        self.lib.gsr_binning_from_chunk(self.binning.base(), num_rendered, C.byref(bst))
+        frame = {"means2D": gst.means2D, "conic_opacity": gst.conic_opacity, "ranges": ist.ranges, "n_contrib": ist.n_contrib,
+                 "final_t": ist.accum_alpha, "point_list": bst.values}
+        for k, _ in a._fields_:
+            if k in frame:
+                setattr(a, k, frame[k])
+        return gst
+
+    def _walk_args(self, kind, rcpt: _capi.ForwardReceipt, tile_rows: "tuple[int, int] | None", profile: bool):
+        """A gsr_features_args / gsr_distortion_args (`kind`) with the fields the two share, for the frame of `rcpt` on torch's
+        current stream; the pass's own fields are left zero."""
+        a = kind()
+        a.struct_size = C.sizeof(kind)
+        a.flags = _capi.GSR_FLAG_PROFILE if profile else 0
+        a.num_gaussians, a.width, a.height = self.num_gaussians, self.width, self.height
+        self._map_frame(a, int(rcpt.num_rendered))
+        a.receipt = rcpt
+        if tile_rows is None:                    # (the band the draw() itself had: the calls take no other)
+            tile_rows = (int(rcpt.tile_row_begin), int(rcpt.tile_row_end))
+        a.tile_row_begin, a.tile_row_end = int(tile_rows[0]), int(tile_rows[1])
+        a.stream = _capi.stream(self.device)
+        return a
+
+    def _check_into(self, t: "torch.Tensor | None", shape: tuple, what=None) -> None:
+        """A tensor of the caller's that the library is given as it stands (None: the caller gave none): float32, on this device,
+        contiguous, exactly `shape`."""
+        if t is None:
+            return
+        assert t.dtype == torch.float32 and t.device == self.device and t.is_contiguous(), what
+        assert tuple(t.shape) == tuple(shape), (what, tuple(t.shape))
+
+    def _new_output(self, rcpt: _capi.ForwardReceipt, tile_rows: "tuple[int, int] | None", shape: tuple) -> torch.Tensor:
+        """A new per-pixel output of a pass: the call writes the rows of its band only — tile_rows, else the receipt's own band —
+        so anything but the whole frame starts from zeros."""
+        whole = tile_rows is None and (int(rcpt.tile_row_begin), int(rcpt.tile_row_end)) == (0, (self.height + 15) // 16)
+        return (torch.empty if whole else torch.zeros)(shape, dtype=torch.float32, device=self.device)
+
+    def _call(self, fn: str, a, *, drop: tuple = (), ms: "str | None" = None, sync: bool = False) -> None:
+        """One library call on `a` with the tail the passes share: if it fails, the double sums named in `drop` go (a call that
+        failed half way may have left sums behind: the next starts from zeroed ones); `ms` names the last_*_ms attribute that
+        gets the call's stage_ms, None unless the call was profiled; sync waits for the stream."""
+        try:
+            _capi.call(fn, C.byref(a), device=self.device)
+        except _capi.GsrError:
+            for name in drop:
+                self._bw.scratch.pop(name, None)
+            raise
+        if ms is not None:
+            setattr(self, ms, float(a.stage_ms) if a.flags & _capi.GSR_FLAG_PROFILE else None)
+        if sync:
+            torch.cuda.current_stream(self.device).synchronize()
+
+    def _check_dL_dalpha(self, dL_dalpha: "torch.Tensor | None") -> None:
+        """backward()'s and absgrad()'s refusal of a dL_dalpha (checked before the first copy or launch of the call)."""
+        if dL_dalpha is not None:
+            assert isinstance(dL_dalpha, torch.Tensor) and dL_dalpha.dtype == torch.float32, "dL_dalpha: a float32 tensor"
+            assert dL_dalpha.device == self.device, ("dL_dalpha", dL_dalpha.device, self.device)
+            assert tuple(dL_dalpha.shape) == (self.height, self.width), ("dL_dalpha", tuple(dL_dalpha.shape))
+
+    def _depth_gradient(self, dL_ddepth: "torch.Tensor | None", depth: "bool | str | None"):
+        """(dL_ddepth as the library reads it, the depth channel's mode) of backward() and absgrad(); (None, None) without one."""
+        if dL_ddepth is None:
+            return None, None
+        gd = dL_ddepth.to(device=self.device, dtype=torch.float32).contiguous()
+        assert gd.shape == (self.height, self.width)
+        return gd, backward_plan.depth_mode(depth, self.last_depth)
+
     # -- backward pass (BASELINE config 5; no counterpart in the reference) ------------------
     def _backward_args(self, rcpt: "_capi.ForwardReceipt | None", col: "torch.Tensor | None", semantics: str,
                        sh_degree: int) -> _capi.BackwardArgs:
         """gsr_backward_args with what does not depend on the gradients asked for: the scene, the camera and what the forward
         call of `rcpt` left in the three chunks (col: its precomputed colours, else its geomState.rgb)."""
-        n = self.num_gaussians
-        gst, ist, bst = _capi.GeometryState(), _capi.ImageState(), _capi.BinningState()
-        self.lib.gsr_geometry_from_chunk(self.geom.base(), n, C.byref(gst))
-        self.lib.gsr_image_from_chunk(self.image.base(), self.width * self.height, C.byref(ist))
-        num_rendered = int(rcpt.num_rendered) if rcpt is not None else self.last_num_rendered
-        self.lib.gsr_binning_from_chunk(self.binning.base(), num_rendered, C.byref(bst))
         a = _capi.BackwardArgs()
         a.struct_size = C.sizeof(_capi.BackwardArgs)
+        gst = self._map_frame(a, int(rcpt.num_rendered) if rcpt is not None else self.last_num_rendered)
         if semantics == "inria":
             a.flags = _capi.GSR_FLAG_SEMANTICS_INRIA
             a.cam_pos, a.shs, a.clamped, a.sh_dims = self._cam_pos.data_ptr(), self.shs.data_ptr(), gst.clamped, int(sh_degree)
-        a.num_gaussians, a.width, a.height = n, self.width, self.height
+        a.num_gaussians, a.width, a.height = self.num_gaussians, self.width, self.height
         a.background = self.background.data_ptr()
-        a.means2D, a.conic_opacity, a.cov3D = gst.means2D, gst.conic_opacity, gst.cov3D
+        a.cov3D, a.radii = gst.cov3D, gst.internal_radii
         a.colors = col.data_ptr() if col is not None else gst.rgb
-        a.radii = gst.internal_radii
-        a.ranges, a.n_contrib, a.final_t = ist.ranges, ist.n_contrib, ist.accum_alpha
-        a.point_list = bst.values
         a.means3D, a.view_matrix = self.means3D.data_ptr(), self._view.data_ptr()
         a.tan_fovx, a.tan_fovy = self._tan
         a.stream = _capi.stream(self.device)
@@ -508,21 +580,13 @@ class SplatRasterizer:
         col = self._colors_of(rcpt)
         plan = backward_plan.plan_backward(semantics, with_cov3D, wide_sums, None if outputs is None else tuple(outputs),
                                            None if into is None else tuple(into), dL_ddepth is not None, camera, col is not None)
-        if dL_dalpha is not None:                # (checked before the first copy or launch of this call)
-            assert isinstance(dL_dalpha, torch.Tensor) and dL_dalpha.dtype == torch.float32, "dL_dalpha: a float32 tensor"
-            assert dL_dalpha.device == dev, ("dL_dalpha", dL_dalpha.device, dev)
-            assert tuple(dL_dalpha.shape) == (self.height, self.width), ("dL_dalpha", tuple(dL_dalpha.shape))
+        self._check_dL_dalpha(dL_dalpha)
         g = dL_dout.to(device=dev, dtype=torch.float32).contiguous()
         assert g.shape == (3, self.height, self.width)
         for k, t in (into or {}).items():
             if k != "camera":
-                assert t.dtype == torch.float32 and t.device == dev and t.is_contiguous(), k
-                assert tuple(t.shape) == (n, ROW_FLOATS[k]), k
-        mode = None
-        if dL_ddepth is not None:
-            gd = dL_ddepth.to(device=dev, dtype=torch.float32).contiguous()
-            assert gd.shape == (self.height, self.width)
-            mode = backward_plan.depth_mode(depth, self.last_depth)
+                self._check_into(t, (n, ROW_FLOATS[k]), k)
+        gd, mode = self._depth_gradient(dL_ddepth, depth)
         self._bw.fit(n)
         arrays = self._bw.take(plan, semantics, with_cov3D, into)
         a = self._backward_args(rcpt, col, semantics, sh_degree)
@@ -533,9 +597,9 @@ class SplatRasterizer:
         for k, t in arrays.items():             # (the fields of gsr_backward_args carry the arrays' names)
             setattr(a, k, t.data_ptr())
         if wide_sums:
-            a.sums_f64 = self._bw.get("sums_f64", n, 12, dtype=torch.float64, zero=True).data_ptr()
+            a.sums_f64 = self._bw.sums("sums_f64", n, 12).data_ptr()
             if dL_ddepth is not None:
-                a.depth_sums_f64 = self._bw.get("depth_sums_f64", n, dtype=torch.float64, zero=True).data_ptr()
+                a.depth_sums_f64 = self._bw.sums("depth_sums_f64", n).data_ptr()
         if plan.chain_inputs:
             a.proj_matrix, a.scales, a.rotations = self._proj.data_ptr(), self.scales.data_ptr(), self.rotations.data_ptr()
             a.scale_modifier = scale_modifier
@@ -544,7 +608,7 @@ class SplatRasterizer:
         feature_call = None
         if features is not None:
             feature_call, feature_keep = self._features_call(rcpt, features[0], features[2] if len(features) > 2 else None,
-                                                             dL_dout=features[1], profile=profile)
+                                                             dL_dout=features[1], tile_rows=tile_rows, profile=profile)
         distortion_call = None
         if distortion is not None:
             distortion_call, distortion_keep = self._distortion_call(rcpt, distortion[0], distortion_power, distortion_moments,
@@ -552,8 +616,6 @@ class SplatRasterizer:
         try:
             if feature_call is not None:        # its geometry sums go where gsr_backward's go: that call chains the total
                 feature_call.geometry_sums_f64 = a.sums_f64
-                if tile_rows is not None:
-                    feature_call.tile_row_begin, feature_call.tile_row_end = int(tile_rows[0]), int(tile_rows[1])
                 _capi.call("gsr_features_backward", C.byref(feature_call), device=dev)
             if distortion_call is not None:     # (likewise; both passes may seed the same sums)
                 distortion_call.geometry_sums_f64 = a.sums_f64
@@ -599,42 +661,24 @@ class SplatRasterizer:
         c = int(features.shape[1])
         f = features.detach().contiguous()
         keep = [f]
-        gst, ist, bst = _capi.GeometryState(), _capi.ImageState(), _capi.BinningState()
-        self.lib.gsr_geometry_from_chunk(self.geom.base(), n, C.byref(gst))
-        self.lib.gsr_image_from_chunk(self.image.base(), self.width * self.height, C.byref(ist))
-        self.lib.gsr_binning_from_chunk(self.binning.base(), int(rcpt.num_rendered), C.byref(bst))
-        a = _capi.FeaturesArgs()
-        a.struct_size = C.sizeof(_capi.FeaturesArgs)
-        a.flags = _capi.GSR_FLAG_PROFILE if profile else 0
-        a.num_gaussians, a.width, a.height, a.channels = n, self.width, self.height, c
-        a.means2D, a.conic_opacity = gst.means2D, gst.conic_opacity
-        a.ranges, a.n_contrib, a.final_t = ist.ranges, ist.n_contrib, ist.accum_alpha
-        a.point_list = bst.values
-        a.receipt = rcpt
-        a.features = f.data_ptr()
+        a = self._walk_args(_capi.FeaturesArgs, rcpt, tile_rows, profile)
+        a.channels, a.features = c, f.data_ptr()
         if background is not None:
             bg = _dev(background, dev).reshape(-1)
             assert bg.numel() == c, ("background", tuple(bg.shape), c)
             keep.append(bg)
             a.background = bg.data_ptr()
-        if tile_rows is None:                    # (the band the draw() itself had: the calls take no other)
-            tile_rows = (int(rcpt.tile_row_begin), int(rcpt.tile_row_end))
-        a.tile_row_begin, a.tile_row_end = int(tile_rows[0]), int(tile_rows[1])
-        a.stream = _capi.stream(dev)
         if out is not None:
             a.out = out.data_ptr()
             keep.append(out)
         if dL_dout is not None:
             g = dL_dout.to(device=dev, dtype=torch.float32).contiguous()
             assert tuple(g.shape) == (c, self.height, self.width), ("dL_dfeature_map", tuple(g.shape))
-            if into is not None:
-                assert into.dtype == torch.float32 and into.device == dev and into.is_contiguous() and tuple(into.shape) == (n, c)
+            self._check_into(into, (n, c))
             res = into if into is not None else torch.empty((n, c), dtype=torch.float32, device=dev)
             self._bw.fit(n)
-            scratch = self._bw.scratch.get("feature_sums_f64")
-            if scratch is None or scratch.numel() < n * c:       # (all zero between calls: a larger C takes a new one)
-                scratch = self._bw.scratch["feature_sums_f64"] = torch.zeros(n * c, dtype=torch.float64, device=dev)
-            a.dL_dout, a.dL_dfeatures, a.feature_sums_f64 = g.data_ptr(), res.data_ptr(), scratch.data_ptr()
+            a.dL_dout, a.dL_dfeatures = g.data_ptr(), res.data_ptr()
+            a.feature_sums_f64 = self._bw.sums("feature_sums_f64", n * c).data_ptr()
             keep += [g, res]
         return a, keep
 
@@ -653,16 +697,10 @@ class SplatRasterizer:
         assert rcpt is not None, "render_features needs the receipt of a draw()"
         assert isinstance(features, torch.Tensor) and features.dim() == 2, "features: [N,C]"
         shape = (int(features.shape[1]), self.height, self.width)
-        if into is not None:
-            assert into.dtype == torch.float32 and into.device == self.device and into.is_contiguous() and tuple(into.shape) == shape
-        # (a call writes the rows of its band only — tile_rows, else the receipt's own band: anything but the whole frame starts from zeros)
-        whole = tile_rows is None and (int(rcpt.tile_row_begin), int(rcpt.tile_row_end)) == (0, (self.height + 15) // 16)
-        out = into if into is not None else (torch.empty if whole else torch.zeros)(shape, dtype=torch.float32, device=self.device)
+        self._check_into(into, shape)
+        out = into if into is not None else self._new_output(rcpt, tile_rows, shape)
         a, _keep = self._features_call(rcpt, features, background, out=out, tile_rows=tile_rows, profile=profile)
-        _capi.call("gsr_features_forward", C.byref(a), device=self.device)
-        self.last_features_ms = float(a.stage_ms) if profile else None
-        if sync:
-            torch.cuda.current_stream(self.device).synchronize()
+        self._call("gsr_features_forward", a, ms="last_features_ms", sync=sync)
         return out
 
     def features_backward(self, features: torch.Tensor, dL_dout: torch.Tensor, *, background=None,
@@ -676,14 +714,7 @@ class SplatRasterizer:
         rcpt = self.last_receipt if receipt is None else receipt
         assert rcpt is not None, "features_backward needs the receipt of a draw()"
         a, keep = self._features_call(rcpt, features, background, dL_dout=dL_dout, into=into, tile_rows=tile_rows, profile=profile)
-        try:
-            _capi.call("gsr_features_backward", C.byref(a), device=self.device)
-        except _capi.GsrError:
-            self._bw.scratch.pop("feature_sums_f64", None)     # (a call that failed half way may have left sums behind)
-            raise
-        self.last_features_ms = float(a.stage_ms) if profile else None
-        if sync:
-            torch.cuda.current_stream(self.device).synchronize()
+        self._call("gsr_features_backward", a, drop=("feature_sums_f64",), ms="last_features_ms", sync=sync)
         return keep[-1]
 
     # -- the depth distortion map (include/gsrast_amd_distortion.h) ---------------------------
@@ -695,8 +726,7 @@ class SplatRasterizer:
                 "distortion: the moments kept by this rasterizer are stale — they are those of render_distortion for another "
                 "frame or power (or there are none): call render_distortion(values, power=...) for this draw() first")
             moments = kept
-        assert moments.dtype == torch.float32 and moments.device == self.device and moments.is_contiguous(), "moments"
-        assert tuple(moments.shape) == (3, self.height, self.width), ("moments", tuple(moments.shape))
+        self._check_into(moments, (3, self.height, self.width), "moments")
         return moments
 
     def _distortion_call(self, rcpt: _capi.ForwardReceipt, values: torch.Tensor, power: int, moments: torch.Tensor, *,
@@ -710,37 +740,19 @@ class SplatRasterizer:
         assert values.dim() == 1 and values.shape[0] == n, ("values", tuple(values.shape), n)
         v = values.detach().contiguous()
         keep = [v, moments]
-        gst, ist, bst = _capi.GeometryState(), _capi.ImageState(), _capi.BinningState()
-        self.lib.gsr_geometry_from_chunk(self.geom.base(), n, C.byref(gst))
-        self.lib.gsr_image_from_chunk(self.image.base(), self.width * self.height, C.byref(ist))
-        self.lib.gsr_binning_from_chunk(self.binning.base(), int(rcpt.num_rendered), C.byref(bst))
-        a = _capi.DistortionArgs()
-        a.struct_size = C.sizeof(_capi.DistortionArgs)
-        a.flags = _capi.GSR_FLAG_PROFILE if profile else 0
-        a.num_gaussians, a.width, a.height, a.power = n, self.width, self.height, int(power)
-        a.means2D, a.conic_opacity = gst.means2D, gst.conic_opacity
-        a.ranges, a.n_contrib, a.final_t = ist.ranges, ist.n_contrib, ist.accum_alpha
-        a.point_list = bst.values
-        a.receipt = rcpt
-        a.values, a.moments = v.data_ptr(), moments.data_ptr()
-        if tile_rows is None:                    # (the band the draw() itself had: the calls take no other)
-            tile_rows = (int(rcpt.tile_row_begin), int(rcpt.tile_row_end))
-        a.tile_row_begin, a.tile_row_end = int(tile_rows[0]), int(tile_rows[1])
-        a.stream = _capi.stream(dev)
+        a = self._walk_args(_capi.DistortionArgs, rcpt, tile_rows, profile)
+        a.power, a.values, a.moments = int(power), v.data_ptr(), moments.data_ptr()
         if out is not None:
             a.out = out.data_ptr()
             keep.append(out)
         if dL_dout is not None:
             g = dL_dout.to(device=dev, dtype=torch.float32).contiguous()
             assert tuple(g.shape) == (self.height, self.width), ("dL_ddistortion_map", tuple(g.shape))
-            if into is not None:
-                assert into.dtype == torch.float32 and into.device == dev and into.is_contiguous() and tuple(into.shape) == (n,)
+            self._check_into(into, (n,))
             res = into if into is not None else torch.empty((n,), dtype=torch.float32, device=dev)
             self._bw.fit(n)
-            scratch = self._bw.scratch.get("distortion_sums_f64")
-            if scratch is None or scratch.numel() < n:           # (all zero between calls)
-                scratch = self._bw.scratch["distortion_sums_f64"] = torch.zeros(n, dtype=torch.float64, device=dev)
-            a.dL_dout, a.dL_dvalues, a.value_sums_f64 = g.data_ptr(), res.data_ptr(), scratch.data_ptr()
+            a.dL_dout, a.dL_dvalues = g.data_ptr(), res.data_ptr()
+            a.value_sums_f64 = self._bw.sums("distortion_sums_f64", n).data_ptr()
             keep += [g, res]
         return a, keep
 
@@ -760,17 +772,13 @@ class SplatRasterizer:
         assert rcpt is not None, "render_distortion needs the receipt of a draw()"
         assert power in (1, 2), ("power", power)
         shape = (self.height, self.width)
-        if into is not None:
-            assert into.dtype == torch.float32 and into.device == self.device and into.is_contiguous() and tuple(into.shape) == shape
-        whole = tile_rows is None and (int(rcpt.tile_row_begin), int(rcpt.tile_row_end)) == (0, (self.height + 15) // 16)
-        new = torch.empty if whole else torch.zeros
-        out = into if into is not None else new(shape, dtype=torch.float32, device=self.device)
-        moments = new((3,) + shape, dtype=torch.float32, device=self.device)
+        self._check_into(into, shape)
+        out = into if into is not None else self._new_output(rcpt, tile_rows, shape)
+        moments = self._new_output(rcpt, tile_rows, (3,) + shape)
         a, _keep = self._distortion_call(rcpt, values, power, moments, out=out, tile_rows=tile_rows, profile=profile)
         self._distortion_moments = (None, 0, None)
-        _capi.call("gsr_distortion_forward", C.byref(a), device=self.device)
+        self._call("gsr_distortion_forward", a, ms="last_distortion_ms")
         self._distortion_moments = (int(rcpt.serial), int(power), moments)
-        self.last_distortion_ms = float(a.stage_ms) if profile else None
         if sync:
             torch.cuda.current_stream(self.device).synchronize()
         return out
@@ -790,14 +798,7 @@ class SplatRasterizer:
         assert power in (1, 2), ("power", power)
         a, keep = self._distortion_call(rcpt, values, power, self._distortion_moments_of(rcpt, power, moments), dL_dout=dL_dmap,
                                         into=into, tile_rows=tile_rows, profile=profile)
-        try:
-            _capi.call("gsr_distortion_backward", C.byref(a), device=self.device)
-        except _capi.GsrError:
-            self._bw.scratch.pop("distortion_sums_f64", None)   # (a call that failed half way may have left sums behind)
-            raise
-        self.last_distortion_ms = float(a.stage_ms) if profile else None
-        if sync:
-            torch.cuda.current_stream(self.device).synchronize()
+        self._call("gsr_distortion_backward", a, drop=("distortion_sums_f64",), ms="last_distortion_ms", sync=sync)
         return keep[-1]
 
     def absgrad(self, dL_dout: torch.Tensor, *, dL_ddepth: "torch.Tensor | None" = None, depth: "bool | str | None" = None,
@@ -818,19 +819,11 @@ class SplatRasterizer:
         rcpt = self.last_receipt if receipt is None else receipt
         assert rcpt is not None, "absgrad needs the receipt of a draw()"
         assert semantics in ("gscuda", "inria"), semantics
-        if dL_dalpha is not None:
-            assert isinstance(dL_dalpha, torch.Tensor) and dL_dalpha.dtype == torch.float32, "dL_dalpha: a float32 tensor"
-            assert dL_dalpha.device == dev, ("dL_dalpha", dL_dalpha.device, dev)
-            assert tuple(dL_dalpha.shape) == (self.height, self.width), ("dL_dalpha", tuple(dL_dalpha.shape))
+        self._check_dL_dalpha(dL_dalpha)
         g = dL_dout.to(device=dev, dtype=torch.float32).contiguous()
         assert g.shape == (3, self.height, self.width)
-        if into is not None:
-            assert into.dtype == torch.float32 and into.device == dev and into.is_contiguous() and tuple(into.shape) == (n, 2)
-        mode = None
-        if dL_ddepth is not None:
-            gd = dL_ddepth.to(device=dev, dtype=torch.float32).contiguous()
-            assert gd.shape == (self.height, self.width)
-            mode = backward_plan.depth_mode(depth, self.last_depth)
+        self._check_into(into, (n, 2))
+        gd, mode = self._depth_gradient(dL_ddepth, depth)
         self._bw.fit(n)
         b = self._backward_args(rcpt, self._colors_of(rcpt), semantics, 3)
         b.dL_dout_color = g.data_ptr()
@@ -846,15 +839,8 @@ class SplatRasterizer:
         ga = dL_dalpha.contiguous() if dL_dalpha is not None else None
         a.dL_dout_alpha = ga.data_ptr() if ga is not None else None
         a.abs_dL_dmean2D = out.data_ptr()
-        a.sums_f64 = self._bw.get("absgrad_sums_f64", n, 2, dtype=torch.float64, zero=True).data_ptr()
-        try:
-            _capi.call("gsr_absgrad", C.byref(a), device=dev)
-        except _capi.GsrError:
-            self._bw.scratch.pop("absgrad_sums_f64", None)     # (a call that failed half way may have left sums behind)
-            raise
-        self.last_absgrad_ms = float(a.stage_ms) if profile else None
-        if sync:
-            torch.cuda.current_stream(dev).synchronize()
+        a.sums_f64 = self._bw.sums("absgrad_sums_f64", n, 2).data_ptr()
+        self._call("gsr_absgrad", a, drop=("absgrad_sums_f64",), ms="last_absgrad_ms", sync=sync)
         return out
 
     def _colors_of(self, rcpt: "_capi.ForwardReceipt | None") -> "torch.Tensor | None":
@@ -907,15 +893,12 @@ class SplatRasterizer:
         if depth:
             a.dL_ddepths = ptr("dL_ddepths")
         if into is not None:
-            assert into.dtype == torch.float32 and into.device == dev and into.is_contiguous() and tuple(into.shape) == (35,)
+            self._check_into(into, (35,))
             g = into
         a.dL_dview_matrix, a.dL_dproj_matrix, a.dL_dcam_pos = g[0:16].data_ptr(), g[16:32].data_ptr(), g[32:35].data_ptr()
         a.scratch = scratch.data_ptr()
         a.stream = _capi.stream(dev)
-        _capi.call("gsr_camera_backward", C.byref(a), device=dev)
-        self.last_camera_ms = float(a.stage_ms) if profile else None
-        if sync:
-            torch.cuda.current_stream(dev).synchronize()
+        self._call("gsr_camera_backward", a, ms="last_camera_ms", sync=sync)
         return {"dL_dview_matrix": g[0:16], "dL_dproj_matrix": g[16:32], "dL_dcam_pos": g[32:35]}
 
     # -- state inspection (what the reference's Inspector does through fromChunk) ------

@@ -1,4 +1,5 @@
-"""The passes that walk a drawn frame's sorted lists — gsr_contribution, gsr_absgrad, gsr_features_forward / _backward — through
+"""The passes that walk a drawn frame's sorted lists — gsr_contribution, gsr_absgrad, gsr_features_forward / _backward,
+gsr_distortion_forward / _backward — through
 this tree's library and through the parent commit's, in one process, one GPU. The parent's library is built from a checkout
 of that commit (python -m gsrast_amd.build there) and named with --parent-lib; the passes' signatures are the same in both, so
 every entry point binds. Each library gets a rasterizer of its own and draws its own frame. Two parts:
@@ -6,12 +7,15 @@ every entry point binds. Each library gets a rasterizer of its own and draws its
      receives at most one atomic per slot, so the double sums do not depend on the order anything arrives in — every output of
      the passes: the contribution's four arrays with and without `dominant`; absgrad for a colour gradient and for colour +
      depth + alpha; the feature map, dL_dfeatures without geometry sums, and every output of backward(features=...) (with
-     them), at C = 3 and 17. On edge_scene() (3 x 2 tiles, partial at both edges) the contribution arrays (integer atomics) and
-     the feature map (no atomics). Any difference ends the run with exit status 1.
+     them), at C = 3 and 17; the distortion map, its three moment planes, dL_dvalues without geometry sums and every output of
+     backward(distortion=...), at power 1 and 2. On edge_scene() (3 x 2 tiles, partial at both edges) the contribution arrays
+     (integer atomics), the feature map, the distortion map and its moments (no atomics). Any difference ends the run with
+     exit status 1.
   2. time. The bench frame (1920 x 1080, garden_like), drawn without a tile history so that both sides take the tiles in patch
      order: the passes' own stage_ms (GSR_FLAG_PROFILE) for the contribution with
      and without `dominant`, absgrad with and without depth, and the features forward and backward at C = 3 and 16, the backward
-     with and without geometry sums: REPS rounds of parent (a), this tree (a), parent (b), this tree (b). The rule: this tree's
+     with and without geometry sums, and the distortion forward and backward at power 2 and 1, the backward with and without
+     geometry sums: REPS rounds of parent (a), this tree (a), parent (b), this tree (b). The rule: this tree's
      median (the mean of its two series' medians) may exceed the parent's by no more than the parent's own inter-quartile spread
      over its two series (lowest first quartile to highest third quartile).
 Usage: python scripts/walk_passes_cost.py --parent-lib PATH [--reps N] [--splats N] [--out FILE] [--only-bits]
@@ -49,7 +53,8 @@ def load_parent(path):
     """The parent commit's library beside this tree's: every entry point gets this tree's signature."""
     P = C.CDLL(os.path.abspath(path))
     for table in (_capi.SIGNATURES, _capi.INIT_SIGNATURES, _capi.OPACITY_SIGNATURES, _capi.MCMC_SIGNATURES, _capi.CONTRIB_SIGNATURES,
-                  _capi.ANTIALIAS_SIGNATURES, _capi.FILTER3D_SIGNATURES, _capi.ABSGRAD_SIGNATURES, _capi.FEATURES_SIGNATURES):
+                  _capi.ANTIALIAS_SIGNATURES, _capi.FILTER3D_SIGNATURES, _capi.ABSGRAD_SIGNATURES, _capi.FEATURES_SIGNATURES,
+                  _capi.DISTORTION_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(P, name)
             fn.restype, fn.argtypes = res, args
@@ -108,6 +113,7 @@ def bits(P, T, out):
         zeros = torch.zeros((3, h, w), device=DEV)
         feats = {c: (torch.randn((n, c), generator=gen).to(DEV), torch.randn((c, h, w), generator=gen).to(DEV),
                      torch.randn((c,), generator=gen).to(DEV)) for c in (3, 17)}
+        V, GV = torch.randn((n,), generator=gen).to(DEV), torch.randn((h, w), generator=gen).to(DEV)
         got = []
         for side in sides:
             def passes(r):
@@ -115,6 +121,12 @@ def bits(P, T, out):
                 res = {"contribution, all four": contribution(r, WHAT)[0], "contribution, without dominant": contribution(r, WHAT[:3])[0]}
                 for c, (F, G, bg) in feats.items():
                     res[f"feature map, C = {c}"] = r.render_features(F, background=bg).clone()
+                for q in (1, 2):
+                    res[f"distortion map, power {q}"] = r.render_distortion(V, power=q).clone()
+                    res[f"distortion moments, power {q}"] = r._distortion_moments[2].clone()
+                    if one_tile:           # (each power's backward calls behind its own forward: they read the moments it kept)
+                        res[f"dL_dvalues without geometry, power {q}"] = r.distortion_backward(V, GV, power=q).clone()
+                        res[f"backward(distortion=...), power {q}"] = {k: v.clone() for k, v in r.backward(zeros, distortion=(V, GV, q)).items()}
                 if not one_tile:
                     return res
                 res["absgrad, colour"] = r.absgrad(gc).clone()
@@ -182,6 +194,22 @@ def times(P, T, out):
             return r.last_features_ms
         passes.update({f"features forward, C = {c}": fwd, f"features backward without geometry, C = {c}": bwd,
                        f"features backward with geometry, C = {c}": joint})
+    V, GV = torch.randn((n,), generator=gen).to(dev), torch.randn((H, W), generator=gen).to(dev)
+    dmap, dV = torch.empty((H, W), device=dev), torch.empty((n,), device=dev)
+    for q in (2, 1):
+        def dfwd(r, q=q):
+            r.render_distortion(V, power=q, into=dmap, profile=True)
+            return r.last_distortion_ms
+
+        def dbwd(r, q=q):          # (the moments: those this side's render_distortion of this power kept, the line before this one)
+            r.distortion_backward(V, GV, power=q, into=dV, profile=True)
+            return r.last_distortion_ms
+
+        def djoint(r, q=q):
+            r.backward(zeros, distortion=(V, GV, q), profile=True)
+            return r.last_distortion_ms
+        passes.update({f"distortion forward, power {q}": dfwd, f"distortion backward without geometry, power {q}": dbwd,
+                       f"distortion backward with geometry, power {q}": djoint})
     ok = True
     for name, fn in passes.items():
         series = [("parent", "a"), ("this tree", "a"), ("parent", "b"), ("this tree", "b")]
