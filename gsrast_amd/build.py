@@ -22,6 +22,11 @@ ARCH = "gfx950"
 # order (no fused multiply-add), which is what makes integer outputs reproducible bit for bit.
 COMMON = (["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
           + os.environ.get("GSR_DEFINES", "").split())      # tuning experiments: GSR_DEFINES="-DX=1 ..."
+# Flags of single translation units. antialias.hip: the SLP vectoriser pairs the float32 divisions of the 2D covariance into
+# <2 x float> operations, and how it pairs them turns with the shape of the inlined code — one division formed twice, packed moves
+# around every pair. Its kernels are bound by their double arithmetic and their memory; without the pass they are shorter and keep
+# half the registers in the forward (no result changes: nothing is reassociated). profiles/chain_passes_cost.txt has the times.
+PER_FILE = {"antialias.hip": ["-fno-slp-vectorize"]}
 
 
 def _sources():
@@ -42,7 +47,7 @@ def _compile(src: str, force: bool, obj_dir: str = OBJ_DIR) -> str:
     stale = (force or not os.path.exists(obj) or os.path.getmtime(obj) < os.path.getmtime(spath)
              or os.path.getmtime(obj) < _headers_mtime())
     if stale:
-        cmd = [HIPCC] + COMMON + ["-c", spath, "-o", obj]
+        cmd = [HIPCC] + COMMON + PER_FILE.get(src, []) + ["-c", spath, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed for {src}:\n{r.stdout}\n{r.stderr}")

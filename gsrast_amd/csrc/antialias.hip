@@ -2,12 +2,12 @@
 // as its own per-Gaussian pass in front of gsr_forward, and its gradient behind gsr_backward. One lane per Gaussian,
 // streaming (HBM-bound): no LDS, no atomics, nothing crosses lanes.
 //
-// The float32 arithmetic of the 2D covariance restates the two preprocess kernels' (preprocess.hip, preprocess_inria.hip:
-// this file is compiled with -ffp-contract=off like them) operation for operation, so that d1 below is the forward call's
-// `det` bit for bit and the cull and clamp decisions are the forward's. The gradient restates the covariance part of
-// gsr_backward's chain (backward.hip, preprocess_backward_kernel), seeded with dL/dcov2D, in double like that one.
+// The float32 arithmetic of the 2D covariance is gaussian_chain.hpp's, which is the two preprocess kernels' operation for
+// operation, so that d1 below is the forward call's `det` bit for bit and the cull and clamp decisions are the forward's. The
+// gradient is the same header's double side, the covariance part of gsr_backward's chain (backward.hip,
+// preprocess_backward_kernel), seeded with dL/dcov2D.
 #include "../../include/gsrast_amd_antialias.h"
-#include "preprocess_common.hpp"
+#include "gaussian_chain.hpp"
 
 namespace gsr {
 namespace {
@@ -39,7 +39,7 @@ struct AntialiasParams {
 struct Compensation {
     float c = 1.0f;            // the factor
     bool flows = false;        // a gradient goes through c: the covariance was computed, d1 is finite and not zero, the floor is not active
-    bool hi_x = false, lo_x = false, hi_y = false, lo_y = false;      // t.x / t.z (t.y / t.z) was clamped at +lim (-lim)
+    RatioClamp clamp = {};     // t.x / t.z (t.y / t.z) was clamped at +lim (-lim)
 };
 
 template <bool INRIA>
@@ -47,28 +47,9 @@ __device__ __forceinline__ Compensation compensation_of(const AntialiasParams& p
                                                         const float4 sc, const float4 rot) {
     Compensation out;
     float tx, ty, tz;
-    M3 sigma;
-    M3 s;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int r = 0; r < 3; ++r) s.m[c][r] = 0.0f;
-    s.m[0][0] = p.scale_modifier * sc.x;
-    s.m[1][1] = p.scale_modifier * sc.y;
-    s.m[2][2] = p.scale_modifier * sc.z;
+    view_point<INRIA>(view, mean, tx, ty, tz);
     if constexpr (INRIA) {
-        const float* v = view;
-        tx = v[0] * mean.x + v[4] * mean.y + v[8] * mean.z + v[12];
-        ty = v[1] * mean.x + v[5] * mean.y + v[9] * mean.z + v[13];
-        tz = v[2] * mean.x + v[6] * mean.y + v[10] * mean.z + v[14];
         if (tz <= 0.2f) return out;
-        const float r = rot.x, x = rot.y, y = rot.z, z = rot.w;
-        M3 rm;
-        rm.m[0][0] = 1.0f - 2.0f * (y * y + z * z); rm.m[0][1] = 2.0f * (x * y - r * z); rm.m[0][2] = 2.0f * (x * z + r * y);
-        rm.m[1][0] = 2.0f * (x * y + r * z); rm.m[1][1] = 1.0f - 2.0f * (x * x + z * z); rm.m[1][2] = 2.0f * (y * z - r * x);
-        rm.m[2][0] = 2.0f * (x * z - r * y); rm.m[2][1] = 2.0f * (y * z + r * x); rm.m[2][2] = 1.0f - 2.0f * (x * x + y * y);
-        const M3 mm = mul3(s, rm);
-        sigma = mul3(transpose3(mm), mm);
     } else {
         const float* m = proj;
         const float phx = (m[0] * mean.x + m[4] * mean.y) + (m[8] * mean.z + m[12] * mean.w);
@@ -78,45 +59,10 @@ __device__ __forceinline__ Compensation compensation_of(const AntialiasParams& p
         const float one_over_w = 1.0f / (0.001f + phw);
         const float prx = one_over_w * phx, pry = one_over_w * phy, prz = one_over_w * phz;
         if (prz < 0.0f || prz > 1.0f || prx < -1.3f || prx > 1.3f || pry < -1.3f || pry > 1.3f) return out;
-        const float dq = (rot.x * rot.x + rot.y * rot.y) + (rot.z * rot.z + rot.w * rot.w);
-        const float inv = 1.0f / sqrtf(dq);
-        const float x = rot.x * inv, y = rot.y * inv, z = rot.z * inv, w = rot.w * inv;
-        M3 rm;
-        rm.m[0][0] = (float)(2.0 * (double)(x * x + y * y) - 1.0);
-        rm.m[0][1] = (float)(2.0 * (double)(y * z + x * w));
-        rm.m[0][2] = (float)(2.0 * (double)(y * w - x * z));
-        rm.m[1][0] = (float)(2.0 * (double)(y * z - x * w));
-        rm.m[1][1] = (float)(2.0 * (double)(x * x + z * z) - 1.0);
-        rm.m[1][2] = (float)(2.0 * (double)(z * w + x * y));
-        rm.m[2][0] = (float)(2.0 * (double)(y * w + x * z));
-        rm.m[2][1] = (float)(2.0 * (double)(z * w - x * y));
-        rm.m[2][2] = (float)(2.0 * (double)(x * x + w * w) - 1.0);
-        const M3 rs = mul3(rm, s);
-        sigma = mul3(rs, transpose3(rs));
-        const float* v = view;
-        tx = (v[0] * mean.x + v[4] * mean.y) + (v[8] * mean.z + v[12] * 1.0f);
-        ty = (v[1] * mean.x + v[5] * mean.y) + (v[9] * mean.z + v[13] * 1.0f);
-        tz = (v[2] * mean.x + v[6] * mean.y) + (v[10] * mean.z + v[14] * 1.0f);
     }
-    // Sigma is symmetric bit for bit (its entries (r, c) and (c, r) are the same products added in the same order): the
-    // six floats the preprocess kernels keep of it and spread again are this matrix
-    const float limx = 1.3f * p.tan_fovx, limy = 1.3f * p.tan_fovy;
-    const float rx = tx / tz, ry = ty / tz;
-    const float ux = fminr(limx, fmaxr(-limx, rx)) * tz;
-    const float uy = fminr(limy, fmaxr(-limy, ry)) * tz;
-    out.hi_x = limx < rx; out.lo_x = rx < -limx;
-    out.hi_y = limy < ry; out.lo_y = ry < -limy;
-    M3 j;
-    j.m[0][0] = p.focal_x / tz; j.m[0][1] = 0.0f; j.m[0][2] = (-p.focal_x * ux) / (tz * tz);
-    j.m[1][0] = 0.0f; j.m[1][1] = p.focal_y / tz; j.m[1][2] = (-p.focal_y * uy) / (tz * tz);
-    j.m[2][0] = 0.0f; j.m[2][1] = 0.0f; j.m[2][2] = 0.0f;
-    M3 wv;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int r = 0; r < 3; ++r) wv.m[c][r] = view[4 * r + c];
-    const M3 tm = mul3(wv, j);
-    const M3 cv = mul3(mul3(transpose3(tm), sigma), tm);
+    const M3 sigma = covariance_of<INRIA>(p.scale_modifier, sc, rotation_of<INRIA>(rot));
+    out.clamp = clamp_ratios_glm(tx, ty, tz, 1.3f * p.tan_fovx, 1.3f * p.tan_fovy);
+    const M3 cv = cov2d_of(view, out.clamp, tz, p.focal_x, p.focal_y, sigma);
     const float a0 = cv.m[0][0], b = cv.m[0][1], c0 = cv.m[1][1];
     const float d0 = a0 * c0 - b * b;
     const float ca = a0 + 0.3f, cc = c0 + 0.3f;
@@ -126,16 +72,6 @@ __device__ __forceinline__ Compensation compensation_of(const AntialiasParams& p
     out.c = sqrtf(fmaxr(kFloor, r));
     out.flows = kFloor < r;
     return out;
-}
-
-typedef float nt_f4 __attribute__((ext_vector_type(4)));
-// (the rows are read once: streaming loads, as in preprocess.hip)
-__device__ __forceinline__ float4 ld4(const float4* q) {
-    const nt_f4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f4*>(q));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void st4(float4* q, float x, float y, float z, float w) {
-    __builtin_nontemporal_store((nt_f4){x, y, z, w}, reinterpret_cast<nt_f4*>(q));
 }
 
 // Memory schedule of a wave: the view (and projection) matrix through the scalar cache, the three rows and the opacity of
@@ -176,60 +112,27 @@ __global__ __launch_bounds__(256) void antialias_backward_kernel(const Antialias
         g_o = k.c * g;
         const bool chain = k.flows && (p.dL_dmeans3D || p.dL_dscales || p.dL_drotations);
         if (chain) {
-            R v[16];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) v[i] = (R)view[i];
+            // t in double from the float32 inputs; the clamp decisions are the float32 forward's
             const R mx = (R)mean.x, my = (R)mean.y, mz = (R)mean.z;
-            const R t0 = v[0] * mx + v[4] * my + v[8] * mz + v[12];
-            const R t1 = v[1] * mx + v[5] * my + v[9] * mz + v[13];
-            const R tz = v[2] * mx + v[6] * my + v[10] * mz + v[14];
+            const R t0 = (R)view[0] * mx + (R)view[4] * my + (R)view[8] * mz + (R)view[12];
+            const R t1 = (R)view[1] * mx + (R)view[5] * my + (R)view[9] * mz + (R)view[13];
+            const R tz = (R)view[2] * mx + (R)view[6] * my + (R)view[10] * mz + (R)view[14];
             const R limx = (R)(1.3f * p.tan_fovx), limy = (R)(1.3f * p.tan_fovy);
-            const bool clx = k.hi_x || k.lo_x, cly = k.hi_y || k.lo_y;
-            const R cx = k.hi_x ? limx : (k.lo_x ? -limx : t0 / tz), cy = k.hi_y ? limy : (k.lo_y ? -limy : t1 / tz);
-            const R tx = cx * tz, ty = cy * tz;
-            const R fx = (R)p.focal_x, fy = (R)p.focal_y;
-            const R j00 = fx / tz, j11 = fy / tz, j02 = -fx * tx / (tz * tz), j12 = -fy * ty / (tz * tz);
-            // P = J W (2 x 3): cov2D = P Sigma P^T
-            R P[2][3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                P[0][c] = j00 * v[4 * c + 0] + j02 * v[4 * c + 2];
-                P[1][c] = j11 * v[4 * c + 1] + j12 * v[4 * c + 2];
-            }
-            // Sigma = Rm diag(sv^2) Rm^T in both profiles
+            const RatioClamp& cl = k.clamp;
+            const R cx = cl.hi_x ? limx : (cl.lo_x ? -limx : t0 / tz), cy = cl.hi_y ? limy : (cl.lo_y ? -limy : t1 / tz);
+            const ProjectionFrame f = projection_frame(view, tz, cx, cy, cl.clx, cl.cly, (R)p.focal_x, (R)p.focal_y);
             const R mod = (R)p.scale_modifier;
             const R sv[3] = {mod * (R)sc.x, mod * (R)sc.y, mod * (R)sc.z};
-            R Rm[3][3];
-            R qn[4] = {(R)rot.x, (R)rot.y, (R)rot.z, (R)rot.w};
-            [[maybe_unused]] R inv = 1.0;
-            if constexpr (INRIA) {
-                const R r = qn[0], x = qn[1], y = qn[2], z = qn[3];
-                Rm[0][0] = 1.0 - 2.0 * (y * y + z * z); Rm[0][1] = 2.0 * (x * y - r * z); Rm[0][2] = 2.0 * (x * z + r * y);
-                Rm[1][0] = 2.0 * (x * y + r * z); Rm[1][1] = 1.0 - 2.0 * (x * x + z * z); Rm[1][2] = 2.0 * (y * z - r * x);
-                Rm[2][0] = 2.0 * (x * z - r * y); Rm[2][1] = 2.0 * (y * z + r * x); Rm[2][2] = 1.0 - 2.0 * (x * x + y * y);
-            } else {
-                inv = 1.0 / sqrt((qn[0] * qn[0] + qn[1] * qn[1]) + (qn[2] * qn[2] + qn[3] * qn[3]));
-#pragma unroll
-                for (int i = 0; i < 4; ++i) qn[i] *= inv;
-                const R x = qn[0], y = qn[1], z = qn[2], w = qn[3];
-                Rm[0][0] = 2.0 * (x * x + y * y) - 1.0; Rm[0][1] = 2.0 * (y * z - x * w); Rm[0][2] = 2.0 * (y * w + x * z);
-                Rm[1][0] = 2.0 * (y * z + x * w); Rm[1][1] = 2.0 * (x * x + z * z) - 1.0; Rm[1][2] = 2.0 * (z * w - x * y);
-                Rm[2][0] = 2.0 * (y * w - x * z); Rm[2][1] = 2.0 * (z * w + x * y); Rm[2][2] = 2.0 * (x * x + w * w) - 1.0;
-            }
+            R Rm[3][3], qn[4], inv;
+            rotation_f64<INRIA>(rot, Rm, qn, inv);
             R s[3][3];
 #pragma unroll
             for (int r = 0; r < 3; ++r)
 #pragma unroll
                 for (int c = 0; c < 3; ++c)
                     s[r][c] = Rm[r][0] * sv[0] * sv[0] * Rm[c][0] + Rm[r][1] * sv[1] * sv[1] * Rm[c][1] + Rm[r][2] * sv[2] * sv[2] * Rm[c][2];
-            R ps[2][3];
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) ps[r][c] = P[r][0] * s[0][c] + P[r][1] * s[1][c] + P[r][2] * s[2][c];
-            const R a0 = ps[0][0] * P[0][0] + ps[0][1] * P[0][1] + ps[0][2] * P[0][2];
-            const R b = ps[0][0] * P[1][0] + ps[0][1] * P[1][1] + ps[0][2] * P[1][2];
-            const R c0 = ps[1][0] * P[1][0] + ps[1][1] * P[1][1] + ps[1][2] * P[1][2];
+            R a0, b, c0;
+            cov2d_f64(f, s, a0, b, c0);
             const R ca = a0 + (R)0.3f, cc = c0 + (R)0.3f;
             const R d0 = a0 * c0 - b * b, d1 = ca * cc - b * b;
             const R r = d0 / d1;
@@ -238,77 +141,12 @@ __global__ __launch_bounds__(256) void antialias_backward_kernel(const Antialias
             const R id1 = 1.0 / d1;
             const R m00 = gr * (c0 - r * cc) * id1, m11 = gr * (a0 - r * ca) * id1;
             const R m01 = gr * (r - 1.0) * b * id1;          // each of the two off-diagonal entries: half of -2 b (1 - r) / d1
-            // gS = P^T gM P (the full symmetric matrix's entries)
-            R gp[2][3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                gp[0][c] = m00 * P[0][c] + m01 * P[1][c];
-                gp[1][c] = m01 * P[0][c] + m11 * P[1][c];
-            }
-            R gS[3][3];
-#pragma unroll
-            for (int rr = 0; rr < 3; ++rr)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) gS[rr][c] = P[0][rr] * gp[0][c] + P[1][rr] * gp[1][c];
-            if (p.dL_dmeans3D) {
-                // through the Jacobian J(t): cov2D = J Mw J^T with Mw = W Sigma W^T; gJ = 2 gcov J Mw
-                R ws[3][3], mw[3][3];
-#pragma unroll
-                for (int rr = 0; rr < 3; ++rr)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) ws[rr][c] = v[0 + rr] * s[0][c] + v[4 + rr] * s[1][c] + v[8 + rr] * s[2][c];
-#pragma unroll
-                for (int rr = 0; rr < 3; ++rr)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) mw[rr][c] = ws[rr][0] * v[0 + c] + ws[rr][1] * v[4 + c] + ws[rr][2] * v[8 + c];
-                const R J[2][3] = {{j00, 0.0, j02}, {0.0, j11, j12}};
-                R jm[2][3], gJ[2][3];
-#pragma unroll
-                for (int rr = 0; rr < 2; ++rr)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) jm[rr][c] = J[rr][0] * mw[0][c] + J[rr][1] * mw[1][c] + J[rr][2] * mw[2][c];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    gJ[0][c] = 2.0 * (m00 * jm[0][c] + m01 * jm[1][c]);
-                    gJ[1][c] = 2.0 * (m01 * jm[0][c] + m11 * jm[1][c]);
-                }
-                const R itz2 = 1.0 / (tz * tz);
-                const R g_tx = -gJ[0][2] * fx * itz2, g_ty = -gJ[1][2] * fy * itz2;
-                const R g_tz = -(gJ[0][0] * fx + gJ[1][1] * fy) * itz2 + (gJ[0][2] * fx * tx + gJ[1][2] * fy * ty) * (2.0 / (tz * tz * tz));
-                // a clamped t.x = cx t.z no longer moves with t.x, and moves with t.z instead
-                const R gt0 = clx ? 0.0 : g_tx, gt1 = cly ? 0.0 : g_ty;
-                const R gt2 = g_tz + (clx ? g_tx * cx : 0.0) + (cly ? g_ty * cy : 0.0);
-#pragma unroll
-                for (int jx = 0; jx < 3; ++jx) gmean[jx] = v[4 * jx + 0] * gt0 + v[4 * jx + 1] * gt1 + v[4 * jx + 2] * gt2;
-            }
+            if (p.dL_dmeans3D) mean_gradient(f, s, m00, m01, m11, gmean);
             if (p.dL_dscales || p.dL_drotations) {
-                // Sigma = M M^T, M = Rm diag(sv): gM = 2 gSigma M
-                R gR[3][3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    R gm[3];
-#pragma unroll
-                    for (int rr = 0; rr < 3; ++rr) gm[rr] = 2.0 * (gS[rr][0] * Rm[0][c] + gS[rr][1] * Rm[1][c] + gS[rr][2] * Rm[2][c]) * sv[c];
-                    gsc[c] = mod * (Rm[0][c] * gm[0] + Rm[1][c] * gm[1] + Rm[2][c] * gm[2]);
-#pragma unroll
-                    for (int rr = 0; rr < 3; ++rr) gR[rr][c] = gm[rr] * sv[c];
-                }
-                if constexpr (INRIA) {
-                    const R r_ = qn[0], x = qn[1], y = qn[2], z = qn[3];
-                    gq[0] = 2.0 * (z * (gR[1][0] - gR[0][1]) + y * (gR[0][2] - gR[2][0]) + x * (gR[2][1] - gR[1][2]));
-                    gq[1] = 2.0 * (y * (gR[0][1] + gR[1][0]) + z * (gR[0][2] + gR[2][0]) + r_ * (gR[2][1] - gR[1][2])) - 4.0 * x * (gR[1][1] + gR[2][2]);
-                    gq[2] = 2.0 * (x * (gR[0][1] + gR[1][0]) + r_ * (gR[0][2] - gR[2][0]) + z * (gR[1][2] + gR[2][1])) - 4.0 * y * (gR[0][0] + gR[2][2]);
-                    gq[3] = 2.0 * (r_ * (gR[1][0] - gR[0][1]) + x * (gR[0][2] + gR[2][0]) + y * (gR[1][2] + gR[2][1])) - 4.0 * z * (gR[0][0] + gR[1][1]);
-                } else {
-                    // dR/dq for the normalised quaternion (x = real part), then through the normalisation
-                    const R x = qn[0], y = qn[1], z = qn[2], w = qn[3];
-                    const R gx = 4.0 * x * (gR[0][0] + gR[1][1] + gR[2][2]) + 2.0 * (w * (gR[1][0] - gR[0][1]) + z * (gR[0][2] - gR[2][0]) + y * (gR[2][1] - gR[1][2]));
-                    const R gy = 4.0 * y * gR[0][0] + 2.0 * (z * (gR[0][1] + gR[1][0]) + w * (gR[0][2] + gR[2][0]) + x * (gR[2][1] - gR[1][2]));
-                    const R gz = 4.0 * z * gR[1][1] + 2.0 * (y * (gR[0][1] + gR[1][0]) + w * (gR[1][2] + gR[2][1]) + x * (gR[0][2] - gR[2][0]));
-                    const R gw = 4.0 * w * gR[2][2] + 2.0 * (y * (gR[0][2] + gR[2][0]) + z * (gR[1][2] + gR[2][1]) + x * (gR[1][0] - gR[0][1]));
-                    const R dot = x * gx + y * gy + z * gz + w * gw;
-                    gq[0] = (gx - x * dot) * inv; gq[1] = (gy - y * dot) * inv; gq[2] = (gz - z * dot) * inv; gq[3] = (gw - w * dot) * inv;
-                }
+                R gS[3][3], gR[3][3];
+                sigma_gradient(f, m00, m01, m11, gS);
+                scale_rotation_gradient(gS, Rm, sv, mod, gsc, gR);
+                quaternion_gradient<INRIA>(gR, qn, inv, gq);
             }
         }
     }
@@ -318,8 +156,6 @@ __global__ __launch_bounds__(256) void antialias_backward_kernel(const Antialias
     if (p.dL_dscales) st4(p.dL_dscales + idx, (float)gsc[0], (float)gsc[1], (float)gsc[2], 0.0f);
     if (p.dL_drotations) st4(p.dL_drotations + idx, (float)gq[0], (float)gq[1], (float)gq[2], (float)gq[3]);
 }
-
-inline bool positive_finite(float v) { return v > 0.0f && v <= 3.402823466e+38f; }      // (false for NaN and Inf)
 
 // What both argument structs share, checked and copied: every refusal of the header, before any HIP call.
 template <typename Args>

@@ -17,6 +17,10 @@
 // partial sums of a record are reduced over the wave with DPP row shifts / broadcasts and leave as
 // nine float atomics per (record, tile) — only records that some pixel of the tile composited.
 //
+// preprocess_backward_kernel: one lane per Gaussian. Its covariance chain — the forward's float32 t and clamp decisions, and in
+// double P = J W, gSigma, the mean's gradient through J, gSigma -> (gscale, gR) -> gq — is gaussian_chain.hpp's, the one
+// statement antialias.hip and normals.hip call too; the conic, pixel-centre, depth and colour parts are this file's.
+//
 // The host call (the end of this file): which pointers of gsr_backward_args must come together, the band of tile rows, the
 // profiles' focal lengths and the table of the output arrays are backward_policy.hpp's (pure, tested on the CPU);
 // gsr_backward makes one BackwardCall context from its answer and runs backward_stages() over it, a function per stage.
@@ -27,6 +31,7 @@
 #include "../../include/gsrast_amd_opacity.h"
 #include "blend_core.hpp"
 #include "blockbin.hpp"
+#include "gaussian_chain.hpp"
 #include "wave_reduce.hpp"
 
 namespace gsr {
@@ -576,39 +581,19 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(const Preproce
     R out[6] = {0, 0, 0, 0, 0, 0};
     R gmean[3] = {0, 0, 0};
     if (visible) {
-        const float* vf = p.view;
-        R v[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) v[i] = (R)vf[i];
         // t, clamped as in computeCov2D (GSCuda.cu:201-210): the clamp DECISIONS are the forward's, in its float32 arithmetic
-        const float txf = (vf[0] * mean.x + vf[4] * mean.y) + (vf[8] * mean.z + vf[12] * 1.0f);
-        const float tyf = (vf[1] * mean.x + vf[5] * mean.y) + (vf[9] * mean.z + vf[13] * 1.0f);
-        const float tzf = (vf[2] * mean.x + vf[6] * mean.y) + (vf[10] * mean.z + vf[14] * 1.0f);
-        const float limx = 1.3f * p.tan_fovx, limy = 1.3f * p.tan_fovy;
-        const float rx = txf / tzf, ry = tyf / tzf;
-        const float cxf = fminf(limx, fmaxf(-limx, rx)), cyf = fminf(limy, fmaxf(-limy, ry));
-        const bool clx = rx != cxf, cly = ry != cyf;          // clamped: t.x (t.y) no longer moves the entry, t.z does
-        const R tz = (R)tzf, cx = (R)cxf, cy = (R)cyf;
-        const R tx = cx * tz, ty = cy * tz;
-        // P = J W (2 x 3): cov2D = P Sigma P^T
-        const R fx = INRIA ? (R)p.focal_x : (R)p.focal, fy = INRIA ? (R)p.focal_y : (R)p.focal;
-        const R j00 = fx / tz, j11 = fy / tz, j02 = -fx * tx / (tz * tz), j12 = -fy * ty / (tz * tz);
-        R P[2][3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            P[0][c] = j00 * v[4 * c + 0] + j02 * v[4 * c + 2];
-            P[1][c] = j11 * v[4 * c + 1] + j12 * v[4 * c + 2];
-        }
+        // (t in the gscuda summation order for both profiles)
+        float txf, tyf, tzf;
+        view_point<false>(p.view, mean, txf, tyf, tzf);
+        const RatioClamp cl = clamp_ratios_libm(txf, tyf, tzf, 1.3f * p.tan_fovx, 1.3f * p.tan_fovy);
+        const ProjectionFrame f = projection_frame(p.view, (R)tzf, (R)cl.cx, (R)cl.cy, cl.clx, cl.cly, INRIA ? (R)p.focal_x : (R)p.focal,
+                                                   INRIA ? (R)p.focal_y : (R)p.focal);
         const R c3[6] = {(R)c3a.x, (R)c3a.y, (R)c3b.x, (R)c3b.y, (R)c3c.x, (R)c3c.y};
         const R s[3][3] = {{c3[0], c3[1], c3[2]}, {c3[1], c3[3], c3[4]}, {c3[2], c3[4], c3[5]}};
-        R ps[2][3];
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) ps[r][c] = P[r][0] * s[0][c] + P[r][1] * s[1][c] + P[r][2] * s[2][c];
-        const R a = (ps[0][0] * P[0][0] + ps[0][1] * P[0][1] + ps[0][2] * P[0][2]) + 0.3;
-        const R b = ps[0][0] * P[1][0] + ps[0][1] * P[1][1] + ps[0][2] * P[1][2];
-        const R cc = (ps[1][0] * P[1][0] + ps[1][1] * P[1][1] + ps[1][2] * P[1][2]) + 0.3;
+        R a, b, cc;
+        cov2d_f64(f, s, a, b, cc);
+        a = a + 0.3;
+        cc = cc + 0.3;
         const R det = a * cc - b * b;
         if (det != 0.0) {
             // gM: gradient w.r.t. the full symmetric cov2D. Summed directly by the render backward (dL_dcov2D), or, without that
@@ -624,45 +609,11 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(const Preproce
                 m11 = -(r10 * k01 + r11 * k11);
             }
             // gS = P^T gM P, stored entries: off-diagonals appear twice in Sigma
-            R gp[2][3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                gp[0][c] = m00 * P[0][c] + m01 * P[1][c];
-                gp[1][c] = m01 * P[0][c] + m11 * P[1][c];
-            }
-            auto gs = [&](int r, int c) { return P[0][r] * gp[0][c] + P[1][r] * gp[1][c]; };
-            out[0] = gs(0, 0); out[1] = 2.0 * gs(0, 1); out[2] = 2.0 * gs(0, 2);
-            out[3] = gs(1, 1); out[4] = 2.0 * gs(1, 2); out[5] = gs(2, 2);
-            if (p.dL_dmeans3D) {
-                // through the Jacobian J(t): cov2D = J Mw J^T with Mw = W Sigma W^T; gJ = 2 gcov J Mw
-                R ws[3][3], mw[3][3];
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) ws[r][c] = v[0 + r] * s[0][c] + v[4 + r] * s[1][c] + v[8 + r] * s[2][c];
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) mw[r][c] = ws[r][0] * v[0 + c] + ws[r][1] * v[4 + c] + ws[r][2] * v[8 + c];
-                const R J[2][3] = {{j00, 0.0, j02}, {0.0, j11, j12}};
-                R jm[2][3], gJ[2][3];
-#pragma unroll
-                for (int r = 0; r < 2; ++r)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) jm[r][c] = J[r][0] * mw[0][c] + J[r][1] * mw[1][c] + J[r][2] * mw[2][c];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    gJ[0][c] = 2.0 * (m00 * jm[0][c] + m01 * jm[1][c]);
-                    gJ[1][c] = 2.0 * (m01 * jm[0][c] + m11 * jm[1][c]);
-                }
-                const R itz2 = 1.0 / (tz * tz);
-                const R g_tx = -gJ[0][2] * fx * itz2, g_ty = -gJ[1][2] * fy * itz2;
-                const R g_tz = -(gJ[0][0] * fx + gJ[1][1] * fy) * itz2 + (gJ[0][2] * fx * tx + gJ[1][2] * fy * ty) * (2.0 / (tz * tz * tz));
-                const R gt0 = clx ? 0.0 : g_tx, gt1 = cly ? 0.0 : g_ty;
-                const R gt2 = g_tz + (clx ? g_tx * cx : 0.0) + (cly ? g_ty * cy : 0.0);
-#pragma unroll
-                for (int j = 0; j < 3; ++j) gmean[j] = v[4 * j + 0] * gt0 + v[4 * j + 1] * gt1 + v[4 * j + 2] * gt2;
-            }
+            R gS[3][3];
+            sigma_gradient(f, m00, m01, m11, gS);
+            out[0] = gS[0][0]; out[1] = 2.0 * gS[0][1]; out[2] = 2.0 * gS[0][2];
+            out[3] = gS[1][1]; out[4] = 2.0 * gS[1][2]; out[5] = gS[2][2];
+            if (p.dL_dmeans3D) mean_gradient(f, s, m00, m01, m11, gmean);
         }
         if (p.dL_dmeans3D) {
             // pixel-space centre: pix = ((proj mean).x / ((proj mean).w + 0.001) * 0.5 + 0.5) * W (GSCuda.cu:302-305, :342)
@@ -681,9 +632,9 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(const Preproce
             }
             if (p.depth) {
                 // d_i = z_i = row 2 of the view matrix applied to the mean; inverse depth: d(1/z) = -dz / z^2
-                const R gz = p.depth_inverse ? -gdep / (tz * tz) : gdep;
+                const R gz = p.depth_inverse ? -gdep / (f.tz * f.tz) : gdep;
 #pragma unroll
-                for (int j = 0; j < 3; ++j) gmean[j] += gz * v[4 * j + 2];
+                for (int j = 0; j < 3; ++j) gmean[j] += gz * f.v[4 * j + 2];
             }
         }
     }
@@ -745,60 +696,16 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(const Preproce
         }
     }
     R gsc[3] = {0, 0, 0}, gq[4] = {0, 0, 0, 0};
-    if (p.dL_dscales) {
-        // Sigma = M M^T, M = R diag(mod s): gM = 2 gSigma M (off-diagonal stored gradients split over both entries)
+    if (p.dL_dscales && visible) {
+        // Sigma = M M^T, M = R(q) diag(mod s): gM = 2 gSigma M (off-diagonal stored gradients split over both entries), then to q
+        // as given: the raw (r, x, y, z) of the upstream profile, or through the normalisation
         const R gS[3][3] = {{out[0], 0.5 * out[1], 0.5 * out[2]}, {0.5 * out[1], out[3], 0.5 * out[4]}, {0.5 * out[2], 0.5 * out[4], out[5]}};
         const R mod = (R)p.scale_modifier;
         const R sv[3] = {mod * (R)sc.x, mod * (R)sc.y, mod * (R)sc.z};
-        if (visible && INRIA) {
-            // Sigma = M M^T, M = R(q) diag(mod s) with the RAW quaternion q = (r, x, y, z) (oracle: inria_cov3d_backward)
-            const R r = (R)rot.x, x = (R)rot.y, y = (R)rot.z, z = (R)rot.w;
-            const R Rm[3][3] = {{1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - r * z), 2.0 * (x * z + r * y)},
-                                {2.0 * (x * y + r * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - r * x)},
-                                {2.0 * (x * z - r * y), 2.0 * (y * z + r * x), 1.0 - 2.0 * (x * x + y * y)}};
-            R gR[3][3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                R gm[3];
-#pragma unroll
-                for (int rr = 0; rr < 3; ++rr) gm[rr] = 2.0 * (gS[rr][0] * Rm[0][c] + gS[rr][1] * Rm[1][c] + gS[rr][2] * Rm[2][c]) * sv[c];
-                gsc[c] = mod * (Rm[0][c] * gm[0] + Rm[1][c] * gm[1] + Rm[2][c] * gm[2]);
-#pragma unroll
-                for (int rr = 0; rr < 3; ++rr) gR[rr][c] = gm[rr] * sv[c];
-            }
-            gq[0] = 2.0 * (z * (gR[1][0] - gR[0][1]) + y * (gR[0][2] - gR[2][0]) + x * (gR[2][1] - gR[1][2]));
-            gq[1] = 2.0 * (y * (gR[0][1] + gR[1][0]) + z * (gR[0][2] + gR[2][0]) + r * (gR[2][1] - gR[1][2])) - 4.0 * x * (gR[1][1] + gR[2][2]);
-            gq[2] = 2.0 * (x * (gR[0][1] + gR[1][0]) + r * (gR[0][2] - gR[2][0]) + z * (gR[1][2] + gR[2][1])) - 4.0 * y * (gR[0][0] + gR[2][2]);
-            gq[3] = 2.0 * (r * (gR[1][0] - gR[0][1]) + x * (gR[0][2] + gR[2][0]) + y * (gR[1][2] + gR[2][1])) - 4.0 * z * (gR[0][0] + gR[1][1]);
-        } else if (visible) {
-            const R qx = (R)rot.x, qy = (R)rot.y, qz = (R)rot.z, qw = (R)rot.w;
-            const R nrm = sqrt((qx * qx + qy * qy) + (qz * qz + qw * qw));
-            const R inv = 1.0 / nrm;
-            const R x = qx * inv, y = qy * inv, z = qz * inv, w = qw * inv;
-            const R Rm[3][3] = {{2.0 * (x * x + y * y) - 1.0, 2.0 * (y * z - x * w), 2.0 * (y * w + x * z)},
-                                {2.0 * (y * z + x * w), 2.0 * (x * x + z * z) - 1.0, 2.0 * (z * w - x * y)},
-                                {2.0 * (y * w - x * z), 2.0 * (z * w + x * y), 2.0 * (x * x + w * w) - 1.0}};
-            R gM[3][3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    gM[r][c] = 2.0 * (gS[r][0] * Rm[0][c] + gS[r][1] * Rm[1][c] + gS[r][2] * Rm[2][c]) * sv[c];
-            R gR[3][3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                gsc[c] = mod * (Rm[0][c] * gM[0][c] + Rm[1][c] * gM[1][c] + Rm[2][c] * gM[2][c]);
-#pragma unroll
-                for (int r = 0; r < 3; ++r) gR[r][c] = gM[r][c] * sv[c];
-            }
-            // dR/dq for the normalised quaternion (x = real part), then through the normalisation
-            const R gx = 4.0 * x * (gR[0][0] + gR[1][1] + gR[2][2]) + 2.0 * (w * (gR[1][0] - gR[0][1]) + z * (gR[0][2] - gR[2][0]) + y * (gR[2][1] - gR[1][2]));
-            const R gy = 4.0 * y * gR[0][0] + 2.0 * (z * (gR[0][1] + gR[1][0]) + w * (gR[0][2] + gR[2][0]) + x * (gR[2][1] - gR[1][2]));
-            const R gz = 4.0 * z * gR[1][1] + 2.0 * (y * (gR[0][1] + gR[1][0]) + w * (gR[1][2] + gR[2][1]) + x * (gR[0][2] - gR[2][0]));
-            const R gw = 4.0 * w * gR[2][2] + 2.0 * (y * (gR[0][2] + gR[2][0]) + z * (gR[1][2] + gR[2][1]) + x * (gR[1][0] - gR[0][1]));
-            const R dot = x * gx + y * gy + z * gz + w * gw;
-            gq[0] = (gx - x * dot) * inv; gq[1] = (gy - y * dot) * inv; gq[2] = (gz - z * dot) * inv; gq[3] = (gw - w * dot) * inv;
-        }
+        R Rm[3][3], qn[4], inv, gR[3][3];
+        rotation_f64<INRIA>(rot, Rm, qn, inv);
+        scale_rotation_gradient(gS, Rm, sv, mod, gsc, gR);
+        quaternion_gradient<INRIA>(gR, qn, inv, gq);
     }
     // ---- stores ----
     if constexpr (INRIA) {

@@ -12,7 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "backward_policy.hpp"
-#include "gsr_common.hpp"
+#include "gaussian_chain.hpp"
 
 namespace gsr {
 namespace {
@@ -105,8 +105,9 @@ __device__ __forceinline__ GaussianIn load_gaussian(const CameraParams& p, unsig
 }
 
 // One visible Gaussian's camera terms, added to acc. The arithmetic is the chain's (preprocess_backward_kernel): t and the
-// clamp decisions of t.x / t.z, t.y / t.z in the forward's float32, everything after in double — with fused multiply-adds
-// (nothing here has to repeat a float32 operation order) and one reciprocal of t.z.
+// clamp decisions of t.x / t.z, t.y / t.z in the forward's float32 — gaussian_chain.hpp's, the statement that kernel calls —
+// everything after in double, written out here on purpose: with fused multiply-adds (nothing there has to repeat a float32
+// operation order) and one reciprocal of t.z.
 template <bool SH>
 __device__ __forceinline__ void add_camera_terms(const CameraParams& p, unsigned i, const GaussianIn& in, double (&acc)[kCamTerms]) {
     const float4 mean = in.mean;
@@ -115,16 +116,13 @@ __device__ __forceinline__ void add_camera_terms(const CameraParams& p, unsigned
     const float4 gcv = in.gcv;
     const double gdep = (double)in.gdep;
     const float* vf = p.view;
-    const float txf = (vf[0] * mean.x + vf[4] * mean.y) + (vf[8] * mean.z + vf[12] * 1.0f);
-    const float tyf = (vf[1] * mean.x + vf[5] * mean.y) + (vf[9] * mean.z + vf[13] * 1.0f);
-    const float tzf = (vf[2] * mean.x + vf[6] * mean.y) + (vf[10] * mean.z + vf[14] * 1.0f);
-    const float limx = 1.3f * p.tan_fovx, limy = 1.3f * p.tan_fovy;
-    const float rx = txf / tzf, ry = tyf / tzf;
-    const float cxf = fminf(limx, fmaxf(-limx, rx)), cyf = fminf(limy, fmaxf(-limy, ry));
-    const bool clx = rx != cxf, cly = ry != cyf;          // clamped: t.x (t.y) no longer moves the entry, t.z does
+    float txf, tyf, tzf;
+    view_point<false>(vf, mean, txf, tyf, tzf);
+    const RatioClamp cl = clamp_ratios_libm(txf, tyf, tzf, 1.3f * p.tan_fovx, 1.3f * p.tan_fovy);
+    const bool clx = cl.clx, cly = cl.cly;
     {   // (the float32 above keeps the forward's operation order; from here on contraction is allowed)
 #pragma clang fp contract(fast)
-    const double tz = (double)tzf, cx = (double)cxf, cy = (double)cyf;
+    const double tz = (double)tzf, cx = (double)cl.cx, cy = (double)cl.cy;
     const double tx = cx * tz, ty = cy * tz;
     const double fx = (double)p.focal_x, fy = (double)p.focal_y;
     const double itz = 1.0 / tz, itz2 = itz * itz;

@@ -21,16 +21,6 @@ constexpr size_t kTempBytes = 16;                    // one word, kept a whole 1
 __device__ __forceinline__ float fmin_glm(float a, float b) { return (b < a) ? b : a; }
 __device__ __forceinline__ float fmax_glm(float a, float b) { return (a < b) ? b : a; }
 
-typedef float nt_f4 __attribute__((ext_vector_type(4)));
-// (the rows are read once: streaming loads, as in antialias.hip)
-__device__ __forceinline__ float4 ld4(const float4* q) {
-    const nt_f4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f4*>(q));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void st4(float4* q, float x, float y, float z, float w) {
-    __builtin_nontemporal_store((nt_f4){x, y, z, w}, reinterpret_cast<nt_f4*>(q));
-}
-
 // blockIdx.x: 256 Gaussians; blockIdx.y: a chunk of kChunk cameras. `cameras` is indexed by loop-uniform values only, so the
 // records arrive by scalar loads and cost no vector memory traffic.
 __global__ __launch_bounds__(256) void filter3d_observe_kernel(int n, int stride, int num_cameras, const float* __restrict__ positions,
@@ -190,7 +180,6 @@ __global__ __launch_bounds__(256) void filter3d_backward_kernel(const BackwardPa
     if (p.dL_dopacities) p.dL_dopacities[idx] = out_o;
 }
 
-inline bool positive_finite(float v) { return v > 0.0f && v <= 3.402823466e+38f; }      // (false for NaN and Inf)
 inline dim3 rows_grid(int n) { return dim3((unsigned)(((long long)n + 255) / 256)); }
 
 int observe_impl(gsr_filter3d_observe_args* a) {

@@ -25,6 +25,18 @@ inline int entry_point(Impl impl, Args... args) { clear_hip_error(); return reco
 // Refused before a launch: a pointer off a `to`-byte boundary (a power of two; null passes), more workgroups than a grid holds.
 inline bool misaligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
 inline bool exceeds_grid(long long blocks) { return blocks > 0x7FFFFFFFll; }
+__host__ __device__ inline bool positive_finite(float v) { return v > 0.0f && v <= 3.402823466e+38f; }      // (false for NaN and Inf)
+
+// A vec4 row that is read (written) once: a streaming load (store), so that it does not push out of the caches what the next
+// kernels read at once (preprocess.hip: 0.146 -> 0.129 ms on the bench frame).
+typedef float nt_f4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 ld4(const float4* q) {
+    const nt_f4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f4*>(q));
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void st4(float4* q, float x, float y, float z, float w) {
+    __builtin_nontemporal_store((nt_f4){x, y, z, w}, reinterpret_cast<nt_f4*>(q));
+}
 
 #define GSR_HIP_TRY(expr)                                   \
     do {                                                    \

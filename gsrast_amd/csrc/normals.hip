@@ -3,11 +3,11 @@
 // surface with its gradient to the depth. One lane per Gaussian (per pixel), streaming: no LDS, no atomics, nothing crosses
 // lanes. The depth backward is a gather: a pixel recomputes the float32 decisions of its four neighbours and adds their shares.
 //
-// The float32 arithmetic restates the header operation for operation (this file is compiled with -ffp-contract=off like the
-// preprocess kernels whose R and t it repeats); the gradients are evaluated in double from the float32 inputs, with the float32
-// forward's decisions, and rounded once.
+// The float32 arithmetic states the header operation for operation (this file is compiled with -ffp-contract=off); R and t are
+// gaussian_chain.hpp's, the preprocess kernels' own. The gradients are evaluated in double from the float32 inputs, with the
+// float32 forward's decisions, and rounded once; from R to the quaternion they take that header's double side.
 #include "../../include/gsrast_amd_normals.h"
-#include "gsr_common.hpp"
+#include "gaussian_chain.hpp"
 
 namespace gsr {
 namespace {
@@ -42,36 +42,9 @@ __device__ __forceinline__ GaussianNormal gaussian_normal_of(const float* v, con
     if (s[2] < s[a]) a = 2;
     out.axis = a;
     float t0, t1, t2;
+    view_point<INRIA>(v, mean, t0, t1, t2);
     float nw[3];
-    if constexpr (INRIA) {
-        t0 = v[0] * mean.x + v[4] * mean.y + v[8] * mean.z + v[12];
-        t1 = v[1] * mean.x + v[5] * mean.y + v[9] * mean.z + v[13];
-        t2 = v[2] * mean.x + v[6] * mean.y + v[10] * mean.z + v[14];
-        const float r = rot.x, x = rot.y, y = rot.z, z = rot.w;
-        if (a == 0) { nw[0] = 1.0f - 2.0f * (y * y + z * z); nw[1] = 2.0f * (x * y + r * z); nw[2] = 2.0f * (x * z - r * y); }
-        else if (a == 1) { nw[0] = 2.0f * (x * y - r * z); nw[1] = 1.0f - 2.0f * (x * x + z * z); nw[2] = 2.0f * (y * z + r * x); }
-        else { nw[0] = 2.0f * (x * z + r * y); nw[1] = 2.0f * (y * z - r * x); nw[2] = 1.0f - 2.0f * (x * x + y * y); }
-    } else {
-        t0 = (v[0] * mean.x + v[4] * mean.y) + (v[8] * mean.z + v[12] * 1.0f);
-        t1 = (v[1] * mean.x + v[5] * mean.y) + (v[9] * mean.z + v[13] * 1.0f);
-        t2 = (v[2] * mean.x + v[6] * mean.y) + (v[10] * mean.z + v[14] * 1.0f);
-        const float dq = (rot.x * rot.x + rot.y * rot.y) + (rot.z * rot.z + rot.w * rot.w);
-        const float inv = 1.0f / sqrtf(dq);
-        const float x = rot.x * inv, y = rot.y * inv, z = rot.z * inv, w = rot.w * inv;
-        if (a == 0) {
-            nw[0] = (float)(2.0 * (double)(x * x + y * y) - 1.0);
-            nw[1] = (float)(2.0 * (double)(y * z + x * w));
-            nw[2] = (float)(2.0 * (double)(y * w - x * z));
-        } else if (a == 1) {
-            nw[0] = (float)(2.0 * (double)(y * z - x * w));
-            nw[1] = (float)(2.0 * (double)(x * x + z * z) - 1.0);
-            nw[2] = (float)(2.0 * (double)(z * w + x * y));
-        } else {
-            nw[0] = (float)(2.0 * (double)(y * w + x * z));
-            nw[1] = (float)(2.0 * (double)(z * w - x * y));
-            nw[2] = (float)(2.0 * (double)(x * x + w * w) - 1.0);
-        }
-    }
+    rotation_axis<INRIA>(rotation_of<INRIA>(rot), a, nw);
     float nv[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) nv[r] = (v[r] * nw[0] + v[4 + r] * nw[1]) + v[8 + r] * nw[2];
@@ -87,16 +60,6 @@ __device__ __forceinline__ GaussianNormal gaussian_normal_of(const float* v, con
 #pragma unroll
     for (int r = 0; r < 3; ++r) out.n[r] = nv[r] / l;
     return out;
-}
-
-typedef float nt_f4 __attribute__((ext_vector_type(4)));
-// (the rows are read once: streaming loads, as in preprocess.hip)
-__device__ __forceinline__ float4 ld4(const float4* q) {
-    const nt_f4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f4*>(q));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void st4(float4* q, float x, float y, float z, float w) {
-    __builtin_nontemporal_store((nt_f4){x, y, z, w}, reinterpret_cast<nt_f4*>(q));
 }
 
 // Memory schedule of a wave: the view matrix through the scalar cache, the three rows of every lane in one round trip, then
@@ -137,23 +100,10 @@ __global__ __launch_bounds__(256) void gaussian_normals_backward_kernel(const Ga
         if (k.valid) {
             const int a = k.axis;
             const R sigma = k.flipped ? -1.0 : 1.0;
-            R qn[4] = {(R)rot.x, (R)rot.y, (R)rot.z, (R)rot.w};
-            [[maybe_unused]] R inv = 1.0;
+            R Rm[3][3], qn[4], inv;
+            rotation_f64<INRIA>(rot, Rm, qn, inv);
             R nw[3];
-            if constexpr (INRIA) {
-                const R r = qn[0], x = qn[1], y = qn[2], z = qn[3];
-                if (a == 0) { nw[0] = 1.0 - 2.0 * (y * y + z * z); nw[1] = 2.0 * (x * y + r * z); nw[2] = 2.0 * (x * z - r * y); }
-                else if (a == 1) { nw[0] = 2.0 * (x * y - r * z); nw[1] = 1.0 - 2.0 * (x * x + z * z); nw[2] = 2.0 * (y * z + r * x); }
-                else { nw[0] = 2.0 * (x * z + r * y); nw[1] = 2.0 * (y * z - r * x); nw[2] = 1.0 - 2.0 * (x * x + y * y); }
-            } else {
-                inv = 1.0 / sqrt((qn[0] * qn[0] + qn[1] * qn[1]) + (qn[2] * qn[2] + qn[3] * qn[3]));
-#pragma unroll
-                for (int i = 0; i < 4; ++i) qn[i] *= inv;
-                const R x = qn[0], y = qn[1], z = qn[2], w = qn[3];
-                if (a == 0) { nw[0] = 2.0 * (x * x + y * y) - 1.0; nw[1] = 2.0 * (y * z + x * w); nw[2] = 2.0 * (y * w - x * z); }
-                else if (a == 1) { nw[0] = 2.0 * (y * z - x * w); nw[1] = 2.0 * (x * x + z * z) - 1.0; nw[2] = 2.0 * (z * w + x * y); }
-                else { nw[0] = 2.0 * (y * w + x * z); nw[1] = 2.0 * (z * w - x * y); nw[2] = 2.0 * (x * x + w * w) - 1.0; }
-            }
+            rotation_axis_f64(Rm, a, nw);
             R v[16];
 #pragma unroll
             for (int i = 0; i < 16; ++i) v[i] = (R)view[i];
@@ -174,23 +124,7 @@ __global__ __launch_bounds__(256) void gaussian_normals_backward_kernel(const Ga
 #pragma unroll
                 for (int c = 0; c < 3; ++c) gR[r][c] = (c == a) ? gnw : 0.0;
             }
-            // from R to q: the formulas of antialias.hip's chain
-            if constexpr (INRIA) {
-                const R r_ = qn[0], x = qn[1], y = qn[2], z = qn[3];
-                gq[0] = 2.0 * (z * (gR[1][0] - gR[0][1]) + y * (gR[0][2] - gR[2][0]) + x * (gR[2][1] - gR[1][2]));
-                gq[1] = 2.0 * (y * (gR[0][1] + gR[1][0]) + z * (gR[0][2] + gR[2][0]) + r_ * (gR[2][1] - gR[1][2])) - 4.0 * x * (gR[1][1] + gR[2][2]);
-                gq[2] = 2.0 * (x * (gR[0][1] + gR[1][0]) + r_ * (gR[0][2] - gR[2][0]) + z * (gR[1][2] + gR[2][1])) - 4.0 * y * (gR[0][0] + gR[2][2]);
-                gq[3] = 2.0 * (r_ * (gR[1][0] - gR[0][1]) + x * (gR[0][2] + gR[2][0]) + y * (gR[1][2] + gR[2][1])) - 4.0 * z * (gR[0][0] + gR[1][1]);
-            } else {
-                // dR/dq for the normalised quaternion (x = real part), then through the normalisation
-                const R x = qn[0], y = qn[1], z = qn[2], w = qn[3];
-                const R gx = 4.0 * x * (gR[0][0] + gR[1][1] + gR[2][2]) + 2.0 * (w * (gR[1][0] - gR[0][1]) + z * (gR[0][2] - gR[2][0]) + y * (gR[2][1] - gR[1][2]));
-                const R gy = 4.0 * y * gR[0][0] + 2.0 * (z * (gR[0][1] + gR[1][0]) + w * (gR[0][2] + gR[2][0]) + x * (gR[2][1] - gR[1][2]));
-                const R gz = 4.0 * z * gR[1][1] + 2.0 * (y * (gR[0][1] + gR[1][0]) + w * (gR[1][2] + gR[2][1]) + x * (gR[0][2] - gR[2][0]));
-                const R gw = 4.0 * w * gR[2][2] + 2.0 * (y * (gR[0][2] + gR[2][0]) + z * (gR[1][2] + gR[2][1]) + x * (gR[1][0] - gR[0][1]));
-                const R dot = x * gx + y * gy + z * gz + w * gw;
-                gq[0] = (gx - x * dot) * inv; gq[1] = (gy - y * dot) * inv; gq[2] = (gz - z * dot) * inv; gq[3] = (gw - w * dot) * inv;
-            }
+            quaternion_gradient<INRIA>(gR, qn, inv, gq);
         }
     }
     st4(p.dL_drotations + idx, (float)gq[0], (float)gq[1], (float)gq[2], (float)gq[3]);
@@ -214,8 +148,6 @@ __device__ __forceinline__ T ndc_of(int i, T size) {
     else return ((T)2 * (T)i) / size - (T)1;
 }
 
-__device__ __forceinline__ bool positive_finite_depth(float d) { return d > 0.0f && d <= 3.402823466e+38f; }      // (false for NaN and Inf)
-
 // What the float32 forward decides for an interior pixel, and its output.
 struct DepthNormal {
     bool valid = false, flipped = false;
@@ -225,7 +157,7 @@ struct DepthNormal {
 template <bool INRIA>
 __device__ __forceinline__ DepthNormal depth_normal_of(const DepthNormalParams& p, int x, int y, float du, float dl, float dr, float dd) {
     DepthNormal out;
-    if (!(positive_finite_depth(du) && positive_finite_depth(dl) && positive_finite_depth(dr) && positive_finite_depth(dd))) return out;
+    if (!(positive_finite(du) && positive_finite(dl) && positive_finite(dr) && positive_finite(dd))) return out;
     const float wf = (float)p.width, hf = (float)p.height;
     const float rx = ndc_of<INRIA>(x, wf) * p.tan_fovx, rxl = ndc_of<INRIA>(x - 1, wf) * p.tan_fovx, rxr = ndc_of<INRIA>(x + 1, wf) * p.tan_fovx;
     const float ry = ndc_of<INRIA>(y, hf) * p.tan_fovy, ryu = ndc_of<INRIA>(y - 1, hf) * p.tan_fovy, ryd = ndc_of<INRIA>(y + 1, hf) * p.tan_fovy;
@@ -308,8 +240,6 @@ __global__ __launch_bounds__(kTileX * kTileY) void depth_normals_backward_kernel
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-inline bool positive_finite(float v) { return v > 0.0f && v <= 3.402823466e+38f; }      // (false for NaN and Inf)
-
 // What both Gaussian argument structs share, checked and copied: every refusal of the header, before any HIP call.
 template <typename Args>
 int fill_gaussian_params(const Args* a, GaussianNormalParams& p) {

@@ -69,10 +69,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const PreprocessParams 
     int32_t out_radius = 0;
     uint32_t out_tiles = 0, out_rect = 0;
 
-    // (the inputs are read once: streaming loads, so that they do not push out of the caches what the next kernels read at
-    // once — 0.146 -> 0.129 ms on the bench frame)
-    typedef float nt_f4 __attribute__((ext_vector_type(4)));
-    auto ld4 = [](const float4* q) { const nt_f4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f4*>(q)); return make_float4(v.x, v.y, v.z, v.w); };
+    // (the inputs are read once: streaming loads, ld4)
     const float4 mean = ld4(p.means3D + idx);
     const float4 ph = mat4_vec4(proj, mean.x, mean.y, mean.z, mean.w);
     const float one_over_w = 1.0f / (0.001f + ph.w);

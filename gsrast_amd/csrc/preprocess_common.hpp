@@ -1,33 +1,13 @@
-// What the two preprocess kernels (preprocess.hip, preprocess_inria.hip) and the duplication (binning.hip) share: 3 x 3
-// matrices, glm's min / max, the 16-pixel tile rectangle with its band clipping, the packed-rectangle encoding, and the
-// parameter fields both kernels take from a call. The kernels' own arithmetic differs on purpose and stays in their files.
+// What the two preprocess kernels (preprocess.hip, preprocess_inria.hip) and the duplication (binning.hip) share beyond
+// gaussian_chain.hpp's 3 x 3 matrices and glm's min / max: the 16-pixel tile rectangle with its band clipping, the
+// packed-rectangle encoding, and the parameter fields both kernels take from a call. The two kernels still spell out their own
+// covariance arithmetic, which differs between them on purpose; gaussian_chain.hpp states the same arithmetic for every other pass.
+// (Of that header they take M3, mul3, transpose3, fminr and fmaxr only; the whole of it is included because the two kernels are
+// meant to take its float32 functions too, once that leaves their resource figures and the preprocess stage's time unchanged.)
 #pragma once
-#include "gsr_common.hpp"
+#include "gaussian_chain.hpp"
 
 namespace gsr {
-
-struct M3 { float m[3][3]; };   // m[col][row]
-
-__device__ __forceinline__ float fminr(float a, float b) { return (b < a) ? b : a; }   // glm::min
-__device__ __forceinline__ float fmaxr(float a, float b) { return (a < b) ? b : a; }   // glm::max
-
-__device__ __forceinline__ M3 mul3(const M3& a, const M3& b) {
-    M3 r;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int row = 0; row < 3; ++row)
-            r.m[c][row] = a.m[0][row] * b.m[c][0] + a.m[1][row] * b.m[c][1] + a.m[2][row] * b.m[c][2];
-    return r;
-}
-__device__ __forceinline__ M3 transpose3(const M3& a) {
-    M3 r;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int row = 0; row < 3; ++row) r.m[c][row] = a.m[row][c];
-    return r;
-}
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(hi, max(lo, v)); }
 
