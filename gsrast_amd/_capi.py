@@ -1,6 +1,7 @@
 """ctypes binding of include/gsrast_amd.h, include/gsrast_amd_init.h, include/gsrast_amd_opacity.h, include/gsrast_amd_mcmc.h,
 include/gsrast_amd_contrib.h, include/gsrast_amd_antialias.h, include/gsrast_amd_filter3d.h, include/gsrast_amd_absgrad.h,
-include/gsrast_amd_features.h, include/gsrast_amd_distortion.h and include/gsrast_amd_normals.h (the C ABI of libgsrast_amd.so).
+include/gsrast_amd_features.h, include/gsrast_amd_distortion.h, include/gsrast_amd_normals.h and include/gsrast_amd_median.h (the C
+ABI of libgsrast_amd.so).
 
 There is no fallback: if the HIP library has not been built, importing the product path
 raises. Field order and types below mirror the header exactly.
@@ -452,6 +453,26 @@ NORMALS_SIGNATURES = {
     "gsr_depth_normals_backward": (C.c_int, [C.POINTER(DepthNormalsBackwardArgs)]),
 }
 
+# include/gsrast_amd_median.h (the median depth map and the per-pixel Gaussian ids of a drawn frame, forward and backward), in the same shape, with its own symbol test.
+GSR_MEDIAN_NONE = 0xFFFFFFFF
+
+
+class MedianArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32),
+                ("num_gaussians", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("threshold", C.c_float),
+                ("means2D", C.c_void_p), ("conic_opacity", C.c_void_p), ("ranges", C.c_void_p), ("n_contrib", C.c_void_p),
+                ("final_t", C.c_void_p), ("point_list", C.c_void_p), ("receipt", ForwardReceipt),
+                ("values", C.c_void_p), ("out", C.c_void_p), ("ids", C.c_void_p), ("dominant_ids", C.c_void_p),
+                ("dL_dout", C.c_void_p), ("dL_dvalues", C.c_void_p), ("value_sums_f64", C.c_void_p),
+                ("tile_row_begin", C.c_int32), ("tile_row_end", C.c_int32), ("stream", C.c_void_p), ("stage_ms", C.c_float)]
+
+
+MEDIAN_SIGNATURES = {
+    "gsr_median_temp_bytes": (C.c_size_t, [C.c_int32]),
+    "gsr_median_forward": (C.c_int, [C.POINTER(MedianArgs)]),
+    "gsr_median_backward": (C.c_int, [C.POINTER(MedianArgs)]),
+}
+
 _lib = None
 
 
@@ -480,7 +501,7 @@ def lib() -> C.CDLL:
                                   + list(MCMC_SIGNATURES.items()) + list(CONTRIB_SIGNATURES.items()) + list(ANTIALIAS_SIGNATURES.items())
                                   + list(FILTER3D_SIGNATURES.items()) + list(ABSGRAD_SIGNATURES.items())
                                   + list(FEATURES_SIGNATURES.items()) + list(DISTORTION_SIGNATURES.items())
-                                  + list(NORMALS_SIGNATURES.items())):
+                                  + list(NORMALS_SIGNATURES.items()) + list(MEDIAN_SIGNATURES.items())):
             fn = getattr(L, name, None)
             if fn is None and _TAG:
                 continue                       # (a tagged A/B build of an older tree may lack the newest entry points)

@@ -12,7 +12,8 @@ written by no later call of the library (the rasterizer writes into them through
 autograd may keep a gradient as `param.grad`, and a loss may be evaluated after the next frame was drawn. A
 SplatRasterizer's chunks, on the other hand, hold ONE forward call: the backward of a frame must run before the same
 rasterizer object draws again, and is refused (RuntimeError, nothing launched) if it did not. Keep one rasterizer object
-per graph that is alive at the same time.
+per graph that is alive at the same time. (The median map of `median=` is the one exception: its backward holds the id map
+and reads nothing of the frame.)
 """
 from __future__ import annotations
 
@@ -264,7 +265,8 @@ def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs,
               semantics: str = "gscuda", sh_degree: int = 3, scale_modifier: float = 1.0, depth: "bool | str" = False,
               colors_precomp: "torch.Tensor | None" = None, radii_slot: "RadiiSlot | None" = None, opacity_grad: bool = False,
               antialiased: bool = False, features: "torch.Tensor | None" = None, distortion: "torch.Tensor | str | None" = None,
-              distortion_power: int = 2, normals: bool = False, **draw_options):
+              distortion_power: int = 2, normals: bool = False, median: "torch.Tensor | str | None" = None,
+              median_threshold: float = 0.5, **draw_options):
     """One differentiable frame: SplatRasterizer.draw forward, .backward / .camera_backward backward.
 
     Tensors in the library's layouts, float32 on rast.device: means3D / scales / rotations [N,4], opacities [N], shs [N,48]
@@ -319,6 +321,16 @@ def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs,
     camera through them; through the normals themselves it reaches the rotations only — not the scales, the means or the camera: a
     view that requires a gradient is a ValueError. With normals.depth_normals of depth / opacity_map it forms 2DGS's
     normal-consistency loss (normals.normal_consistency). Without `normals` every return value and every launch stay as they
+    were.
+
+    median: a float32 [N] tensor on rast.device, which may require a gradient — or "depth": the view-space z, formed exactly as
+    distortion="depth" forms it. The median map [H,W] (SplatRasterizer.render_median: per pixel the value of the last blended
+    record with a transmittance above median_threshold in front of it — 0.5: 2DGS's median depth; 0 where nothing was blended) is
+    appended behind everything else, as the LAST element of the returned tuple. It is a STEP function of the geometry. What is not
+    differentiated: the selection — the map's gradient reaches `median` only (SplatRasterizer.median_backward, the selection held
+    fixed), and through torch, for "depth", means3D and the view; nothing reaches the scales, rotations or opacities through it.
+    It is an autograd function of its own, called right behind the frame's: its backward holds the id map and nothing of the
+    frame, so it also runs after `rast` has drawn again. Without `median` every return value and every launch stay as they
     were."""
     assert set(draw_options) <= set(_DRAW_OPTIONS), sorted(draw_options)
     assert depth in (False, True, "inverse"), depth
@@ -329,19 +341,55 @@ def rasterize(rast: SplatRasterizer, means3D, scales, rotations, opacities, shs,
     if antialiased:
         opacities = _antialias.compensate(means3D, scales, rotations, opacities, view, opts["tan_fov"], rast.width, rast.height,
                                           semantics=semantics, scale_modifier=opts["scale_modifier"], proj=proj, radii_slot=radii_slot)
+    if median is not None:
+        # (checked before anything is launched: the pass runs right behind the frame's own)
+        median = _distortion_values(median, means3D, view)
+        n = int(means3D.shape[0])
+        if not isinstance(median, torch.Tensor) or median.dtype != F32 or tuple(median.shape) != (n,) or median.device != rast.device:
+            raise ValueError(f"median: expected \"depth\" or float32 [{n}] on {rast.device}, got "
+                             f"{getattr(median, 'dtype', type(median))} {tuple(getattr(median, 'shape', ()))}")
+        median_threshold = float(median_threshold)
+        if not 0.0 <= median_threshold < 1.0:
+            raise ValueError(f"median_threshold: {median_threshold} is not in [0, 1)")
     if normals:
-        return _with_normals(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, features, distortion)
-    if distortion is None:
+        res = _with_normals(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, features, distortion)
+    elif distortion is None:
         if features is None:
-            return _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, None, None)[:3]
-        return _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, features, None)[:4]
-    distortion = _distortion_values(distortion, means3D, view)
-    out = _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, features, distortion)
-    return out[:3] + ((out[3],) if features is not None else ()) + (out[4],)
+            res = _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, None, None)[:3]
+        else:
+            res = _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, features, None)[:4]
+    else:
+        distortion = _distortion_values(distortion, means3D, view)
+        out = _Rasterize.apply(rast, opts, means3D, scales, rotations, opacities, shs, view, proj, cam_pos, colors_precomp, features, distortion)
+        res = out[:3] + ((out[3],) if features is not None else ()) + (out[4],)
+    if median is None:
+        return res
+    return res + (_Median.apply(rast, median, median_threshold),)
+
+
+class _Median(torch.autograd.Function):
+    """The median map of the frame `rast` has just drawn (SplatRasterizer.render_median), differentiable with respect to the
+    values with the selection held fixed. The backward holds the id map and nothing of the frame: it runs whether or not the
+    rasterizer has drawn again, and _Rasterize knows nothing of it."""
+
+    @staticmethod
+    def forward(ctx, rast, values, threshold):
+        res = rast.render_median(values, threshold=threshold, ids=True, sync=False)
+        ctx.rast, ctx.ids, ctx.n = rast, res["ids"], rast.num_gaussians
+        return res["map"]
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None or not ctx.needs_input_grad[1]:
+            return None, None, None
+        rast = ctx.rast
+        if rast.num_gaussians != ctx.n or tuple(ctx.ids.shape) != (rast.height, rast.width):
+            raise RuntimeError("the rasterizer of this median map was given a scene or a frame of another size since it was rendered")
+        return None, rast.median_backward(ctx.ids, g, sync=False), None
 
 
 def _distortion_values(distortion, means3D, view):
-    """rasterize's `distortion` as a tensor: "depth" is the view-space z of means3D, formed with torch operations."""
+    """rasterize's `distortion` (and `median`) as a tensor: "depth" is the view-space z of means3D, formed with torch operations."""
     if isinstance(distortion, str):
         assert distortion == "depth", distortion
         v = view.reshape(-1)                                  # (column-major: row 2 of the view matrix is elements 2, 6, 10, 14)
@@ -484,7 +532,7 @@ def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: 
            scale_modifier: float = 1.0, depth: "bool | str" = False, radii_slot: "RadiiSlot | None" = None,
            opacity_grad: bool = False, antialiased: bool = False, filter_3d: "torch.Tensor | None" = None,
            features: "torch.Tensor | None" = None, distortion: "torch.Tensor | str | None" = None, distortion_power: int = 2,
-           normals: bool = False, **draw_options):
+           normals: bool = False, median: "torch.Tensor | str | None" = None, median_threshold: float = 0.5, **draw_options):
     """`activate` then `rasterize`: (color [3,H,W], depth [H,W] or None, opacity_map [H,W]) of `params` seen from `camera`
     — a Camera (its matrices are uploaded once per device and kept with it; write to a Camera's arrays and it must be a new
     object) or a tuple (view, proj, cam_pos, tan_fovx, tan_fovy) whose first three are device tensors, which may require
@@ -505,7 +553,9 @@ def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: 
     appended as the last element of the result.
     normals=True: the normal map [3,H,W] of `rasterize` — the per-Gaussian normals of the activated (and, with filter_3d, smoothed:
     the filter adds the same amount to every squared scale, so the shortest axis stays the shortest) scales and rotations — follows
-    the feature map, before the distortion map; the view matrix must then not require a gradient."""
+    the feature map, before the distortion map; the view matrix must then not require a gradient.
+    median, median_threshold: a float32 [N] tensor or "depth": the median map [H,W] of `rasterize` is appended as the last element
+    of the result, behind the distortion map."""
     if semantics == "inria" and sh_degree >= 1:
         assert params.sh_layout == "coefficient_major", 'semantics="inria" reads shs as [N][16][3]: sh_layout="coefficient_major"'
     slot = radii_slot if radii_slot is not None else RadiiSlot()
@@ -516,4 +566,5 @@ def render(params: GaussianParams, rast: SplatRasterizer, camera, *, semantics: 
     return rasterize(rast, means3D, scales, rotations, opacities, params.shs, view, proj, cam_pos, (tan_fovx, tan_fovy),
                      semantics=semantics, sh_degree=sh_degree, scale_modifier=scale_modifier, depth=depth, radii_slot=slot,
                      opacity_grad=opacity_grad, antialiased=antialiased, features=features, distortion=distortion,
-                     distortion_power=distortion_power, normals=normals, **draw_options)
+                     distortion_power=distortion_power, normals=normals, median=median, median_threshold=median_threshold,
+                     **draw_options)

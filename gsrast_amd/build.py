@@ -37,7 +37,7 @@ def _headers_mtime() -> float:
     paths = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".h"))]
     paths += [os.path.join(HERE, "..", "include", h) for h in ("gsrast_amd.h", "gsrast_amd_init.h", "gsrast_amd_opacity.h", "gsrast_amd_mcmc.h",
                                                                       "gsrast_amd_contrib.h", "gsrast_amd_antialias.h", "gsrast_amd_filter3d.h", "gsrast_amd_absgrad.h",
-                                                                      "gsrast_amd_features.h", "gsrast_amd_distortion.h", "gsrast_amd_normals.h")]
+                                                                      "gsrast_amd_features.h", "gsrast_amd_distortion.h", "gsrast_amd_normals.h", "gsrast_amd_median.h")]
     return max(os.path.getmtime(p) for p in paths)
 
 

@@ -150,11 +150,20 @@ def depth_normals(depth, tan_fov, *, semantics: str = "gscuda"):
     return _DepthNormals.apply(depth, (float(tan_fov[0]), float(tan_fov[1])), flags)
 
 
-def normal_consistency(normal_map, depth_map, opacity_map, tan_fov, *, semantics: str = "gscuda", eps: float = 1e-6):
+def normal_consistency(normal_map, depth_map, opacity_map, tan_fov, *, semantics: str = "gscuda", eps: float = 1e-6,
+                       surface_depth=None):
     """2DGS's normal-consistency term as a per-pixel map [H,W]: 1 - sum_c N_r N_d, with N_r = normal_map [3,H,W] (the composited
     Gaussian normals: `render(..., normals=True)`) and N_d = depth_normals(depth_map / opacity_map.clamp_min(eps)) *
     opacity_map.detach() — the normal of the expected depth, weighted like N_r by the accumulated opacity. depth_map and
     opacity_map are `render(..., depth=True, opacity_grad=True)`'s. A torch composition around the fused operator: take `.mean()`
-    for the loss."""
-    n_d = depth_normals(depth_map / opacity_map.clamp_min(eps), tan_fov, semantics=semantics) * opacity_map.detach()
+    for the loss.
+    surface_depth: a depth image [H,W] to take the surface from instead — `render(..., median="depth")`'s median depth, 2DGS's
+    depth_ratio = 1, which does not lie between surfaces at a silhouette as the expected depth does. N_d is then
+    depth_normals(surface_depth) * opacity_map.detach(); depth_map is not read and may be None. The median depth is a step
+    function of the geometry: through N_d the loss then reaches the means' z (and the view) only. The default, None, is the
+    term as it was."""
+    if surface_depth is not None:
+        n_d = depth_normals(surface_depth, tan_fov, semantics=semantics) * opacity_map.detach()
+    else:
+        n_d = depth_normals(depth_map / opacity_map.clamp_min(eps), tan_fov, semantics=semantics) * opacity_map.detach()
     return 1.0 - (normal_map * n_d).sum(0)

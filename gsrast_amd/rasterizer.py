@@ -150,6 +150,7 @@ class SplatRasterizer:
         self.last_absgrad_ms: "float | None" = None    # of the last absgrad(profile=True)
         self.last_features_ms: "float | None" = None   # of the last render_features / features_backward / backward(features=...) with profile=True
         self.last_distortion_ms: "float | None" = None # of the last render_distortion / distortion_backward / backward(distortion=...) with profile=True
+        self.last_median_ms: "float | None" = None     # of the last render_median / median_backward with profile=True
         # the moments of the last render_distortion: (that frame's receipt serial, the power, [3,H,W]) — what its backward reads
         self._distortion_moments: "tuple[int | None, int, torch.Tensor | None]" = (None, 0, None)
         self.rects: torch.Tensor | None = None
@@ -800,6 +801,95 @@ class SplatRasterizer:
                                         into=into, tile_rows=tile_rows, profile=profile)
         self._call("gsr_distortion_backward", a, drop=("distortion_sums_f64",), ms="last_distortion_ms", sync=sync)
         return keep[-1]
+
+    # -- the median depth map and the per-pixel Gaussian ids (include/gsrast_amd_median.h) ----
+    def render_median(self, values: "torch.Tensor | None" = None, *, threshold: float = 0.5, ids: bool = True, dominant: bool = False,
+                      receipt: "_capi.ForwardReceipt | None" = None, tile_rows: "tuple[int, int] | None" = None,
+                      out: "dict | None" = None, profile: bool = False, sync: bool = True) -> dict:
+        """The median map and the per-pixel Gaussian ids of the last draw() (gsr_median_forward), with that call's own alpha, T and
+        decisions — call it after a draw() and before the next one. Returns a dict of new tensors:
+          "map" [H,W] float32 (with `values`: float32 [N] on this device, one scalar per Gaussian — the view depth for the median
+              depth): values[i] of the record i the pixel selected, the value's own bits; 0 where nothing was blended;
+          "ids" [H,W] int32 (ids=True): that record's Gaussian, the last blended record with a transmittance above `threshold` in
+              front of it; -1 (GSR_MEDIAN_NONE) where nothing was blended. threshold: 0.5 the median of 2DGS, 0 the last blended
+              record, just under 1 (np.nextafter(1, 0)) the first; 0 <= threshold < 1;
+          "dominant_ids" [H,W] int32 (dominant=True): the Gaussian with the largest blending weight alpha T of the pixel
+              (ContributionStats' `dominant` decision, per pixel); -1 where nothing was blended.
+        At least one of the three must be asked for. The map is a STEP function of the geometry: only `values` receives a gradient
+        (median_backward). receipt: default this object's last draw(). tile_rows: the band to walk and write, any band inside the
+        rows of the draw() (default: those rows); other rows are left alone. out: {"map" / "ids" / "dominant_ids": tensor} of the
+        caller's, contiguous on this device, float32 / int32 [H,W], written instead of new ones (which are 0 / -1 outside the band).
+        One more walk over the sorted lists (refused after draw(sorted_lists=False)). profile: last_median_ms gets the time."""
+        rcpt = self.last_receipt if receipt is None else receipt
+        assert rcpt is not None, "render_median needs the receipt of a draw()"
+        dev, shape = self.device, (self.height, self.width)
+        want = (("map",) if values is not None else ()) + (("ids",) if ids else ()) + (("dominant_ids",) if dominant else ())
+        assert want, "render_median: nothing asked for (values, ids or dominant)"
+        out = dict(out or {})
+        assert set(out) <= set(want), ("out", sorted(out), want)
+        res = {}
+        for k in want:
+            dtype = torch.float32 if k == "map" else torch.int32
+            t = out.get(k)
+            if t is None:
+                t = (torch.zeros(shape, dtype=dtype, device=dev) if k == "map" else torch.full(shape, -1, dtype=dtype, device=dev))
+            assert t.dtype == dtype and t.device == dev and t.is_contiguous() and tuple(t.shape) == shape, (k, t.dtype, tuple(t.shape))
+            res[k] = t
+        a = self._walk_args(_capi.MedianArgs, rcpt, tile_rows, profile)
+        a.threshold = float(threshold)
+        keep = None
+        if values is not None:
+            assert isinstance(values, torch.Tensor) and values.dtype == torch.float32 and values.device == dev, "values: a float32 tensor on this device"
+            assert values.dim() == 1 and values.shape[0] == self.num_gaussians, ("values", tuple(values.shape), self.num_gaussians)
+            keep = values.detach().contiguous()
+            a.values, a.out = keep.data_ptr(), res["map"].data_ptr()
+        if ids:
+            a.ids = res["ids"].data_ptr()
+        if dominant:
+            a.dominant_ids = res["dominant_ids"].data_ptr()
+        self._call("gsr_median_forward", a, ms="last_median_ms", sync=sync)
+        return res
+
+    def median_backward(self, ids: torch.Tensor, dL_dmap: torch.Tensor, *, tile_rows: "tuple[int, int] | None" = None,
+                        into: "torch.Tensor | None" = None, profile: bool = False, sync: bool = True) -> torch.Tensor:
+        """dL_dvalues [N] of sum(dL_dmap * render_median(values)["map"]) with the selection held fixed (gsr_median_backward):
+        row i is the sum of dL_dmap over the pixels whose id is i. ids: the int32 [H,W] "ids" of that render_median call; dL_dmap:
+        [H,W]. The call reads nothing of the frame: it is valid after this object has drawn again. tile_rows: the band of that
+        call (default: every row). The scratch (8 N bytes of doubles) is kept by this object, zero between calls and dropped if
+        a call fails. into: a float32 [N] tensor on this device, contiguous, written in full and returned."""
+        n, dev = self.num_gaussians, self.device
+        assert isinstance(ids, torch.Tensor) and ids.dtype == torch.int32 and ids.device == dev and ids.is_contiguous(), "ids: the int32 map of render_median"
+        assert tuple(ids.shape) == (self.height, self.width), ("ids", tuple(ids.shape))
+        g = dL_dmap.to(device=dev, dtype=torch.float32).contiguous()
+        assert tuple(g.shape) == (self.height, self.width), ("dL_dmap", tuple(g.shape))
+        self._check_into(into, (n,))
+        res = into if into is not None else torch.empty((n,), dtype=torch.float32, device=dev)
+        self._bw.fit(n)
+        a = _capi.MedianArgs()
+        a.struct_size = C.sizeof(_capi.MedianArgs)
+        a.flags = _capi.GSR_FLAG_PROFILE if profile else 0
+        a.num_gaussians, a.width, a.height = n, self.width, self.height
+        a.ids, a.dL_dout, a.dL_dvalues = ids.data_ptr(), g.data_ptr(), res.data_ptr()
+        a.value_sums_f64 = self._bw.sums("median_sums_f64", n).data_ptr()
+        if tile_rows is not None:
+            a.tile_row_begin, a.tile_row_end = int(tile_rows[0]), int(tile_rows[1])
+        a.stream = _capi.stream(dev)
+        self._call("gsr_median_backward", a, drop=("median_sums_f64",), ms="last_median_ms", sync=sync)
+        return res
+
+    def pick(self, x: int, y: int, *, threshold: float = 0.5, dominant: bool = False) -> "int | None":
+        """Which Gaussian is under pixel (x, y) of the last draw(): the index render_median's "ids" (dominant=True: "dominant_ids")
+        has there, or None where nothing was blended. Walks only the tile row that holds y; one synchronisation."""
+        x, y = int(x), int(y)
+        assert 0 <= x < self.width and 0 <= y < self.height, ("pick", x, y)
+        rcpt = self.last_receipt
+        assert rcpt is not None, "pick needs a draw()"
+        row = y // 16
+        if not (int(rcpt.tile_row_begin) <= row < int(rcpt.tile_row_end)):
+            return None                          # (the draw() did not cover this row)
+        res = self.render_median(threshold=threshold, ids=not dominant, dominant=dominant, tile_rows=(row, row + 1), sync=False)
+        i = int(res["dominant_ids" if dominant else "ids"][y, x])
+        return None if i < 0 else i
 
     def absgrad(self, dL_dout: torch.Tensor, *, dL_ddepth: "torch.Tensor | None" = None, depth: "bool | str | None" = None,
                 dL_dalpha: "torch.Tensor | None" = None, receipt: "_capi.ForwardReceipt | None" = None, semantics: str = "gscuda",
