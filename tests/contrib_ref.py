@@ -1,93 +1,56 @@
-"""Reference of the per-Gaussian contribution statistics (include/gsrast_amd_contrib.h): a float32 numpy replay of
-oracle/oracle_np.py's blend loop (the same masks, the same operation order, exp = the C++ oracle's libm expf) over given
-arrays, which keeps q = (uint32)(alpha T 2^32) of every blended (record, pixel) instead of a colour. Shared by
+"""Reference of the per-Gaussian contribution statistics (include/gsrast_amd_contrib.h): the float32 replay of the
+blend loop that tests/walk_ref.py holds (the masks, the operation order, exp = the C++ oracle's libm expf) over given arrays,
+with hooks that keep q = (uint32)(alpha T 2^32) of every blended (record, pixel) instead of a colour. Shared by
 tests/test_contrib_cpu.py and tests/test_gpu_contrib.py; also the scenes both files use, so that what the CPU file establishes
 of a scene (the replay's finalT / nContrib are cpu_oracle.forward's bit for bit; the blindness guards) holds for the arrays
 the GPU file compares."""
 import functools
+import types
 
 import numpy as np
+
+import walk_ref
+from walk_ref import T_CUTOFF
 
 F = np.float32
 NAMES = ("weight_sum", "weight_max", "pixels", "dominant")
 DTYPES = {"weight_sum": np.uint64, "weight_max": np.uint32, "pixels": np.uint64, "dominant": np.uint64}
-T_CUTOFF = {"gscuda": 0.001, "inria": 0.0001}
-
-
-def _libm_exp(x):
-    from oracle import cpu_oracle
-    return cpu_oracle.expf(x)
 
 
 def contribution(means2D, conic_opacity, ranges, values, W, H, t_cutoff=0.001, tile_rows=None, exp=None, wide=False):
     """The four integer arrays [N] over the tiles of rows `tile_rows` (default: all), and finalT / nContrib [H, W] of the
     replay (zeros outside those rows). wide: alpha, T and w in float64 instead (the decisions stay the float32 replay's: both
     run side by side), and no fixed point — returns {"weight_sum_f64": float64[N]} beside the rest."""
-    exp = _libm_exp if exp is None else exp
-    means2D = np.asarray(means2D, F).reshape(-1, 2)
-    co = np.asarray(conic_opacity, F).reshape(-1, 4)
-    ranges = np.asarray(ranges).view(np.uint32).reshape(-1, 2).astype(np.int64)
-    values = np.asarray(values).view(np.uint32).astype(np.int64)
-    n = means2D.shape[0]
-    gx, gy = (W + 15) // 16, (H + 15) // 16
-    r0_, r1_ = (0, gy) if tile_rows is None else tile_rows
+    n = np.asarray(means2D).size // 2
     out = {k: np.zeros(n, DTYPES[k]) for k in NAMES}
     wide_sum = np.zeros(n, np.float64)
-    finalT, ncontrib, stopped = np.zeros((H, W), F), np.zeros((H, W), np.uint32), np.zeros((H, W), bool)
-    ly, lx = np.divmod(np.arange(256), 16)
     scale = F(4294967296.0)
-    with np.errstate(all="ignore"):
-        for tyi in range(r0_, r1_):
-            for txi in range(gx):
-                r0, r1 = (int(v) for v in ranges[tyi * gx + txi])
-                px, py = txi * 16 + lx, tyi * 16 + ly
-                inside = (px < min(txi * 16 + 16, W)) & (py < min(tyi * 16 + 16, H))
-                done = ~inside
-                T = np.ones(256, F)
-                T64 = np.ones(256, np.float64)
-                contrib, last = np.zeros(256, np.uint32), np.zeros(256, np.uint32)
-                best, best_id = np.zeros(256, np.uint32), np.full(256, -1, np.int64)
-                fx, fy = px.astype(F), py.astype(F)
-                for k in range(r0, max(r0, r1)):
-                    if done.all():
-                        break
-                    g = int(values[k])
-                    act = ~done
-                    contrib[act] += 1
-                    gxy, con = means2D[g], co[g]
-                    dx, dy = gxy[0] - fx, gxy[1] - fy
-                    power = F(-0.5) * (con[0] * dx * dx + con[2] * dy * dy) - con[1] * dx * dy
-                    alpha = np.minimum(F(0.99), con[3] * exp(power))
-                    test = T * (F(1.0) - alpha)
-                    live = act & ~(power > 0) & ~(alpha < F(1.0) / F(255.0))
-                    stop = live & (test < F(t_cutoff))
-                    upd = live & ~stop
-                    done |= stop
-                    if upd.any():
-                        w = (alpha * T).astype(F)
-                        q = np.trunc((w * scale).astype(F).astype(np.float64)).astype(np.uint64)[upd]       # (the product by 2^32 is exact)
-                        assert (q > 0).all() and (q < (1 << 32)).all()
-                        out["weight_sum"][g] += np.uint64(int(q.sum()))
-                        out["weight_max"][g] = max(int(out["weight_max"][g]), int(q.max()))
-                        out["pixels"][g] += np.uint64(int(upd.sum()))
-                        better = np.zeros(256, bool)
-                        better[upd] = q.astype(np.uint32) > best[upd]                 # strict: a tie stays with the front-most
-                        best[better] = q.astype(np.uint32)[better[upd]]
-                        best_id[better] = g
-                        if wide:
-                            d = (dx.astype(np.float64), dy.astype(np.float64))
-                            p64 = -0.5 * (float(con[0]) * d[0] * d[0] + float(con[2]) * d[1] * d[1]) - float(con[1]) * d[0] * d[1]
-                            a64 = np.minimum(float(F(0.99)), float(con[3]) * np.exp(p64))
-                            wide_sum[g] += float((a64 * T64)[upd].sum())
-                            T64[upd] = (T64 * (1.0 - a64))[upd]
-                    T[upd] = test[upd]
-                    last[upd] = contrib[upd]
-                ys, xs = py[inside], px[inside]
-                finalT[ys, xs] = T[inside]
-                ncontrib[ys, xs] = last[inside]
-                stopped[ys, xs] = done[inside]
-                won = best_id[inside & (best > 0)]
-                np.add.at(out["dominant"], won, np.uint64(1))
+
+    def start(tx, ty):
+        return types.SimpleNamespace(T64=np.ones(256, np.float64), best=np.zeros(256, np.uint32), best_id=np.full(256, -1, np.int64))
+
+    def record(r, g, pos, con, dx, dy, power, alpha, T, upd):
+        w = (alpha * T).astype(F)
+        q = np.trunc((w * scale).astype(F).astype(np.float64)).astype(np.uint64)[upd]       # (the product by 2^32 is exact)
+        assert (q > 0).all() and (q < (1 << 32)).all()
+        out["weight_sum"][g] += np.uint64(int(q.sum()))
+        out["weight_max"][g] = max(int(out["weight_max"][g]), int(q.max()))
+        out["pixels"][g] += np.uint64(int(upd.sum()))
+        better = np.zeros(256, bool)
+        better[upd] = q.astype(np.uint32) > r.best[upd]               # strict: a tie stays with the front-most
+        r.best[better] = q.astype(np.uint32)[better[upd]]
+        r.best_id[better] = g
+        if wide:
+            d = (dx.astype(np.float64), dy.astype(np.float64))
+            p64 = -0.5 * (float(con[0]) * d[0] * d[0] + float(con[2]) * d[1] * d[1]) - float(con[1]) * d[0] * d[1]
+            a64 = np.minimum(float(F(0.99)), float(con[3]) * np.exp(p64))
+            wide_sum[g] += float((a64 * r.T64)[upd].sum())
+            r.T64[upd] = (r.T64 * (1.0 - a64))[upd]
+
+    def end(r, px, py, inside, T, last, done):
+        np.add.at(out["dominant"], r.best_id[inside & (r.best > 0)], np.uint64(1))
+
+    finalT, ncontrib, stopped = walk_ref.replay(means2D, conic_opacity, ranges, values, W, H, t_cutoff, tile_rows, exp, start, record, end)
     out.update(finalT=finalT, nContrib=ncontrib, stopped=stopped)          # (stopped: the pixel ended on the cut-off)
     if wide:
         out["weight_sum_f64"] = wide_sum

@@ -2,20 +2,22 @@
 and tests/test_gpu_median.py with the scenes of tests/contrib_ref.py (all_scenes, LIST_LENGTHS: imported), so that what the CPU
 file establishes of a scene holds for the arrays the GPU file compares.
 
-forward: a float32 numpy restatement of the header's forward, line for line, in contrib_ref.contribution's replay (the same
-masks, the same operation order, exp = the C++ oracle's libm expf, the cut-off): sel, dom and the gathered value per pixel, and
+forward: a float32 numpy restatement of the header's forward, line for line, as hooks of walk_ref.replay (the
+masks, the operation order, exp = the C++ oracle's libm expf, the cut-off: written once there): sel, dom and the gathered value per pixel, and
 beside them where in its tile's list the selected record stands and the pixel's first and last blended records — what the
 blindness guards ask. The GPU's three maps are compared with it bit for bit.
 backward: the header's sum in float64 (np.add.at), with the sum of |g| per Gaussian for the bound.
 depth_gradients64: the "depth" composition of autograd.rasterize in float64 torch, fed a map of ids."""
+import types
+
 import numpy as np
 
-import contrib_ref
+import walk_ref
 from contrib_ref import LIST_LENGTHS, all_scenes      # noqa: F401  (the scenes both files use)
+from walk_ref import T_CUTOFF, depth_values, ulp32    # noqa: F401  (depth_values: the view-space z as autograd._distortion_values forms it)
 
 F = np.float32
 NONE = np.uint32(0xFFFFFFFF)
-T_CUTOFF = contrib_ref.T_CUTOFF
 FIRST_HIT = float(np.nextafter(np.float32(1.0), np.float32(0.0)))
 THRESHOLDS = (0.5, 0.05, 0.0, FIRST_HIT)
 
@@ -24,69 +26,36 @@ def forward(means2D, conic_opacity, ranges, lists, values, W, H, threshold, t_cu
     """out [H,W] float32, ids / dominant_ids [H,W] uint32, finalT, nContrib [H,W] of the replay over the tiles of rows `tile_rows`
     (default: all; 0 / NONE / zeros outside), and per pixel the 1-based list positions sel_pos, first_pos, last_pos of the
     selected, the first and the last blended record (0: none) and blended, how many it blended. values: [N] or None (out zeros)."""
-    exp = contrib_ref._libm_exp if exp is None else exp
-    means2D = np.asarray(means2D, F).reshape(-1, 2)
-    co = np.asarray(conic_opacity, F).reshape(-1, 4)
-    ranges = np.asarray(ranges).view(np.uint32).reshape(-1, 2).astype(np.int64)
-    lists = np.asarray(lists).view(np.uint32).astype(np.int64)
     thr = F(threshold)
     assert F(0.0) <= thr < F(1.0), threshold
-    gx, gy = (W + 15) // 16, (H + 15) // 16
-    r0_, r1_ = (0, gy) if tile_rows is None else tile_rows
     ids, dom_ids = np.full((H, W), NONE, np.uint32), np.full((H, W), NONE, np.uint32)
-    finalT, ncontrib = np.zeros((H, W), F), np.zeros((H, W), np.uint32)
     pos = {k: np.zeros((H, W), np.int64) for k in ("sel_pos", "first_pos", "last_pos", "blended")}
-    ly, lx = np.divmod(np.arange(256), 16)
     scale = F(4294967296.0)
-    with np.errstate(all="ignore"):
-        for tyi in range(r0_, r1_):
-            for txi in range(gx):
-                r0, r1 = (int(v) for v in ranges[tyi * gx + txi])
-                px, py = txi * 16 + lx, tyi * 16 + ly
-                inside = (px < min(txi * 16 + 16, W)) & (py < min(tyi * 16 + 16, H))
-                done = ~inside
-                T = np.ones(256, F)
-                contrib, last = np.zeros(256, np.uint32), np.zeros(256, np.uint32)
-                sel, dom, best = np.full(256, NONE, np.uint32), np.full(256, NONE, np.uint32), np.zeros(256, np.uint32)
-                sel_pos, first_pos, count = np.zeros(256, np.int64), np.zeros(256, np.int64), np.zeros(256, np.int64)
-                fx, fy = px.astype(F), py.astype(F)
-                for k in range(r0, max(r0, r1)):
-                    if done.all():
-                        break
-                    g = int(lists[k])
-                    act = ~done
-                    contrib[act] += 1
-                    gxy, con = means2D[g], co[g]
-                    dx, dy = gxy[0] - fx, gxy[1] - fy
-                    power = F(-0.5) * (con[0] * dx * dx + con[2] * dy * dy) - con[1] * dx * dy
-                    alpha = np.minimum(F(0.99), con[3] * exp(power))
-                    test = T * (F(1.0) - alpha)
-                    live = act & ~(power > 0) & ~(alpha < F(1.0) / F(255.0))
-                    stop = live & (test < F(t_cutoff))
-                    upd = live & ~stop                                   # the record is BLENDED into these pixels
-                    done |= stop
-                    if upd.any():
-                        take = upd & (T > thr)                           # T: the transmittance in front of the record
-                        sel[take] = g
-                        sel_pos[take] = k - r0 + 1
-                        w = (alpha * T).astype(F)
-                        q = np.trunc((w * scale).astype(F).astype(np.float64)).astype(np.uint64).astype(np.uint32)
-                        better = upd & (q > best)                        # strict: a tie stays in front, q == 0 never wins
-                        best[better] = q[better]
-                        dom[better] = g
-                        first_pos[upd & (count == 0)] = k - r0 + 1
-                        count[upd] += 1
-                    T[upd] = test[upd]
-                    last[upd] = contrib[upd]
-                ys, xs = py[inside], px[inside]
-                ids[ys, xs] = sel[inside]
-                dom_ids[ys, xs] = dom[inside]
-                finalT[ys, xs] = T[inside]
-                ncontrib[ys, xs] = last[inside]
-                pos["sel_pos"][ys, xs] = sel_pos[inside]
-                pos["first_pos"][ys, xs] = first_pos[inside]
-                pos["last_pos"][ys, xs] = last[inside]
-                pos["blended"][ys, xs] = count[inside]
+
+    def start(tx, ty):
+        return types.SimpleNamespace(sel=np.full(256, NONE, np.uint32), dom=np.full(256, NONE, np.uint32), best=np.zeros(256, np.uint32),
+                                     sel_pos=np.zeros(256, np.int64), first_pos=np.zeros(256, np.int64), count=np.zeros(256, np.int64))
+
+    def record(r, g, at, con, dx, dy, power, alpha, T, upd):
+        take = upd & (T > thr)                           # T: the transmittance in front of the record
+        r.sel[take] = g
+        r.sel_pos[take] = at
+        w = (alpha * T).astype(F)
+        q = np.trunc((w * scale).astype(F).astype(np.float64)).astype(np.uint64).astype(np.uint32)
+        better = upd & (q > r.best)                      # strict: a tie stays in front, q == 0 never wins
+        r.best[better] = q[better]
+        r.dom[better] = g
+        r.first_pos[upd & (r.count == 0)] = at
+        r.count[upd] += 1
+
+    def end(r, px, py, inside, T, last, done):
+        ys, xs = py[inside], px[inside]
+        ids[ys, xs] = r.sel[inside]
+        dom_ids[ys, xs] = r.dom[inside]
+        for key, v in (("sel_pos", r.sel_pos), ("first_pos", r.first_pos), ("last_pos", last), ("blended", r.count)):
+            pos[key][ys, xs] = v[inside]
+
+    finalT, ncontrib, _ = walk_ref.replay(means2D, conic_opacity, ranges, lists, W, H, t_cutoff, tile_rows, exp, start, record, end)
     out = np.zeros((H, W), F)
     if values is not None:
         val = np.asarray(values, F).reshape(-1)
@@ -119,12 +88,6 @@ def backward(ids, g, n, tile_rows=None):
     return sums, mags, pixels
 
 
-def ulp32(x):
-    """The spacing of float32 at |x| (float64 in, float64 out; the smallest normal's for anything below it)."""
-    a = np.maximum(np.abs(np.asarray(x, np.float64)), float(np.finfo(np.float32).tiny)).astype(np.float32)
-    return (np.nextafter(a, np.float32(np.inf)).astype(np.float64) - a.astype(np.float64))
-
-
 def backward_bound(sums, mags):
     """|got - ref| <= ulp32(ref) + 2^-32 sum |g|: at most 2^21 double additions of the row's terms (each off by at most 2^-53 of
     the running magnitude, which sum |g| bounds), then one rounding to float32 (half an ulp; one whole ulp is allowed)."""
@@ -143,13 +106,6 @@ def random_gradient(cam, seed=43):
 
 def random_values(n, seed=47):
     return np.random.default_rng(seed + n).normal(size=n).astype(F)
-
-
-def depth_values(means3D, view):
-    """The view-space z as autograd._distortion_values forms it, in float32 numpy: (x v2 + y v6) + (z v10 + v14)."""
-    m = np.asarray(means3D, F)
-    v = np.asarray(view, F).reshape(-1)
-    return ((m[:, 0] * v[2] + m[:, 1] * v[6]) + (m[:, 2] * v[10] + v[14])).astype(F)
 
 
 def depth_gradients64(means3D, view, ids, g):
