@@ -84,7 +84,7 @@ def gaussian_normals64(rotations, view, decisions, semantics):
     n = len(q)
     nw = torch.stack(cols, 1)[torch.arange(n), torch.from_numpy(np.asarray(decisions["axis"]))]
     Wm = torch.stack([torch.stack([v[4 * c + r] for c in range(3)]) for r in range(3)])          # W[r][c] = V(r, c)
-    sigma = torch.from_numpy(np.where(decisions["flipped"], -1.0, 1.0))
+    sigma = torch.from_numpy(np.where(decisions["flipped"], -1.0, 1.0)).to(nw.dtype)
     nv = (nw @ Wm.T) * sigma[:, None]
     valid = torch.from_numpy(np.asarray(decisions["valid"]))
     safe = torch.where(valid[:, None], nv, torch.ones_like(nv))
@@ -198,10 +198,10 @@ def depth_normals64(Du, Dl, Dr, Dd, tan_fov, semantics, decisions):
     """The same function of float64 torch images with the decisions given: the up / left / right / down neighbour of a pixel is
     read from Du / Dl / Dr / Dd (the same image four times, or four leaves of it). [3,H,W]; 0 where not valid."""
     H, W = Du.shape
-    out = torch.zeros((3, H, W), dtype=torch.float64)
+    out = torch.zeros((3, H, W), dtype=Du.dtype)                              # (float64; tests/step_autograd_ref.py also runs it in float32)
     if H < 3 or W < 3:
         return out
-    t = lambda a: torch.from_numpy(np.asarray(a, np.float64))
+    t = lambda a: torch.from_numpy(np.asarray(a, np.float64)).to(Du.dtype)
     tx, ty = np.float64(F(tan_fov[0])), np.float64(F(tan_fov[1]))
     xs, ys = np.arange(1, W - 1), np.arange(1, H - 1)
     rx, rxl, rxr = (t(ndc(xs + k, W, semantics, np.float64) * tx)[None, :] for k in (0, -1, 1))
@@ -212,7 +212,7 @@ def depth_normals64(Du, Dl, Dr, Dd, tan_fov, semantics, decisions):
     dvx, dvy, dvz = rx * dd - rx * du, ryd * dd - ryu * du, dd - du
     dhx, dhy, dhz = rxr * dr - rxl * dl, ry * dr - ry * dl, dr - dl
     c = torch.stack([dvy * dhz - dvz * dhy, dvz * dhx - dvx * dhz, dvx * dhy - dvy * dhx])
-    c = c * torch.from_numpy(np.where(decisions["flipped"][1:-1, 1:-1], -1.0, 1.0))
+    c = c * t(np.where(decisions["flipped"][1:-1, 1:-1], -1.0, 1.0))
     safe = torch.where(valid, c, torch.ones_like(c))
     out[:, 1:-1, 1:-1] = torch.where(valid, safe / safe.norm(dim=0, keepdim=True), torch.zeros_like(c))
     return out

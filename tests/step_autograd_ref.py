@@ -34,7 +34,16 @@ decisions join the structure (with_decisions):
   flows     bool[N]    c = sqrt(d0 / d1) is computed and differentiated; floored, d1_bad bool[N]: the rows that take a constant
                        instead (the square root of the floor; 1), as antialias_ref.compensation_f32 decides them
 No Gaussian is left out for them: rows_near_a_threshold reports the visible rows on which one lies within MARGIN of its
-threshold or differs from its float64 twin, and the tests assert that there are none."""
+threshold or differs from its float64 twin, and the tests assert that there are none.
+
+The three geometry regularisers, off by default too (tests/step_frames.py's GEOMETRY_CASES; tests/test_step_geometry_cpu.py pins
+them): distortion= / distortion_power (the distortion map as the pairwise sum over a pixel's blended records), normals=True
+(the per-Gaussian normals of the rotation nodes, composited into a normal map), median= / median_threshold (the values of the
+structure's id map). gradients(loss_terms=) adds their loss terms, the normal-consistency term among them (consistency_map,
+consistency_pixels: the pixels that carry it). They add to the structure (with_geometry):
+  normal_decisions  dict of axis int[N], flipped bool[N], valid bool[N]: normals_ref.gaussian_normals_f32's on the float32 arrays
+  median_ids        int[H,W]  the Gaussian each pixel selected, -1 for none (median_ref.forward's, or the device's)
+and seven cuts to CUTS."""
 from __future__ import annotations
 
 import numpy as np
@@ -49,7 +58,16 @@ CUTS = ("background", "jacobian_mean", "view_direction", "depth_mean", "clamp_to
         # the compensation: c a constant; c differentiated along the unsmoothed scales' path (ds'/ds = 1 inside c only)
         "compensation", "compensation_scales",
         # the feature map's geometry (only dL/dF flows); the opacity map
-        "feature_geometry", "opacity_map")
+        "feature_geometry", "opacity_map",
+        # the distortion map: only the values' path flows; m detached (for "depth": the torch path to xyz and view)
+        "distortion_geometry", "distortion_values",
+        # the normal map: the per-Gaussian normals detached (only the blend weights flow); the reverse
+        "normal_rotation", "normal_weights",
+        # the consistency term's depth normal: opacity detached inside depth / opacity; the opacity.detach() factor made
+        # differentiable — the WRONG form, kept as modifier_first is, to show that the test tells the two apart
+        "depth_normal_opacity", "depth_normal_weight",
+        # the median map: its values detached
+        "median_values")
 
 SH_C0 = 0.28209479177387814
 SH_C1 = 0.4886025119029199
@@ -68,8 +86,9 @@ C_FLOORED = float(np.sqrt(np.float32(0.000025)))           # ... and a floored r
 # max(2e-4, 2 e32[k]), e32 = what float32 arithmetic alone does to the array on that frame (this restatement in float32
 # against itself in float64, same structure, same dropped pixels). 2e-4 is the RTOL of tests/test_gpu_backward*.py.
 # tests/test_step_autograd_cpu.py measures e32 and checks this table against it. Entries: (case, array) -> bound, for the
-# arrays whose 2 e32 exceeds the floor — none does (e32 is at most 3.5e-6 on CASES and 5.1e-6 on FULL_CASES, which
-# tests/test_step_full_cpu.py measures in the same way): every array of every case is at the floor.
+# arrays whose 2 e32 exceeds the floor — none does (e32 is at most 3.5e-6 on CASES, 5.1e-6 on FULL_CASES and 3.3e-6 on
+# GEOMETRY_CASES, which tests/test_step_full_cpu.py and tests/test_step_geometry_cpu.py measure in the same way): every array
+# of every case is at the floor.
 FLOOR = 2e-4
 BOUNDS = {}
 
@@ -129,17 +148,36 @@ def with_decisions(structure, masks=None, identity=None):
     return out
 
 
+def with_geometry(structure, normal_decisions=None, median_ids=None):
+    """structure plus the float32 decisions of the per-Gaussian normals (normals_ref.gaussian_normals_f32's dict on the float32
+    arrays the kernel is handed: axis, flipped, valid, each [N]) and the median map's ids (uint32 or int32 [H,W] as
+    median_ref.forward or the device gives them; kept as int64 with -1 where nothing was selected)."""
+    out = dict(structure)
+    if normal_decisions is not None:
+        out["normal_decisions"] = {k: np.asarray(normal_decisions[k]) for k in ("axis", "flipped", "valid")}
+    if median_ids is not None:
+        ids = np.ascontiguousarray(median_ids)
+        ids = (ids.view(np.uint32) if ids.dtype.itemsize == 4 else ids).astype(np.int64)
+        out["median_ids"] = np.where(ids >= structure["vis"].shape[0], -1, ids)
+    return out
+
+
 # ---- the differentiable forward ----------------------------------------------------------------------------------------------
-def leaves(raw, cam, dtype=F64, colors=False, features=None, constant=()):
+def leaves(raw, cam, dtype=F64, colors=False, features=None, constant=(), distortion_values=None, median_values=None):
     """The leaf tensors forward() is differentiated by: the raw parameters (and `colors` for the colors_precomp case,
-    `features` [N,C] for the feature map) and the three camera tensors, from their float32 values. constant: names of
-    the camera tensors that are no leaves (the view matrix under antialiased=True)."""
+    `features` [N,C] for the feature map, distortion_values / median_values [N] for a distortion= / median= tensor) and the
+    three camera tensors, from their float32 values. constant: names of the camera tensors that are no leaves (the view
+    matrix under antialiased=True or normals=True)."""
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dtype).requires_grad_(True)
     out = {k: t(raw[k]) for k in RAW}
     if colors:
         out["colors"] = t(raw["colors"])
     if features is not None:
         out["features"] = t(features)
+    if distortion_values is not None:
+        out["distortion_values"] = t(distortion_values)
+    if median_values is not None:
+        out["median_values"] = t(median_values)
     out.update(view=t(cam.view), proj=t(cam.proj), cam_pos=t(cam.cam_pos))
     for k in constant:
         out[k] = out[k].detach()
@@ -181,7 +219,8 @@ def _rotation(q, profile):
 
 
 def forward(leaf, structure, tan_fovx, tan_fovy, width, height, *, background, profile="gscuda", sh_degree=0,
-            scale_modifier=1.0, depth=False, cut=None, filter_3d=None, antialiased=False, opacity=False, modifier_first=False):
+            scale_modifier=1.0, depth=False, cut=None, filter_3d=None, antialiased=False, opacity=False, modifier_first=False,
+            distortion=None, distortion_power=2, normals=False, median=None, median_threshold=0.5):
     """(color [3,H,W], depth [H,W] or None, aux). leaf: dict of tensors xyz [N,3], opacity_logit [N], log_scale [N,3],
     rotation [N,4], shs [N,48], view [16], proj [16], cam_pos [3] and optionally colors [N,3] (composited as given, no SH).
     aux: the activated tensors means3D [N,3], scales [N,3], rotations [N,4], opacities [N] (graph nodes: differentiate by them
@@ -200,8 +239,25 @@ def forward(leaf, structure, tan_fovx, tan_fovy, width, height, *, background, p
     leaf["features"] [N,C]: aux["feature_map"] [C,H,W] = sum F_i alpha_i T_i over a zero background. opacity=True:
     aux["opacity_map"] [H,W] = 1 - T. Both are graph nodes. aux["rows"]: float64 numpy over the visible Gaussians of what
     the row decisions are taken on (rx, ry = t.x / t.z, t.y / t.z; r = d0 / d1 and d1 when antialiased). aux["blended"]
-    bool[n]: some pixel composites the Gaussian."""
+    bool[n]: some pixel composites the Gaussian.
+
+    distortion: "depth" or "values" (leaf["distortion_values"] [N]); aux["distortion_map"] [H,W] is the header's definition
+    (include/gsrast_amd_distortion.h) written as the pairwise sum over the records each pixel blends, with w = alpha T of this
+    forward: power 2, sum_i sum_j w_i w_j (m_i - m_j)^2; power 1, the signed form in list order, 2 sum_i w_i sum_{j<i} w_j
+    (m_i - m_j). No moment recurrence. "depth": m = row 2 of the view matrix times (x, y, z, 1), from the xyz and view leaves.
+    normals=True: the per-Gaussian normals are normals_ref.gaussian_normals64 of this forward's rotation nodes under
+    structure["normal_decisions"] (the view matrix a constant there), composited like features over a zero background into
+    aux["normal_map"] [3,H,W]; aux["rows"] gains what their decisions are taken on (rows_near_a_threshold).
+    median: "depth" or "values" (leaf["median_values"]); aux["median_map"] [H,W] = values[structure["median_ids"]], 0 where
+    the id is -1. The selection is recomputed here without gradient — the last blended record with the transmittance in front
+    of it above float32(median_threshold) — as aux["median_selected"] (global ids, -1: none); aux["median_differs"] [H,W]
+    is where it is not the structure's (pixels_to_drop adds those), and a pixel with a blended record whose T lies within
+    MARGIN of the threshold joins `near`."""
     assert cut is None or cut in CUTS, cut
+    assert distortion in (None, "depth", "values") and median in (None, "depth", "values") and distortion_power in (1, 2)
+    assert distortion is not None or cut not in ("distortion_geometry", "distortion_values")
+    assert normals or cut not in ("normal_rotation", "normal_weights")
+    assert median is not None or cut != "median_values"
     assert filter_3d is not None or (not modifier_first and cut not in ("filter_scale", "filter_opacity", "filter_coef"))
     assert cut != "compensation_scales" or (antialiased and filter_3d is not None)
     assert cut != "compensation" or antialiased
@@ -315,6 +371,29 @@ def forward(leaf, structure, tan_fovx, tan_fovy, width, height, *, background, p
         if cut == "depth_mean":
             dval = dval.detach()
         dval = dval * 1.0
+    # -- the values of the distortion and median maps; the per-Gaussian normals
+    z_all = means3D @ V[2, :3] + V[2, 3]                         # (its own nodes: the torch path of "depth" beside the rasterizer's t)
+    dist_m = med_m = nrm = None
+    if distortion is not None:
+        dist_m = (z_all if distortion == "depth" else leaf["distortion_values"] * 1.0)[idx]
+        if cut == "distortion_values":
+            dist_m = dist_m.detach()
+    if median is not None:
+        med_m = z_all if median == "depth" else leaf["median_values"] * 1.0
+        if cut == "median_values":
+            med_m = med_m.detach()
+        thr = float(np.float32(median_threshold))
+    if normals:
+        from normals_ref import gaussian_normals64
+        dec = {k: np.asarray(v)[idx.numpy()] for k, v in structure["normal_decisions"].items()}
+        nrm = gaussian_normals64(rotations[idx], leaf["view"].detach(), dec, profile)
+        if cut == "normal_rotation":
+            nrm = nrm.detach()
+        with torch.no_grad():                                     # what the normals' decisions are taken on, in this arithmetic
+            nw = R[torch.arange(n), :, torch.from_numpy(np.asarray(dec["axis"], np.int64))]
+            nv = nw @ V[:3, :3].T
+            rows.update(normal_dot=(nv * t).sum(1).to(F64).numpy(), normal_length=torch.sqrt((nv * nv).sum(1)).to(F64).numpy(),
+                        t_length=torch.sqrt((t * t).sum(1)).to(F64).numpy(), normal_scales=s.detach().to(F64).numpy())
     # -- the blend, tile by tile: [records, pixels]
     local = np.full(structure["vis"].shape[0], -1, np.int64)
     local[idx.numpy()] = np.arange(n)
@@ -326,6 +405,9 @@ def forward(leaf, structure, tan_fovx, tan_fovy, width, height, *, background, p
     feat = leaf["features"][idx] if "features" in leaf else None
     fmap = torch.zeros((feat.shape[1], height, width), dtype=dt) if feat is not None else None
     omap = torch.zeros((height, width), dtype=dt) if opacity else None
+    dist = torch.zeros((height, width), dtype=dt) if dist_m is not None else None
+    nmap = torch.zeros((3, height, width), dtype=dt) if normals else None
+    msel = torch.full((height, width), -1, dtype=torch.int64) if median is not None else None
     finalT = torch.ones((height, width), dtype=dt)
     last = torch.zeros((height, width), dtype=torch.int64)
     near = torch.zeros((height, width), dtype=torch.bool)
@@ -373,6 +455,22 @@ def forward(leaf, structure, tan_fovx, tan_fovy, width, height, *, background, p
             if feat is not None:
                 wgt_f = wgt.detach() if cut == "feature_geometry" else wgt
                 fmap[:, ya:yb, xa:xb] = (wgt_f.T @ feat[ids]).T.reshape(-1, *shape)
+            if dist_m is not None and L:
+                mv = dist_m[ids]
+                diff = mv[:, None] - mv[None, :]                              # [i, j]: m_i - m_j
+                pair = diff * diff if distortion_power == 2 else 2.0 * torch.tril(diff, -1)      # (power 1: the records j < i in front)
+                wgt_d = wgt.detach() if cut == "distortion_geometry" else wgt
+                dist[ya:yb, xa:xb] = ((pair @ wgt_d) * wgt_d).sum(0).reshape(shape)
+            if normals:
+                wgt_n = wgt.detach() if cut == "normal_weights" else wgt
+                nmap[:, ya:yb, xa:xb] = (wgt_n.T @ nrm[ids]).T.reshape(3, *shape)
+            if median is not None and L:
+                with torch.no_grad():
+                    Tb4 = Tx.detach()
+                    at = torch.where(on & (Tb4 > thr), order + 1, torch.zeros_like(order)).max(0).values
+                    gl = torch.from_numpy(np.asarray(structure["values"][r0:r1], np.int64))
+                    msel[ya:yb, xa:xb] = torch.where(at > 0, gl[(at - 1).clamp_min(0)], torch.full_like(at, -1)).reshape(shape)
+                    nr = nr | (on & ((Tb4 - thr).abs() <= MARGIN * thr))
             if opacity:
                 omap[ya:yb, xa:xb] = (1.0 - (Tf.detach() if cut == "opacity_map" else Tf)).reshape(shape)
             finalT[ya:yb, xa:xb] = Tf.detach().reshape(shape)
@@ -385,14 +483,24 @@ def forward(leaf, structure, tan_fovx, tan_fovy, width, height, *, background, p
                                   Sigma[:, 2, 2]], 1).detach())
     if antialiased:
         aux["per_gaussian"]["opacities"] = o
+    if dist_m is not None:
+        aux["distortion_map"] = dist
+    if normals:
+        aux["normal_map"] = nmap
+    if median is not None:
+        mid = torch.from_numpy(np.asarray(structure["median_ids"], np.int64))
+        aux.update(median_map=torch.where(mid >= 0, med_m[mid.clamp_min(0)], torch.zeros((), dtype=dt)),
+                   median_selected=msel.numpy(), median_differs=msel.numpy() != structure["median_ids"])
     return color, dmap, aux
 
 
-def rows_near_a_threshold(aux, structure, tan_fovx, tan_fovy, filter_3d=None, antialiased=False):
+def rows_near_a_threshold(aux, structure, tan_fovx, tan_fovy, filter_3d=None, antialiased=False, normals=False):
     """(near, differ): bool over aux["visible"] — a row decision of the compensation or of the smoothing within a relative
     MARGIN of its threshold in float64, or taken otherwise in float64 than the float32 decision in `structure`. The
     decisions: the two clamps, and with antialiased r = d0 / d1 against the floor and d1 (zero or not finite); with
-    filter_3d, f * f > 0. aux: of the uncut float64 forward()."""
+    filter_3d, f * f > 0; with normals, the per-Gaussian normal's: the two smallest (smoothed) scales within a relative MARGIN
+    of each other or another shortest axis in float64, the flip's dot product nv . t within MARGIN of 0 relative to |nv| |t| or of
+    another sign, and the normal's length against 0. aux: of the uncut float64 forward()."""
     vis, rows = aux["visible"], aux["rows"]
     near, differ = np.zeros(vis.size, bool), np.zeros(vis.size, bool)
     close = lambda v, thr: np.abs(v - thr) <= MARGIN * thr
@@ -408,23 +516,113 @@ def rows_near_a_threshold(aux, structure, tan_fovx, tan_fovy, filter_3d=None, an
         f = np.asarray(filter_3d, np.float32).astype(np.float64)[vis]
         differ |= ~(f * f > 0.0) != structure["identity"][vis]
         near |= (f != 0) & (f * f <= float(np.finfo(np.float32).tiny) * (1.0 + MARGIN))
+    if normals:
+        dec = {k: np.asarray(v)[vis] for k, v in structure["normal_decisions"].items()}
+        sc = rows["normal_scales"]
+        two = np.sort(sc, 1)[:, :2]
+        near |= (two[:, 1] - two[:, 0]) <= MARGIN * two[:, 1]
+        axis = np.zeros(vis.size, np.int64)                       # (the header's rule: the first of equal scales)
+        for k in (1, 2):
+            axis = np.where(sc[:, k] < sc[np.arange(vis.size), axis], k, axis)
+        length = rows["normal_length"]
+        near |= (np.abs(rows["normal_dot"]) <= MARGIN * length * rows["t_length"]) | (length <= MARGIN)
+        differ |= (axis != dec["axis"]) | ((rows["normal_dot"] > 0) != dec["flipped"]) | ((length > 0) != dec["valid"])
     return near, differ
 
 
 def pixels_to_drop(aux, structure):
     """bool[H,W]: the pixels left out of the loss — a float64 decision within a relative 1e-5 of its threshold, or a last
-    contributor that differs from the forward state's nContrib. aux: of the uncut float64 forward()."""
-    return aux["near"] | (aux["last"] != structure["nContrib"])
+    contributor that differs from the forward state's nContrib, or (median=) a selected record that is not the structure's.
+    aux: of the uncut float64 forward()."""
+    drop = aux["near"] | (aux["last"] != structure["nContrib"])
+    return drop | aux["median_differs"] if "median_differs" in aux else drop
 
 
-def gradients(leaf, structure, cam, w, wd, drop, dtype=F64, wf=None, wa=None, **forward_options):
+def eroded(keep):
+    """keep without the pixels any of whose four neighbours is not kept."""
+    out = keep.copy()
+    out[1:] &= keep[:-1]
+    out[:-1] &= keep[1:]
+    out[:, 1:] &= keep[:, :-1]
+    out[:, :-1] &= keep[:, 1:]
+    return out
+
+
+def depth_normal_pixels(surface, tan_fov, semantics, decisions):
+    """(near, differ) bool[H,W] of the depth normal of the float64 image `surface` against the float32 decisions
+    (normals_ref.depth_normals_f32's dict on the float32 image): near — where the four neighbours are usable, the flip's dot
+    product c . r within MARGIN of 0 relative to |c| |r|, or the cross product's length |c| within MARGIN of 0 relative to
+    |dv| |dh| (the two differences it is the product of); differ — the neighbours' usability (finite and > 0), the flip or
+    the validity taken otherwise in float64."""
+    from normals_ref import ndc
+    D = np.asarray(surface, np.float64)
+    H, W = D.shape
+    near, differ = np.zeros((H, W), bool), np.zeros((H, W), bool)
+    tx, ty = np.float64(np.float32(tan_fov[0])), np.float64(np.float32(tan_fov[1]))
+    xs, ys = np.arange(1, W - 1), np.arange(1, H - 1)
+    rx, rxl, rxr = (ndc(xs + k, W, semantics, np.float64)[None, :] * tx for k in (0, -1, 1))
+    ry, ryu, ryd = (ndc(ys + k, H, semantics, np.float64)[:, None] * ty for k in (0, -1, 1))
+    du, dd, dl, dr = D[:-2, 1:-1], D[2:, 1:-1], D[1:-1, :-2], D[1:-1, 2:]
+    with np.errstate(all="ignore"):
+        ok = lambda d: np.isfinite(d) & (d > 0)
+        finite = ok(du) & ok(dd) & ok(dl) & ok(dr)
+        dv = np.stack(np.broadcast_arrays(rx * dd - rx * du, ryd * dd - ryu * du, dd - du))
+        dh = np.stack(np.broadcast_arrays(rxr * dr - rxl * dl, ry * dr - ry * dl, dr - dl))
+        c = np.cross(dv, dh, axis=0)
+        dot = c[0] * rx + c[1] * ry + c[2]
+        length = np.sqrt((c * c).sum(0))
+        valid = finite & np.isfinite(length) & (length != 0)
+        product = np.sqrt((dv * dv).sum(0) * (dh * dh).sum(0))
+        close = (np.abs(dot) <= MARGIN * length * np.sqrt(rx * rx + ry * ry + 1.0)) | (length <= MARGIN * product)
+    inner = (slice(1, -1), slice(1, -1))
+    near[inner] = finite & close
+    differ[inner] = ((finite != decisions["finite"][inner]) | (valid != decisions["valid"][inner])
+                     | (valid & ((dot > 0) != decisions["flipped"][inner])))
+    return near, differ
+
+
+def consistency_pixels(drop, surface, tan_fov, semantics, decisions):
+    """keep_n bool[H,W], the pixels that carry the normal-consistency term: the kept pixels (~drop) eroded by the
+    4-neighbourhood — a dropped pixel's depth is a neighbour of four kept ones — without those on which a decision of the depth
+    normal is near its threshold or differs from its float32 twin (depth_normal_pixels; surface: the float64 image)."""
+    near, differ = depth_normal_pixels(surface, tan_fov, semantics, decisions)
+    return eroded(~drop) & ~near & ~differ
+
+
+def consistency_map(normal_map, depth, opacity_map, median_map, term, tan_fov, cut=None):
+    """The map 1 - sum_c N_r N_d of normals.normal_consistency in torch: N_d = normals_ref.depth_normals64 of depth /
+    opacity.clamp_min(1e-6) (term["surface"] == "median": of the median map) under term["decisions"], times opacity.detach()
+    — or times term["opacity_weight"] [H,W], where the caller holds that constant factor at a value of its own."""
+    from normals_ref import depth_normals64
+    if term["surface"] == "median":
+        surf = median_map
+    else:
+        surf = depth / (opacity_map.detach() if cut == "depth_normal_opacity" else opacity_map).clamp_min(1e-6)
+    n_d = depth_normals64(surf, surf, surf, surf, tan_fov, term["semantics"], term["decisions"])
+    if "opacity_weight" in term:                                 # (the detached factor held at a given value: finite differences)
+        return 1.0 - (normal_map * n_d * torch.from_numpy(term["opacity_weight"]).to(n_d.dtype)).sum(0)
+    n_d = n_d * (opacity_map if cut == "depth_normal_weight" else opacity_map.detach())
+    return 1.0 - (normal_map * n_d).sum(0)
+
+
+def gradients(leaf, structure, cam, w, wd, drop, dtype=F64, wf=None, wa=None, loss_terms=None, loss_only=False, **forward_options):
     """One step of the reference: forward(leaf, structure, <cam's tangents and size>, **forward_options), loss =
     (w . color).sum() + (wd . depth).sum() [+ (wf . feature_map).sum() + (wa . opacity_map).sum(): wf [C,H,W] with
     leaf["features"], wa [H,W] with opacity=True; afterwards aux["feature_map"] / ["opacity_map"] are float64 numpy] with the
     dropped pixels' weights zero, and autograd. A member of `leaf` that requires no gradient is a constant and has no entry. Returns (grads, color, depth,
     aux) — grads: float64 numpy, keyed by the leaves' names, by "means3D", "scales", "rotations", "opacities" (the gradients
     w.r.t. the activated arrays) and by "per_gaussian.mean2D" etc. (w.r.t. aux["per_gaussian"], rows in the order of
-    aux["visible"]); zeros where the loss does not depend on the tensor."""
+    aux["visible"]); zeros where the loss does not depend on the tensor.
+
+    loss_terms: dict of the terms beyond the linear ones above, each optional (the GPU test builds the same with the library):
+      "distortion": (lambda_d, g_d [H,W])   + lambda_d sum keep g_d distortion_map
+      "median": g_m [H,W]                   + sum keep g_m median_map
+      "normal_map": w_n [3,H,W]             + sum keep w_n normal_map
+      "consistency": dict(weight=lambda_n, surface="expected" | "median", semantics=, decisions=, keep_n=)
+                                            + lambda_n sum keep_n consistency_map(...): decisions, the depth normal's float32
+                                            ones on the float32 maps; keep_n, consistency_pixels' (needs opacity=True)
+    Afterwards aux["distortion_map"] / ["normal_map"] / ["median_map"] are float64 numpy too. loss_only=True returns the loss
+    as a Python float instead, without differentiating."""
     depth = forward_options.get("depth", False)
     color, dmap, aux = forward(leaf, structure, cam.tan_fovx, cam.tan_fovy, cam.width, cam.height, **forward_options)
     keep = torch.from_numpy(~drop)
@@ -434,6 +632,21 @@ def gradients(leaf, structure, cam, w, wd, drop, dtype=F64, wf=None, wa=None, **
         loss = loss + (torch.from_numpy(wf).to(dtype) * keep * aux["feature_map"]).sum()
     if wa is not None:
         loss = loss + (torch.from_numpy(wa).to(dtype) * keep * aux["opacity_map"]).sum()
+    img = lambda a: torch.from_numpy(np.asarray(a)).to(dtype)
+    terms = loss_terms or {}
+    if "distortion" in terms:
+        loss = loss + terms["distortion"][0] * (img(terms["distortion"][1]) * keep * aux["distortion_map"]).sum()
+    if "median" in terms:
+        loss = loss + (img(terms["median"]) * keep * aux["median_map"]).sum()
+    if "normal_map" in terms:
+        loss = loss + (img(terms["normal_map"]) * keep * aux["normal_map"]).sum()
+    if "consistency" in terms:
+        term = terms["consistency"]
+        cmap = consistency_map(aux["normal_map"], dmap, aux["opacity_map"], aux.get("median_map"), term,
+                               (cam.tan_fovx, cam.tan_fovy), forward_options.get("cut"))
+        loss = loss + term["weight"] * (img(term["keep_n"]) * cmap).sum()
+    if loss_only:                                                # (the float64 loss alone: for finite differences of it)
+        return float(loss.detach())
     names = [k for k in leaf if leaf[k].requires_grad]
     tensors = [leaf[k] for k in names] + [aux[k] for k in ("means3D", "scales", "rotations", "opacities")]
     names = names + ["means3D", "scales", "rotations", "opacities"]
@@ -444,7 +657,7 @@ def gradients(leaf, structure, cam, w, wd, drop, dtype=F64, wf=None, wa=None, **
     got = torch.autograd.grad(loss, tensors, allow_unused=True)
     grads = {k: (g.detach().to(F64).numpy() if g is not None else np.zeros(tuple(t.shape)))
              for k, g, t in zip(names, got, tensors)}
-    for k in ("feature_map", "opacity_map"):
-        if aux[k] is not None:
+    for k in ("feature_map", "opacity_map", "distortion_map", "normal_map", "median_map"):
+        if aux.get(k) is not None:
             aux[k] = aux[k].detach().to(F64).numpy()
     return grads, color.detach().to(F64).numpy(), (dmap.detach().to(F64).numpy() if depth else None), aux

@@ -2,7 +2,10 @@
 scene in raw parameters, the camera, the loss weights, and the reference step of a case (tests/step_autograd_ref.py). And,
 in a second table (FULL_CASES, full_*), the frames of tests/test_step_full_cpu.py and tests/test_gpu_step_full.py: the same
 pose and size with the 3D filter, the opacity compensation, a feature map and the opacity map, on a scene derived from
-raw_scene without altering it."""
+raw_scene without altering it. And, in a third table (GEOMETRY_CASES, geometry_*), the frames of
+tests/test_step_geometry_cpu.py and tests/test_gpu_step_geometry.py: the same pose, size and sizes of splats with the distortion
+map (distortion=, distortion_power), the normal map and the normal-consistency term (normals=True), the median map (median=,
+median_threshold), every Gaussian flattened along one axis."""
 from __future__ import annotations
 
 import functools
@@ -126,16 +129,20 @@ def full_camera_of(case):
     return posed_camera(W, H, kx=FULL_CASES[case]["kx"], **P1)
 
 
-@functools.lru_cache(maxsize=None)
 def full_scene(case):
+    """The scene of a FULL_CASES frame (read-only by convention: it is cached)."""
+    return _sized_scene(FULL_CASES[case]["profile"], FULL_CASES[case]["scale_modifier"])
+
+
+@functools.lru_cache(maxsize=None)
+def _sized_scene(profile, scale_modifier):
     """raw_scene(profile), copied, with its ordinary splats (not the stacks, the ones behind the camera or the wide ones)
     brought to the frame's resolution: every other one doubled and clipped into LARGE_BAND, the others clipped into SMALL_BAND
     — but every seventh of those left as it is, far below a pixel. The stacks shrunk to a pixel's size (STACK_TOP,
     STACK_SHRINK), the large and the wide ones fainter (LARGE_OPACITY, WIDE_OPACITY). Under a scale_modifier k every scale is divided by k: the rasterizer sees the same sizes again, and the
     filter, which the modifier multiplies too, is made for them (filter_values). Plus "features" [N,5], standard normal (a
     case of C channels reads the first C columns)."""
-    c = FULL_CASES[case]
-    raw = {k: v.copy() for k, v in raw_scene(c["profile"]).items()}
+    raw = {k: v.copy() for k, v in raw_scene(profile).items()}
     special = np.zeros(N, bool)
     for a, b in ((10, 17), (80, 87), (20, 32), (100, 112), (140, 148)):
         special[a:b] = True
@@ -147,7 +154,7 @@ def full_scene(case):
     raw["log_scale"][[10, 11, 80, 81]] = ln(STACK_TOP)
     for a in (12, 82):
         raw["log_scale"][a:a + 5] += ln(STACK_SHRINK)
-    raw["log_scale"] -= ln(c["scale_modifier"])
+    raw["log_scale"] -= ln(scale_modifier)
     for rows_, factor in ((np.arange(140, 148), WIDE_OPACITY), (large, LARGE_OPACITY)):
         o = 1.0 / (1.0 + np.exp(-raw["opacity_logit"][rows_].astype(np.float64))) * factor
         raw["opacity_logit"][rows_] = np.log(o / (1.0 - o)).astype(np.float32)
@@ -155,19 +162,22 @@ def full_scene(case):
     return raw
 
 
-@functools.lru_cache(maxsize=None)
 def filter_values(case):
+    """The filter of a FULL_CASES frame, float32 [N]; None for a case without the filter."""
+    return _filter_values_of(FULL_CASES[case]["profile"], FULL_CASES[case]["scale_modifier"]) if FULL_CASES[case]["filter"] else None
+
+
+@functools.lru_cache(maxsize=None)
+def _filter_values_of(profile, scale_modifier):
     """The scene's filter as tests/test_gpu_filter3d.py makes it: observe and finalize (the float32 restatement) of five
     training cameras at this frame's size, scaled by FILTER_SCALE (over the case's scale_modifier, as the scene's scales
     are), every tenth value zero — from row IDENTITY_FROM on, so that few of the IDENTITY rows are among the ones raw_scene
-    puts behind the camera (float32 [N]). None for a case without the filter."""
+    puts behind the camera (float32 [N])."""
     import filter3d_ref
     from gsrast_amd import filter3d
-    if not FULL_CASES[case]["filter"]:
-        return None
     rec, max_focal = filter3d.camera_records(filter3d_ref.orbit_cameras(5, width=W, height=H, radius=5.0, seed=6, arc=1.0))
-    v = filter3d_ref.finalize_f32(filter3d_ref.observe_f32(full_scene(case)["xyz"], rec), max_focal)
-    v = (v * np.float32(FILTER_SCALE / FULL_CASES[case]["scale_modifier"])).astype(np.float32)
+    v = filter3d_ref.finalize_f32(filter3d_ref.observe_f32(_sized_scene(profile, scale_modifier)["xyz"], rec), max_focal)
+    v = (v * np.float32(FILTER_SCALE / scale_modifier)).astype(np.float32)
     v[IDENTITY_FROM::10] = 0.0
     v.setflags(write=False)
     return v
@@ -190,12 +200,15 @@ def full_row_arrays(case, scales, opacities, means3D, rotations, cam, smoothed=N
     smoothed: (scales' [N,4], opacities' [N]) where the caller has the smoothed arrays themselves (the device's): the
     compensation's decisions are then taken on those. Returns dict: scales [N,4], opacities [N] (what gsr_forward reads),
     identity (or None), masks (or None), smoothed (forward_f32's dict or None)."""
+    return _row_arrays(FULL_CASES[case], filter_values(case), scales, opacities, means3D, rotations, cam, smoothed)
+
+
+def _row_arrays(c, filt, scales, opacities, means3D, rotations, cam, smoothed=None):
     import antialias_ref
     import filter3d_ref
-    c = FULL_CASES[case]
     out = dict(scales=np.asarray(scales, np.float32), opacities=np.asarray(opacities, np.float32), identity=None, masks=None, smoothed=None)
     if c["filter"]:
-        sm = filter3d_ref.forward_f32(out["scales"], out["opacities"], filter_values(case))
+        sm = filter3d_ref.forward_f32(out["scales"], out["opacities"], filt)
         out.update(scales=sm["scales_out"], opacities=sm["opacities_out"], identity=sm["identity"], smoothed=sm)
         if smoothed is not None:
             out.update(scales=np.asarray(smoothed[0], np.float32), opacities=np.asarray(smoothed[1], np.float32))
@@ -236,6 +249,162 @@ def full_reference_step(case, structure, cut=None, dtype=R.F64, drop=None):
         drop = R.pixels_to_drop(aux, structure)
     return R.gradients(full_leaves(case, dtype), structure, cam, w, wd, drop, dtype=dtype, wf=wf, wa=wa,
                        **full_forward_options(case, cut)) + (drop,)
+
+
+# ---- the frames of the geometry regularisers (tests/test_step_geometry_cpu.py, tests/test_gpu_step_geometry.py): the distortion
+# map, the normal map with the normal-consistency term, the median map. Same pose, size and scene family as FULL_CASES.
+# distortion / median: None, "depth" or "values" (a [N] leaf of the scene); surface: which depth the consistency term's normal is
+# taken from ("expected": depth / opacity; "median"), None for no such term; lam_d, lam_n: the weights of the distortion and the
+# consistency term, chosen so that each term's share of the largest entry of xyz.grad and of rotation.grad lies between a tenth
+# and ten times the colour's (tests/test_step_geometry_cpu.py prints the shares and asserts the band); linear: the maps that
+# carry a plain linear weight. constant: the view matrix is no leaf under antialiased=True or normals=True (the library refuses it).
+def _geometry(profile, deg, mod=1.0, kx=1.0, depth=False, filt=False, antialiased=False, channels=0, opacity=False, colour=True,
+              normals=False, distortion=None, power=2, median=None, threshold=0.5, surface=None, lam_d=1.0, lam_n=1.0, linear=(), wide=1.0):
+    return dict(wide=wide, profile=profile, sh_degree=deg, depth=depth, scale_modifier=mod, kx=kx, filter=filt, antialiased=antialiased,
+                channels=channels, opacity=opacity, colour=colour, normals=normals, distortion=distortion, power=power, median=median,
+                threshold=threshold, surface=surface, lam_d=lam_d, lam_n=lam_n, linear=tuple(linear),
+                constant=("view",) if (antialiased or normals) else ())
+
+
+WIDE_FAINTER = 0.6            # pose-distortion-median: the wide splats' opacity once more multiplied by this — under the upstream profile
+                              # they cover the whole frame, and some pixel must blend nothing and select no median id
+LAMBDA = {"2dgs-inria": (0.5, 1.0), "2dgs-gscuda-median": (1.0, 1.0)}       # case -> (lam_d, lam_n)
+GEOMETRY_CASES = {
+    "2dgs-inria": _geometry("inria", 3, depth=True, filt=True, antialiased=True, opacity=True, normals=True, distortion="depth",
+                            power=2, surface="expected", lam_d=LAMBDA["2dgs-inria"][0], lam_n=LAMBDA["2dgs-inria"][1]),
+    "2dgs-gscuda-median": _geometry("gscuda", 0, mod=2.0, depth=True, opacity=True, normals=True, distortion="depth", power=1,
+                                    median="depth", threshold=0.5, surface="median", lam_d=LAMBDA["2dgs-gscuda-median"][0],
+                                    lam_n=LAMBDA["2dgs-gscuda-median"][1]),
+    "pose-distortion-median": _geometry("inria", 2, kx=1.7, depth=True, distortion="depth", power=2, median="depth",
+                                        linear=("depth", "distortion", "median"), wide=WIDE_FAINTER),
+    "value-tensors": _geometry("gscuda", 0, channels=2, colour=False, normals=True, distortion="values", power=1, median="values",
+                               threshold=0.05, linear=("distortion", "median", "features", "normal_map")),
+    "normals-alone": _geometry("inria", 1, filt=True, colour=False, normals=True, linear=("normal_map",)),
+}
+FLATTEN = (0.3, 0.6)          # one seeded axis of every Gaussian becomes its shortest scale times a factor from this band: the sizes
+                              # of full_scene tie two or three scales of many rows (the clips, the stacks), and which axis is the
+                              # shortest must be a decision far from its threshold
+
+
+def geometry_camera_of(case):
+    from helpers import posed_camera
+    return posed_camera(W, H, kx=GEOMETRY_CASES[case]["kx"], **P1)
+
+
+@functools.lru_cache(maxsize=None)
+def geometry_scene(case):
+    """The sizes of full_scene for the case's profile and scale_modifier, copied, every Gaussian flattened along one seeded axis
+    (FLATTEN: that axis becomes the row's shortest scale times the factor), plus "distortion_values" and "median_values" [N], standard normal (of either sign, in no order along the lists)."""
+    c = GEOMETRY_CASES[case]
+    raw = {k: v.copy() for k, v in _sized_scene(c["profile"], c["scale_modifier"]).items()}
+    rng = np.random.default_rng(31)
+    axis, factor = rng.integers(0, 3, N), rng.uniform(*FLATTEN, N)
+    raw["log_scale"][np.arange(N), axis] = raw["log_scale"].min(1) + np.log(factor).astype(np.float32)
+    if c["wide"] != 1.0:
+        o = 1.0 / (1.0 + np.exp(-raw["opacity_logit"][140:148].astype(np.float64))) * c["wide"]
+        raw["opacity_logit"][140:148] = np.log(o / (1.0 - o)).astype(np.float32)
+    raw["distortion_values"] = rng.normal(size=N).astype(np.float32)
+    raw["median_values"] = rng.normal(size=N).astype(np.float32)
+    return raw
+
+
+def geometry_filter_values(case):
+    c = GEOMETRY_CASES[case]
+    return _filter_values_of(c["profile"], c["scale_modifier"]) if c["filter"] else None
+
+
+def geometry_weights(case, seed=37):
+    """dict of float32 weights: w [3,H,W] (zeros where the case has no colour term), wf [C,H,W] or None, and for the maps of
+    the case g_d, g_m [H,W] (a smooth field of one sign on the distortion map, as a mean over the pixels gives it; white noise
+    on the median map) and w_n [3,H,W] (white noise on the normal map, where it carries a linear weight)."""
+    c = GEOMETRY_CASES[case]
+    w, wd = weights()
+    rng = np.random.default_rng(seed)
+    wf = rng.normal(size=(5, H, W)).astype(np.float32)[:c["channels"]] if c["channels"] else None
+    g_d = (1.0 + 0.25 * rng.normal(size=(H, W))).astype(np.float32)
+    g_m = rng.normal(size=(H, W)).astype(np.float32)
+    w_n = rng.normal(size=(3, H, W)).astype(np.float32)
+    return dict(w=w if c["colour"] else np.zeros_like(w), wd=wd if "depth" in c["linear"] else np.zeros_like(wd), wf=wf, g_d=g_d, g_m=g_m, w_n=w_n)
+
+
+def geometry_row_arrays(case, scales, opacities, means3D, rotations, cam, smoothed=None):
+    """full_row_arrays for a GEOMETRY_CASES frame, plus "normal_decisions": normals_ref.gaussian_normals_f32's decisions on the
+    float32 arrays the normals' kernel is handed (the smoothed scales; None for a case without normals)."""
+    import normals_ref
+    c = GEOMETRY_CASES[case]
+    out = _row_arrays(c, geometry_filter_values(case), scales, opacities, means3D, rotations, cam, smoothed)
+    out["normal_decisions"] = (normals_ref.gaussian_normals_f32(means3D, out["scales"], rotations, cam.view, c["profile"])[1]
+                               if c["normals"] else None)
+    return out
+
+
+def geometry_structure_of(case, cam, rows, radii, ranges, values, n_contrib, clamped=None, median_ids=None):
+    """The structure of a GEOMETRY_CASES frame: structure_of, the row decisions of geometry_row_arrays' result `rows`, and the
+    median map's ids (median_ref.forward's on the CPU, the device's on the GPU)."""
+    s = R.with_decisions(structure_of(geometry_scene(case), cam, radii, ranges, values, n_contrib, clamped), rows["masks"], rows["identity"])
+    return R.with_geometry(s, rows["normal_decisions"], median_ids)
+
+
+def geometry_forward_options(case, cut=None):
+    c = GEOMETRY_CASES[case]
+    return dict(background=BG, profile=c["profile"], sh_degree=c["sh_degree"], scale_modifier=c["scale_modifier"], depth=c["depth"],
+                cut=cut, filter_3d=geometry_filter_values(case), antialiased=c["antialiased"], opacity=c["opacity"],
+                distortion=c["distortion"], distortion_power=c["power"], normals=c["normals"], median=c["median"],
+                median_threshold=c["threshold"])
+
+
+def geometry_leaves(case, dtype=R.F64):
+    c, raw = GEOMETRY_CASES[case], geometry_scene(case)
+    return R.leaves(raw, geometry_camera_of(case), dtype=dtype, features=raw["features"][:, :c["channels"]] if c["channels"] else None,
+                    constant=c["constant"], distortion_values=raw["distortion_values"] if c["distortion"] == "values" else None,
+                    median_values=raw["median_values"] if c["median"] == "values" else None)
+
+
+def geometry_loss_terms(case, consistency=None, only=None):
+    """step_autograd_ref.gradients' loss_terms of the case. consistency: dict(decisions=, keep_n=) for a case with a consistency
+    term (None leaves the term out). only: keep just these terms, for the shares of the terms ("distortion", "consistency", ...)."""
+    c, g = GEOMETRY_CASES[case], geometry_weights(case)
+    terms = {}
+    if c["distortion"]:
+        terms["distortion"] = (c["lam_d"], g["g_d"])
+    if c["median"] and "median" in c["linear"]:
+        terms["median"] = g["g_m"]
+    if "normal_map" in c["linear"]:
+        terms["normal_map"] = g["w_n"]
+    if c["surface"] and consistency is not None:
+        terms["consistency"] = dict(weight=c["lam_n"], surface=c["surface"], semantics=c["profile"], **consistency)
+    return terms if only is None else {k: v for k, v in terms.items() if k in only}
+
+
+def surface_of(case, depth, opacity_map, median_map):
+    """The image the consistency term's depth normal reads, in the arrays' own type (numpy): depth / max(opacity, 1e-6), or the
+    median map."""
+    if GEOMETRY_CASES[case]["surface"] == "median":
+        return median_map
+    return depth / np.maximum(opacity_map, opacity_map.dtype.type(1e-6))
+
+
+def geometry_reference_step(case, structure, surface32=None, cut=None, dtype=R.F64, drop=None, keep_n=None, only=None, colour=True):
+    """(grads, color, depth, aux, drop, keep_n) of a GEOMETRY_CASES step on `structure`. surface32: the float32 image the library's
+    depth normals read (surface_of of the float32 maps — the CPU oracle's or the device's), for a case with a consistency term.
+    drop, keep_n: None — decided here by the uncut float64 forward (step_autograd_ref.pixels_to_drop, consistency_pixels).
+    only: the loss terms kept (geometry_loss_terms); colour=False: without the colour term — for the shares of the terms."""
+    import normals_ref
+    c, cam, g = GEOMETRY_CASES[case], geometry_camera_of(case), geometry_weights(case)
+    w = g["w"] if colour else np.zeros_like(g["w"])
+    wf = g["wf"] if (only is None or "features" in only) else None
+    tan = (cam.tan_fovx, cam.tan_fovy)
+    decisions = normals_ref.depth_normals_f32(surface32, tan, c["profile"])[1] if c["surface"] else None
+    if drop is None:
+        none = np.zeros((H, W), bool)
+        _, _, dmap, aux = R.gradients(geometry_leaves(case), structure, cam, w, g["wd"], none, wf=wf,
+                                      loss_terms=geometry_loss_terms(case), **geometry_forward_options(case))
+        drop = R.pixels_to_drop(aux, structure)
+        if c["surface"]:
+            keep_n = R.consistency_pixels(drop, surface_of(case, dmap, aux["opacity_map"], aux.get("median_map")), tan, c["profile"], decisions)
+    consistency = dict(decisions=decisions, keep_n=keep_n) if c["surface"] else None
+    return R.gradients(geometry_leaves(case, dtype), structure, cam, w, g["wd"], drop, dtype=dtype, wf=wf,
+                       loss_terms=geometry_loss_terms(case, consistency, only), **geometry_forward_options(case, cut)) + (drop, keep_n)
 
 
 def weights(seed=17):
